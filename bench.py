@@ -8,7 +8,9 @@ image pairs (weak scaling, no data-path collective inside the SIFT stage).  valu
 max-over-ranks time.  Inputs come from tools/scene.py (PCG32 terrain + texture rendered through
 Image::Camera, ~0.03 features per pixel like the reference's everest imagery).
 
-Besides the contract keys the JSON line carries
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the result line (contract keys
++ `config`).  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).  With `--full` the timed
+steps also carry the stage events, and the JSON line carries besides the contract keys
   roofline      : the DoG-pyramid stage (ssrlcv_hip_sift_build_dog) against HBM, algorithmic bytes 362.25*W*H per image
                   (`frac`; `frac_s1_s8` adds 8d's figure for the extrema search the stage also runs),
                   duration from HIP events around the stage inside the timed steps;
@@ -25,6 +27,7 @@ Besides the contract keys the JSON line carries
   cpu_baseline  : the CPU oracle (oracle/, a port restating the reference's kernels) on BASELINE config[1] -- the 2-view
                   1024 x 1024 pair of the same generator through the whole flow, stage by stage -- plus SIFT on one
                   2048 x 2048 view: one warm-up + median of 5 repetitions per stage, on rank 0's host cores.
+(each leg but the rooflines can be left out of a --full run with its --no-* option).
 """
 import argparse
 import json
@@ -87,6 +90,48 @@ def synth_descriptors(n, seed):
     f["values"] = v.astype(np.uint8)
     f["loc"] = rng.uniform(0, 4096, (n, 2)).astype(np.float32)
     return f
+
+
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much in all
+DUMP_DESCRIPTOR_ROWS = 8192     # descriptors written per image (a seeded sample of the features)
+DUMP_SEED = 0x53524C43
+
+
+def _sample_rows(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k of n rows; every row when k >= n."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, feats):
+    """--dump-outputs: the Feature arrays the last timed step returned (one per image of this rank), as float32 / float64
+    .npy files under out_dir, DUMP_LIMIT_BYTES at most in all, so that two builds can be compared output for output.
+    Per image i, for the rows img<i>_rows (every feature unless that would pass the limit, else a seeded sample):
+    img<i>_loc [n, 2], _sigma, _theta, _parent, _descriptor_sum (sum of the 128 bytes) and _descriptor_wsum (sum of
+    (k + 1) * byte k; both sums are exact in float32); and the 128 bytes themselves, img<i>_descriptors [m, 128], for the
+    seeded sample img<i>_descriptor_rows of m = min(n, DUMP_DESCRIPTOR_ROWS) features (fewer with many images).
+    num_features: the count per image.  The feature order is the library's, which is deterministic."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"num_features": np.array([len(f) for f in feats], np.float64)}
+    desc_k = min(DUMP_DESCRIPTOR_ROWS, DUMP_LIMIT_BYTES // 2 // ((128 * 4 + 8) * len(feats)))   # half the budget at most
+    desc_rows = [_sample_rows(len(f), desc_k, DUMP_SEED + 2 * i + 1) for i, f in enumerate(feats)]
+    room = DUMP_LIMIT_BYTES - (1 << 20) - sum(len(r) * (128 * 4 + 8) for r in desc_rows)   # 1 MB for the .npy headers
+    per_row = 4 * (2 + 5) + 8                                                              # the float32 fields + the row index
+    weights = np.arange(1, 129, dtype=np.float32)
+    for i, (f, dr) in enumerate(zip(feats, desc_rows)):
+        rows = _sample_rows(len(f), room // (per_row * len(feats)), DUMP_SEED + 2 * i)
+        s = f[rows]
+        values = s["values"].astype(np.float32)
+        arrays.update({"img%d_rows" % i: rows.astype(np.float64), "img%d_loc" % i: s["loc"].astype(np.float32),
+                       "img%d_sigma" % i: s["sigma"].astype(np.float32), "img%d_theta" % i: s["theta"].astype(np.float32),
+                       "img%d_parent" % i: s["parent"].astype(np.float32),
+                       "img%d_descriptor_sum" % i: values.sum(1), "img%d_descriptor_wsum" % i: values @ weights,
+                       "img%d_descriptors" % i: f["values"][dr].astype(np.float32),
+                       "img%d_descriptor_rows" % i: dr.astype(np.float64)})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    assert sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in arrays) <= DUMP_LIMIT_BYTES
 
 
 def git_head():
@@ -623,6 +668,40 @@ def run_pushbroom(args, torch, dist, world, rank, dev, size, views):
     return out
 
 
+def full_legs(args, line, torch, dist, capi, world, rank, dev, imgs, W):
+    """--full: the legs after the headline, in the order every rank enters them (rank 0 adds their results to `line`)."""
+    img0 = imgs[0]
+    del imgs[1:]
+    torch.cuda.empty_cache()
+    if not args.no_nview:
+        # every rank enters the N-view leg together (the barrier inside run_nview): the rank-0-only legs come after it,
+        # so that its stage times are not polluted by rank skew
+        nviews = args.nview_views if args.nview_views > 0 else max(4, world)
+        nv = run_nview(args, torch, dist, capi, world, rank, dev, nviews, args.nview_size, max(args.nview_steps, 1), 2)
+        nv_inputs = nv.pop("_inputs")
+        if rank == 0:
+            line["nview"] = nv
+    if not args.no_pushbroom:
+        # config[4]; every rank enters together (its exchanges are collectives), before the rank-0-only legs
+        torch.cuda.empty_cache()
+        pb = run_pushbroom(args, torch, dist, world, rank, dev, args.pushbroom_size, args.pushbroom_views if args.pushbroom_views > 0 else max(8, world))
+        if rank == 0:
+            line["pushbroom8"] = pb
+        torch.cuda.empty_cache()
+    if rank == 0:
+        if not args.no_class_api:
+            line["class_api"] = class_api_leg(img0, W, line["value"] / world)
+            if not args.no_nview and world == 1:
+                line["class_api"]["flow"] = class_api_flow_leg(nv_inputs[0], nv_inputs[1], args.nview_size, nv["ms_per_step_stats_rank0"]["median"], nv_inputs[2])
+        if not args.no_matcher:
+            line["matcher"] = bench_matcher(capi, torch, args.match_n, args.match_n, args.match_iters)
+            line["matcher_f16"] = bench_matcher(capi, torch, args.match_n, args.match_n, args.match_iters, "f16")
+            line["matcher_f16"]["same_output_as_int8"] = line["matcher_f16"]["checksum"] == line["matcher"]["checksum"]
+            line["matcher_epipolar"] = bench_matcher_epipolar(capi, torch, args.match_n, W, args.match_iters)
+        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a single-GPU-run figure
+            line["cpu_baseline"] = cpu_baseline(args.cpu_size, args.cpu_big, args.cpu_reps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -648,7 +727,13 @@ def main():
     ap.add_argument("--pushbroom-size", type=int, default=8192)
     ap.add_argument("--pushbroom-views", type=int, default=0, help="0 = max(8, world)")
     ap.add_argument("--noise-input", action="store_true", help="round-1 input: multi-scale noise instead of the scene generator")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: stage events in the timed steps, the rooflines, and the N-view, pushbroom, class-API, "
+                         "matcher and CPU-baseline legs (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -703,7 +788,8 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    events = [[[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in plans] for _ in range(args.steps)]
+    # stage events in the timed steps only for --full's rooflines: a plain run times the bare steps
+    events = [[[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in plans] if args.full else None for _ in range(args.steps)]
     t0 = time.perf_counter()
     for k in range(args.steps):
         step(events[k])
@@ -716,45 +802,33 @@ def main():
     for p in plans:
         p.set_stage_event(None)
     nfeat = [p.count() for p in plans]  # raises if a key-point list overflowed its capacity (truncated result)
-    pyr_ms = float(np.mean([e[0].elapsed_time(e[1]) for st in events for e in st]))
-    desc_ms = float(np.mean([e[1].elapsed_time(e[2]) for st in events for e in st]))
-    # The scale-space stage ALONE (ssrlcv_hip_sift_build_dog as its own call, a few back-to-back launches per image, HIP events
-    # on the launching stream; outside the timed region): inside the fused extract octave 0's list chain of the key-point
-    # stage runs beside the stage's tail since round 5, so the stage-boundary event there sees a longer scale-space stage.
-    alone = []
-    for p, im in zip(plans, imgs):
-        for _ in range(2):
-            p.build_dog(im)
-        torch.cuda.synchronize()
-        a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a0.record()
-        for _ in range(5):
-            p.build_dog(im)
-        a1.record()
-        torch.cuda.synchronize()
-        alone.append(a0.elapsed_time(a1) / 5)
-    alone_ms = float(np.mean(alone))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [p.features_host(_H.FEATURE) for p in plans])
+    if args.full:
+        pyr_ms = float(np.mean([e[0].elapsed_time(e[1]) for st in events for e in st]))
+        desc_ms = float(np.mean([e[1].elapsed_time(e[2]) for st in events for e in st]))
+        # The scale-space stage ALONE (ssrlcv_hip_sift_build_dog as its own call, a few back-to-back launches per image, HIP events
+        # on the launching stream; outside the timed region): inside the fused extract octave 0's list chain of the key-point
+        # stage runs beside the stage's tail since round 5, so the stage-boundary event there sees a longer scale-space stage.
+        alone = []
+        for p, im in zip(plans, imgs):
+            for _ in range(2):
+                p.build_dog(im)
+            torch.cuda.synchronize()
+            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a0.record()
+            for _ in range(5):
+                p.build_dog(im)
+            a1.record()
+            torch.cuda.synchronize()
+            alone.append(a0.elapsed_time(a1) / 5)
+        alone_ms = float(np.mean(alone))
     del plans
 
     line = None
     if rank == 0:
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "r06_pyramid_traffic.json" if os.path.exists(os.path.join(ROOT, "profiles", "r06_pyramid_traffic.json")) else "r05_pyramid_traffic.json")
-        if W == 4096 and H_ == 4096 and os.path.exists(tpath):
-            # HBM bytes of the pyramid stage per image from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the stage
-            # benchmark (collected off-line: counters cannot be read from inside the timed run)
-            tj = json.load(open(tpath))
-            traffic, traffic_src = tj["pyramid_stage_bytes_per_image"], "profiles/%s @ %s" % (os.path.basename(tpath), tj.get("commit"))
         pixels_per_step = world * args.images * W * H_
         value = pixels_per_step * args.steps / dt / 1e6
-        # Algorithmic bytes of the stage.  `frac` is priced on SURVEY.md 8(d)'s / BASELINE.md section 4's own figure,
-        # B_pyr = 362.25 W H (S1-S7: u8 once, 6 levels per octave written and read once, 5 DoG levels written) -- the
-        # definition of rounds 1-2 and of the 0.70 target.  The stage also runs S8 (findExtrema) in the same pass since
-        # round 3; SURVEY's figure for it is 20 B read + 1 B written per scale-space pixel = 111.56 W H, reported as the
-        # secondary, separately labelled `frac_s1_s8` (round 3 called THAT figure `frac`: 0.58 there is 0.44 here).
-        b_pyr = 362.25 * W * H_
-        b_ext = 21.0 * 5.3125 * W * H_
-        achieved = b_pyr / (pyr_ms * 1e-3) / 1e9
         line = {
             "metric": "Mpix/s SIFT extract (+ Mmatches/s 128-D brute-force, see `matcher`)",
             "value": value, "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -764,6 +838,24 @@ def main():
                                    "path) on each image, pixels resident in HBM" % (W, H_, workload),
                        "images_per_gpu": args.images, "features_per_image": nfeat, "parallelism": "image-pair shard",
                        "library": "%s build (%s)" % (_lib.flavour(), os.path.basename(_lib.LIB_PATH))},
+        }
+    if rank == 0 and args.full:
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, "profiles", "r06_pyramid_traffic.json" if os.path.exists(os.path.join(ROOT, "profiles", "r06_pyramid_traffic.json")) else "r05_pyramid_traffic.json")
+        if W == 4096 and H_ == 4096 and os.path.exists(tpath):
+            # HBM bytes of the pyramid stage per image from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the stage
+            # benchmark (collected off-line: counters cannot be read from inside the timed run)
+            tj = json.load(open(tpath))
+            traffic, traffic_src = tj["pyramid_stage_bytes_per_image"], "profiles/%s @ %s" % (os.path.basename(tpath), tj.get("commit"))
+        # Algorithmic bytes of the stage.  `frac` is priced on SURVEY.md 8(d)'s / BASELINE.md section 4's own figure,
+        # B_pyr = 362.25 W H (S1-S7: u8 once, 6 levels per octave written and read once, 5 DoG levels written) -- the
+        # definition of rounds 1-2 and of the 0.70 target.  The stage also runs S8 (findExtrema) in the same pass since
+        # round 3; SURVEY's figure for it is 20 B read + 1 B written per scale-space pixel = 111.56 W H, reported as the
+        # secondary, separately labelled `frac_s1_s8` (round 3 called THAT figure `frac`: 0.58 there is 0.44 here).
+        b_pyr = 362.25 * W * H_
+        b_ext = 21.0 * 5.3125 * W * H_
+        achieved = b_pyr / (pyr_ms * 1e-3) / 1e9
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": "scale-space stage = ssrlcv_hip_sift_build_dog: S1-S8 (u8 upsample in the first level's loader, "
@@ -784,7 +876,7 @@ def main():
                                                  "fused extract, where octave 0's list chain of the key-point stage runs beside the "
                                                  "stage's tail (round 5: the step gains what the stage-boundary event loses)"}},
             "describe": describe_roofline(desc_ms, int(np.mean(nfeat)), W),
-        }
+        })
         fpath = os.path.join(ROOT, "profiles", "r06_pyramid_floor.json")
         if W == 4096 and H_ == 4096 and os.path.exists(fpath):
             # per-launch floor table of the stage (tools/collect_floor.sh + tools/pyramid_floor.py, serial run under rocprofv3):
@@ -799,36 +891,9 @@ def main():
                 "largest_gaps": [{"kernel": r["kernel"], "octave": r.get("octave"), "level": r.get("level"), "solo_us": r["solo_us"],
                                   "copy_floor_us": r.get("copy_floor_us"), "issue_floor_us": r.get("issue_floor_us"), "gap_us": r["gap_us"]}
                                  for r in sorted(rows, key=lambda r: -r["gap_us"])[:6]]}
-    img0 = imgs[0]
-    del imgs[1:]
-    torch.cuda.empty_cache()
-    if not args.no_nview:
-        # every rank enters the N-view leg together (the barrier inside run_nview): the rank-0-only legs come after it,
-        # so that its stage times are not polluted by rank skew
-        nviews = args.nview_views if args.nview_views > 0 else max(4, world)
-        nv = run_nview(args, torch, dist, capi, world, rank, dev, nviews, args.nview_size, max(args.nview_steps, 1), 2)
-        nv_inputs = nv.pop("_inputs")
-        if rank == 0:
-            line["nview"] = nv
-    if not args.no_pushbroom:
-        # config[4]; every rank enters together (its exchanges are collectives), before the rank-0-only legs
-        torch.cuda.empty_cache()
-        pb = run_pushbroom(args, torch, dist, world, rank, dev, args.pushbroom_size, args.pushbroom_views if args.pushbroom_views > 0 else max(8, world))
-        if rank == 0:
-            line["pushbroom8"] = pb
-        torch.cuda.empty_cache()
+    if args.full:
+        full_legs(args, line, torch, dist, capi, world, rank, dev, imgs, W)
     if rank == 0:
-        if not args.no_class_api:
-            line["class_api"] = class_api_leg(img0, W, line["value"] / world)
-            if not args.no_nview and world == 1:
-                line["class_api"]["flow"] = class_api_flow_leg(nv_inputs[0], nv_inputs[1], args.nview_size, nv["ms_per_step_stats_rank0"]["median"], nv_inputs[2])
-        if not args.no_matcher:
-            line["matcher"] = bench_matcher(capi, torch, args.match_n, args.match_n, args.match_iters)
-            line["matcher_f16"] = bench_matcher(capi, torch, args.match_n, args.match_n, args.match_iters, "f16")
-            line["matcher_f16"]["same_output_as_int8"] = line["matcher_f16"]["checksum"] == line["matcher"]["checksum"]
-            line["matcher_epipolar"] = bench_matcher_epipolar(capi, torch, args.match_n, W, args.match_iters)
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a single-GPU-run figure
-            line["cpu_baseline"] = cpu_baseline(args.cpu_size, args.cpu_big, args.cpu_reps)
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()
