@@ -39,8 +39,9 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *   1  rounds 1-4 (unversioned)
  *   2  round 5: ssrlcv_hip_merge_matches counts[2] -> counts[4] and one argument fewer; select_pair_bundles,
  *      set/get_match_arithmetic, ssrlcv_sift_plan_set_stage_event added
- *   3  round 6: ssrlcv_hip_abi_version itself */
-#define SSRLCV_HIP_ABI_VERSION 3
+ *   3  round 6: ssrlcv_hip_abi_version itself
+ *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added */
+#define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
 const char* ssrlcv_hip_status_string(int status);
@@ -109,6 +110,63 @@ int ssrlcv_hip_pose_lm_terms(const ssrlcv_match* matches, uint32_t numMatches, c
 /* computeCost alone (:731-740), for the trial poses of the inner LM loop; cost: one device float. */
 int ssrlcv_hip_pose_cost(const ssrlcv_match* matches, uint32_t numMatches, const ssrlcv_pose* pose,
                          const ssrlcv_camera* query, const ssrlcv_camera* target, float* cost, ssrlcv_stream_t stream);
+
+/* ---- fundamental-matrix RANSAC and relative pose (PoseEstimator::estimatePoseRANSAC, src/PoseEstimator.cu:92-312) ----
+ * PARITY UNPINNED: the reference holds no fixture for this path; these conventions are this library's own.
+ *   matches     ssrlcv_match: q = keyPoints[0].loc (query pixel), t = keyPoints[1].loc (target pixel).  A match with
+ *               invalid != 0 is never an inlier; a sample that draws one yields no candidate.
+ *   constraint  t~^T F q~ = 0 with q~ = (q.x, q.y, 1).  Every F is row-major float[9] in pixel coordinates, scaled to unit
+ *               Frobenius norm, sign fixed so that the entry of largest magnitude is positive (lowest index on ties).
+ *   inlier      Sampson distance below `threshold` px:
+ *               (t~^T F q~)^2 < threshold^2 ((F q~)_0^2 + (F q~)_1^2 + (F^T t~)_0^2 + (F^T t~)_1^2); a zero denominator
+ *               is not an inlier.
+ *   normalise   one similarity per image: translate by the centre of that image's bounding box of the VALID match
+ *               locations; one common scale s = 2 / (largest extent of either box).  Solving and scoring run in
+ *               normalised coordinates with threshold s * threshold (the Sampson distance scales by s exactly).  A pixel
+ *               F is taken to normalised coordinates in float64 and rescaled to unit norm before it is tested, so a
+ *               candidate scores the same in the RANSAC and in ssrlcv_hip_fmatrix_score.
+ *   samples     sample h (0 <= h < numSamples): for j = 0, 1, ... z = seed + (h 2^32 + j + 1) 0x9E3779B97F4A7C15 (mod 2^64),
+ *               splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9; z ^= z >> 27, z *= 0x94D049BB133111EB;
+ *               z ^= z >> 31), index ((z >> 32) numMatches) >> 32; duplicates skipped until 7 distinct indices, at most
+ *               64 draws (else no candidate).
+ *   solver      float64: null space F1, F2 of the 7x9 system (Householder), real roots of det(a F1 + (1 - a) F2) in
+ *               ascending order (cubic through its values at a = 0, 1, -1, 2; when the leading coefficient is below
+ *               1e-12 of the largest the lower-degree polynomial is solved), candidate r of sample h in slot 3 h + r,
+ *               denormalised to pixels.  Empty slots: F all zero, count 0.
+ *   best        largest count, lowest slot on ties (one 64-bit atomicMax of (count << 32 | ~slot)).
+ *   refit       always: least-squares 8-point fit on the best candidate's inliers (9x9 float64 normal matrix from
+ *               per-block partials summed in block order, Jacobi eigenvector of the smallest eigenvalue, rank 2 through
+ *               the 3x3 SVD); kept when it has at least as many inliers.
+ *   determinism two calls with the same inputs give bit-equal F, count, mask, candidates and counts (integer counts, no
+ *               float atomics).
+ * Fewer than 7 matches, fewer than 7 valid ones, or no candidate with an inlier: SSRLCV_OK, count 0, F all zero. */
+/* the scratch of fmatrix_score and pose_from_fmatrix: a workspace of at least this many bytes */
+#define SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES 256
+size_t ssrlcv_hip_fmatrix_ransac_workspace_bytes(uint32_t numMatches, uint32_t numSamples);
+/* F_out: 9 floats; inlierCount_out: one uint32; inlierMask_out (NULL: none): numMatches bytes, 1 = inlier of F_out;
+ * candidates_out (NULL: none): 27 numSamples floats; counts_out (NULL: none): 3 numSamples uint32.  All device memory.
+ * Fully stream-ordered (no host synchronisation), so it may be captured into a graph.
+ * SSRLCV_ERR_INVALID_ARG: matches, F_out, inlierCount_out or workspace NULL, numSamples 0 or above 2^26, threshold not
+ * a positive finite number.  SSRLCV_ERR_WORKSPACE: workspaceBytes below the query. */
+int ssrlcv_hip_fmatrix_ransac(const ssrlcv_match* matches, uint32_t numMatches, uint32_t numSamples, float threshold,
+                              uint64_t seed, void* workspace, size_t workspaceBytes, float* F_out,
+                              uint32_t* inlierCount_out, uint8_t* inlierMask_out, float* candidates_out,
+                              uint32_t* counts_out, ssrlcv_stream_t stream);
+/* The RANSAC's scoring kernel on its own: counts_out[i] = inliers of F[9 i .. 9 i + 8] (k candidates, device), with
+ * the normalisation above taken from these matches.  inlierMask_out only with k == 1.  Stream-ordered. */
+int ssrlcv_hip_fmatrix_score(const ssrlcv_match* matches, uint32_t numMatches, const float* F, uint32_t k, float threshold,
+                             void* workspace, size_t workspaceBytes, uint32_t* counts_out, uint8_t* inlierMask_out,
+                             ssrlcv_stream_t stream);
+/* Relative pose from F (device, 9 floats) in the convention pose_lm_terms consumes: the target ray rotated by
+ * (roll, pitch, yaw), placed at (x, y, z) in the query camera's frame.  Intrinsics of the ray model:
+ * K = [[foc / dpix.x, 0, size.x / 2], [0, foc / dpix.y, size.y / 2], [0, 0, 1]], E = K_t^T F K_q projected to singular
+ * values (1, 1, 0); of its four (R, C) the one with the most matches whose two ray depths are positive wins (device
+ * vote, integer counts, lowest candidate on ties) over the matches with inlierMask != 0 (NULL: every valid match).
+ * Angles: getAxisRotations of the rotation; position: the unit direction of C times |target.cam_pos - query.cam_pos| / 1000
+ * (LM_optimize's scale).  Synchronous.  F all zero: SSRLCV_ERR_INVALID_ARG. */
+int ssrlcv_hip_pose_from_fmatrix(const ssrlcv_match* matches, uint32_t numMatches, const uint8_t* inlierMask,
+                                 const float* F, const ssrlcv_camera* query_host, const ssrlcv_camera* target_host,
+                                 void* workspace, size_t workspaceBytes, ssrlcv_pose* pose_host, ssrlcv_stream_t stream);
 
 /* ============================== M: matching ======================================================= */
 

@@ -35,7 +35,7 @@ class HipAbiMismatch(RuntimeError):
 
 
 # the SSRLCV_HIP_ABI_VERSION of include/ssrlcv_hip.h this package's ctypes signatures (capi.py) were written against
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 def load():
@@ -57,7 +57,8 @@ def load():
         _lib.ssrlcv_hip_status_string.restype = ctypes.c_char_p
         for name in ("ssrlcv_hip_match_workspace_bytes", "ssrlcv_sift_plan_workspace_bytes",
                      "ssrlcv_hip_ba_sweep2_workspace_bytes", "ssrlcv_hip_sort_workspace_bytes",
-                     "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes"):
+                     "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes",
+                     "ssrlcv_hip_fmatrix_ransac_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
     return _lib
@@ -71,6 +72,8 @@ EXPORTED = [
     "ssrlcv_hip_generate_bundles", "ssrlcv_hip_generate_pushbroom_bundles", "ssrlcv_hip_triangulate2",
     "ssrlcv_hip_triangulateN", "ssrlcv_hip_ba_sweep2_workspace_bytes", "ssrlcv_hip_ba_sweep2",
     "ssrlcv_hip_pose_lm_terms", "ssrlcv_hip_pose_cost",
+    "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_fmatrix_ransac", "ssrlcv_hip_fmatrix_score",
+    "ssrlcv_hip_pose_from_fmatrix",
     "ssrlcv_projection_matrix_host", "ssrlcv_hip_match_workspace_bytes", "ssrlcv_hip_set_match_arithmetic", "ssrlcv_hip_get_match_arithmetic", "ssrlcv_hip_seed_distances_u8x128",
     "ssrlcv_hip_match_u8x128", "ssrlcv_hip_compact_matches", "ssrlcv_hip_compact_matches_async", "ssrlcv_hip_keypoints_from_members",
     "ssrlcv_hip_matchset_from_matches", "ssrlcv_merge_matches_host", "ssrlcv_merge_matches_host_mode", "ssrlcv_host_free", "ssrlcv_assign_pairs_host",

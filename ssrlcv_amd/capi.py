@@ -182,6 +182,53 @@ def pose_cost(matches_d, n, pose6, query_cam_np, target_cam_np):
     return float(out.item())
 
 
+# ------------------------------------------------------------------ fundamental-matrix RANSAC / relative pose
+FMATRIX_AUX_WORKSPACE_BYTES = 256  # SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES
+
+
+def fmatrix_ransac(matches_d, n, samples, threshold, seed=0, mask=False, candidates=False):
+    """-> dict(F[3, 3] float32, count, mask (uint8[n] or None), candidates (float32[3 samples, 9] or None),
+    counts (uint32[3 samples] or None)) of ssrlcv_hip_fmatrix_ransac; matches_d: MATCH records on the device."""
+    ws = dev_bytes(LIB.ssrlcv_hip_fmatrix_ransac_workspace_bytes(c_u32(n), c_u32(samples)))
+    F = torch.empty(9, dtype=torch.float32, device="cuda")
+    cnt = torch.empty(1, dtype=torch.int32, device="cuda")
+    m = dev_bytes(n) if mask else None
+    cand = torch.empty(27 * samples, dtype=torch.float32, device="cuda") if candidates else None
+    counts = torch.empty(3 * samples, dtype=torch.int32, device="cuda") if candidates else None
+    check(LIB.ssrlcv_hip_fmatrix_ransac(ptr(matches_d), c_u32(n), c_u32(samples), c_f32(threshold), ctypes.c_uint64(seed),
+                                        ptr(ws), c_sz(ws.numel()), ptr(F), ptr(cnt), ptr(m), ptr(cand), ptr(counts),
+                                        stream_ptr()))
+    return {"F": F.cpu().numpy().reshape(3, 3), "count": int(cnt.item()),
+            "mask": m.cpu().numpy()[:n].copy() if mask else None,
+            "candidates": cand.cpu().numpy().reshape(-1, 9) if candidates else None,
+            "counts": counts.cpu().numpy().view(np.uint32).copy() if candidates else None}
+
+
+def fmatrix_score(matches_d, n, F, threshold, mask=False):
+    """-> (counts uint32[k], mask uint8[n] or None): inliers of each of the k pixel F matrices (numpy [k, 9] or [3, 3])."""
+    Fh = np.ascontiguousarray(np.asarray(F, np.float32).reshape(-1, 9))
+    k = len(Fh)
+    Fd = torch.from_numpy(Fh.reshape(-1).copy()).cuda()
+    ws = dev_bytes(FMATRIX_AUX_WORKSPACE_BYTES)
+    counts = torch.empty(k, dtype=torch.int32, device="cuda")
+    m = dev_bytes(n) if mask else None
+    check(LIB.ssrlcv_hip_fmatrix_score(ptr(matches_d), c_u32(n), ptr(Fd), c_u32(k), c_f32(threshold), ptr(ws),
+                                       c_sz(ws.numel()), ptr(counts), ptr(m), stream_ptr()))
+    return counts.cpu().numpy().view(np.uint32).copy(), (m.cpu().numpy()[:n].copy() if mask else None)
+
+
+def pose_from_fmatrix(matches_d, n, mask_d, F, query_cam_np, target_cam_np):
+    """-> pose6 float32 (roll, pitch, yaw, x, y, z) of ssrlcv_hip_pose_from_fmatrix; mask_d: uint8 device tensor or None."""
+    Fd = torch.from_numpy(np.ascontiguousarray(np.asarray(F, np.float32).reshape(9))).cuda()
+    q, t = _host_bytes(query_cam_np, 80), _host_bytes(target_cam_np, 80)
+    ws = dev_bytes(FMATRIX_AUX_WORKSPACE_BYTES)
+    pose = np.zeros(6, np.float32)
+    check(LIB.ssrlcv_hip_pose_from_fmatrix(ptr(matches_d), c_u32(n), ptr(mask_d), ptr(Fd), q.ctypes.data_as(c_vp),
+                                           t.ctypes.data_as(c_vp), ptr(ws), c_sz(ws.numel()), pose.ctypes.data_as(c_vp),
+                                           stream_ptr()))
+    return pose
+
+
 # ------------------------------------------------------------------ matching
 def projection_matrix(camera_np):
     cam = np.ascontiguousarray(camera_np).view(np.uint8).reshape(-1)[:80].copy()

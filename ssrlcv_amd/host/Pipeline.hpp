@@ -9,9 +9,11 @@
 //   * the 2-view MatchSet (src/Pipeline.cu:198-224) is assembled ON THE DEVICE from the validated
 //     DMatch list by ssrlcv_hip_matchset_from_matches, which also reduces the largest descriptor distance -- upstream
 //     copies the list to the host twice (once for a max loop, once sliced to Match) and fills both arrays in a loop;
-//   * the relative-pose arithmetic of the pose stage lives in two small functions that the tests can call.
+//   * the relative-pose arithmetic of the pose stage lives in two small functions that the tests can call;
+//   * the pose stage refines the cameras' relative pose with LM as upstream does; PoseEstimator::estimatePoseRANSAC is
+//     built but, as upstream (src/Pipeline.cu:101), not on this path.
 // Out of scope at this edge: image decoding (images arrive as `.cpimg` + `<id>_h.uty` pixel
-// checkpoints, or as ready Image objects), PoseEstimator::estimatePoseRANSAC (disabled upstream too), MeshFactory
+// checkpoints, or as ready Image objects), MeshFactory
 // (its setPoints + savePoints pair is the ASCII PLY dump: writePLY).
 #pragma once
 #include <sys/stat.h>
@@ -102,28 +104,7 @@ inline void reportError(const std::string& label, float value) {
   logger.info << line.str();
 }
 
-// Pose of camera `b` seen from camera `a`: position = (a - b) turned back through a's z, y, x rotations, angles = the
-// axis rotations of Ra^T Rb (the starting point the reference hands to its LM refinement, src/Pipeline.cu:103-119).
-inline Pose relativePose(const Image::Camera& a, const Image::Camera& b) {
-  float3 t = a.cam_pos - b.cam_pos;
-  const float3 axes[3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}};
-  const float turn[3] = {-a.cam_rot.z, -a.cam_rot.y, -a.cam_rot.x};
-  for (int k = 0; k < 3; ++k) t = rotatePointArbitrary(t, axes[k], turn[k]);
-  float Ra[3][3], RaT[3][3], Rb[3][3], Rab[3][3];
-  getRotationMatrix(a.cam_rot, Ra);
-  transpose(Ra, RaT);
-  getRotationMatrix(b.cam_rot, Rb);
-  multiply(RaT, Rb, Rab);
-  const float3 angles = getAxisRotations(Rab);
-  Pose p;
-  p.roll = angles.x;
-  p.pitch = angles.y;
-  p.yaw = angles.z;
-  p.x = t.x;
-  p.y = t.y;
-  p.z = t.z;
-  return p;
-}
+// relativePose (the pose stage's starting point) lives in PoseEstimator.hpp, whose RANSAC falls back to it.
 
 // The inverse step: put camera `b` where `pose` (relative to `a`, position in units of 1000) says it is (:127-136).
 inline void applyRelativePose(const Image::Camera& a, const Pose& pose, Image::Camera& b) {

@@ -1,8 +1,9 @@
 // ssrlcv_amd/host/PoseEstimator.hpp -- ssrlcv::PoseEstimator's Levenberg-Marquardt refinement of the relative pose
 // (include/PoseEstimator.cuh:30-61, src/PoseEstimator.cu:314-515) over the fused HIP terms kernel
-// (ssrlcv_hip_pose_lm_terms / ssrlcv_hip_pose_cost).  estimatePoseRANSAC (7-point F-matrix RANSAC, :92-312) is not
-// built: the reference's own stage flow has it commented out (src/Pipeline.cu:101) and starts LM from the
-// cameras' relative pose.
+// (ssrlcv_hip_pose_lm_terms / ssrlcv_hip_pose_cost), and estimatePoseRANSAC (:92-312) over the device 7-point F-matrix
+// RANSAC (ssrlcv_hip_fmatrix_ransac, conventions in include/ssrlcv_hip.h; PARITY UNPINNED) and the E decomposition with
+// its cheirality vote (ssrlcv_hip_pose_from_fmatrix).  The reference's own stage flow has the RANSAC commented out
+// (src/Pipeline.cu:101) and starts LM from the cameras' relative pose; doPoseEstimation here does the same.
 //
 // LM_iteration follows upstream step for step: terms at the current pose; then up to 20 trial steps with
 // JTJ + lambda I, pseudo-inverse with singular values <= 1e-4 dropped (cusolverDnSgesvd upstream, pseudoInverse()
@@ -31,6 +32,31 @@ struct Pose {
 };
 static_assert(sizeof(Pose) == sizeof(ssrlcv_pose), "Pose layout");
 
+namespace stage {
+// Pose of camera `b` seen from camera `a`: position = (a - b) turned back through a's z, y, x rotations, angles = the
+// axis rotations of Ra^T Rb (the starting point the reference hands to its LM refinement, src/Pipeline.cu:103-119).
+inline Pose relativePose(const Image::Camera& a, const Image::Camera& b) {
+  float3 t = a.cam_pos - b.cam_pos;
+  const float3 axes[3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}};
+  const float turn[3] = {-a.cam_rot.z, -a.cam_rot.y, -a.cam_rot.x};
+  for (int k = 0; k < 3; ++k) t = rotatePointArbitrary(t, axes[k], turn[k]);
+  float Ra[3][3], RaT[3][3], Rb[3][3], Rab[3][3];
+  getRotationMatrix(a.cam_rot, Ra);
+  transpose(Ra, RaT);
+  getRotationMatrix(b.cam_rot, Rb);
+  multiply(RaT, Rb, Rab);
+  const float3 angles = getAxisRotations(Rab);
+  Pose p;
+  p.roll = angles.x;
+  p.pitch = angles.y;
+  p.yaw = angles.z;
+  p.x = t.x;
+  p.y = t.y;
+  p.z = t.z;
+  return p;
+}
+}  // namespace stage
+
 class PoseEstimator {
  private:
   ptr::value<Unity<Match>> matches;  // keypoints should be (query, target)
@@ -47,14 +73,66 @@ class PoseEstimator {
     return h;
   }
 
+  // the RANSAC call behind both public methods; mask / F (device) receive the inlier mask and F when not null
+  FMatrixInliers fmatrixRANSAC(unsigned samples, float threshold, uint64_t seed, ptr::device<unsigned char>* mask,
+                               ptr::device<float>* Fdev = nullptr) {
+    MemoryState origin = matches->getMemoryState();
+    if (origin == cpu || matches->getFore() == cpu) matches->transferMemoryTo(gpu);
+    const uint32_t n = (uint32_t)matches->size();
+    ptr::device<unsigned char> ws(ssrlcv_hip_fmatrix_ransac_workspace_bytes(n, samples));
+    ptr::device<float> Fown(9);
+    ptr::device<uint32_t> count(1);
+    float* Fd = Fdev ? Fdev->get() : Fown.get();
+    HipSafeCall(ssrlcv_hip_fmatrix_ransac((const ssrlcv_match*)matches->device.get(), n, samples, threshold, seed, ws.get(),
+                                          ssrlcv_hip_fmatrix_ransac_workspace_bytes(n, samples), Fd, count.get(),
+                                          mask ? mask->get() : nullptr, nullptr, nullptr, nullptr));
+    FMatrixInliers out;
+    uint32_t c = 0;
+    HipSafeCall(ssrlcv_hip_memcpy(&out.fmatrix[0][0], Fd, 9 * sizeof(float), 1));
+    HipSafeCall(ssrlcv_hip_memcpy(&c, count.get(), sizeof c, 1));
+    out.inliers = c;
+    out.valid = c >= 7;
+    if (origin == cpu) matches->setMemoryState(cpu);
+    return out;
+  }
+
  public:
   // Sets up pose estimator to adjust target image
   PoseEstimator(ptr::value<Image> query, ptr::value<Image> target, ptr::value<Unity<Match>> matches)
       : matches(matches), query(query), target(target) {}
 
+  // 7-point F-matrix RANSAC over `samples` fixed samples (sample hash seeded by `seed`), inlier = Sampson distance below
+  // `threshold` px, one least-squares refit; fmatrix row-major in pixels, unit norm.  valid = at least 7 inliers.
+  FMatrixInliers estimateFMatrixRANSAC(unsigned samples = 4096, float threshold = 1.0f, uint64_t seed = 0) {
+    return fmatrixRANSAC(samples, threshold, seed, nullptr);
+  }
+
+  // estimateFMatrixRANSAC with its defaults, then the relative pose of E = K_t^T F K_q (the cheirality vote on its
+  // inliers), in LM_optimize's convention.  Without a valid F: an error in the log and the cameras' own relative pose.
   Pose estimatePoseRANSAC() {
-    logger.err << "PoseEstimator::estimatePoseRANSAC is not part of this build (SURVEY.md section 8f item 3)";
-    exit(-1);
+    MemoryState origin = matches->getMemoryState();
+    if (origin == cpu || matches->getFore() == cpu) matches->transferMemoryTo(gpu);
+    const unsigned long n = matches->size();
+    ptr::device<unsigned char> mask(n ? n : 1);
+    ptr::device<float> F(9);
+    FMatrixInliers fm = fmatrixRANSAC(4096, 1.0f, 0, &mask, &F);
+    Pose pose;
+    if (fm.valid) {
+      ptr::device<unsigned char> aux(SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES);
+      HipSafeCall(ssrlcv_hip_pose_from_fmatrix((const ssrlcv_match*)matches->device.get(), (uint32_t)n, mask.get(), F.get(),
+                                               (const ssrlcv_camera*)&query->camera, (const ssrlcv_camera*)&target->camera,
+                                               aux.get(), SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES, (ssrlcv_pose*)&pose, nullptr));
+    } else {
+      logger.err.printf("PoseEstimator::estimatePoseRANSAC: no valid F-matrix (%lu inliers); using the cameras' relative pose",
+                        fm.inliers);
+      pose = stage::relativePose(query->camera, target->camera);
+      const float3 b = baselineInQueryFrame();
+      pose.x = b.x / 1000;
+      pose.y = b.y / 1000;
+      pose.z = b.z / 1000;
+    }
+    if (origin == cpu) matches->setMemoryState(cpu);
+    return pose;
   }
 
   // PoseEstimator::LM_optimize (src/PoseEstimator.cu:314-341): the start position is the baseline between the two cameras
