@@ -33,14 +33,17 @@ extern "C" {
 typedef void* ssrlcv_stream_t; /* hipStream_t */
 
 /* ABI version: bumped on EVERY change of an exported signature, of a struct layout in ssrlcv_types.h or of the meaning of
- * an argument (additions included).  A caller compiled against this header compares the library it loaded with the
- * number it was built for before the first call: the C++ mirror does (host/Memory.hpp ssrlcv::requireAbi, on first use)
- * and so does the Python loader (ssrlcv_amd/_lib.py).
+ * an argument.  A pure addition of new entry points (no existing signature, layout or meaning changes) keeps the number:
+ * a binder that does not call them is unaffected, and one that does fails loudly against an older library (C++ at
+ * symbol resolution; Python in ssrlcv_amd/_lib.py, which checks that every name of its EXPORTED list resolves).  A caller
+ * compiled against this header compares the library it loaded with the number it was built for before the first call:
+ * the C++ mirror does (host/Memory.hpp ssrlcv::requireAbi, on first use) and so does the Python loader.
  *   1  rounds 1-4 (unversioned)
  *   2  round 5: ssrlcv_hip_merge_matches counts[2] -> counts[4] and one argument fewer; select_pair_bundles,
  *      set/get_match_arithmetic, ssrlcv_sift_plan_set_stage_event added
  *   3  round 6: ssrlcv_hip_abi_version itself
- *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added */
+ *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added;
+ *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -167,6 +170,49 @@ int ssrlcv_hip_fmatrix_score(const ssrlcv_match* matches, uint32_t numMatches, c
 int ssrlcv_hip_pose_from_fmatrix(const ssrlcv_match* matches, uint32_t numMatches, const uint8_t* inlierMask,
                                  const float* F, const ssrlcv_camera* query_host, const ssrlcv_camera* target_host,
                                  void* workspace, size_t workspaceBytes, ssrlcv_pose* pose_host, ssrlcv_stream_t stream);
+
+/* ---- point cloud: k nearest neighbours, statistical neighbour-distance filter, normals (MeshFactory) -------------------
+ * PARITY UNPINNED: the reference's Octree-based filters and normal estimation have no fixture; this contract is the
+ * definition.  Points are n ssrlcv_float3 in device memory; 1 <= k <= SSRLCV_KNN_MAX_K and n >= k + 1.
+ *   non-finite  a point with any NaN or +-inf coordinate is excluded: no neighbours (index UINT32_MAX, dist2 +inf), never
+ *               anyone's neighbour, mean distance +inf (always removed by the filter, left out of its statistics), normal
+ *               (0, 0, 0).  A finite point with fewer than k finite other points has the same empty tail.
+ *   k-NN        the neighbours of i are the k points j != i smallest by the key (d2(i, j), j), in ascending key order, with
+ *               dx = p[j].x - p[i].x (likewise y, z) and d2 = (dx*dx + dy*dy) + dz*dz in float32, every product and sum
+ *               rounded in that order.  Duplicates (d2 = 0) are ordinary neighbours; ties go to the lower index.  The
+ *               result is unique: it does not depend on the cell size, the launch shape or scheduling.
+ *   mean        m_i = (sqrtf(d2_1) + ... + sqrtf(d2_k)) / k: a sequential float32 sum in neighbour order, one division.
+ *   filter      over the points with finite m_i: mu = sum(m_i) / n_f, std = sqrt(sum((m_i - mu)^2) / n_f) (population),
+ *               both float64 through a fixed partition and a fixed tree (no float atomics: bit-identical run to run);
+ *               t = mu + sigma * std; point i is kept iff m_i is finite and (double)m_i <= t.  No such point: {0, 0, 0}.
+ *   normals     covariance of the k + 1 points (i and its neighbours) about their mean, float64; the unit eigenvector of
+ *               the smallest eigenvalue (cyclic Jacobi, fixed sweep count), oriented so that dot(n, viewpoint - p_i) >= 0,
+ *               written as float32.  Zero covariance (all k + 1 coincident) or a missing neighbour: (0, 0, 0).  A
+ *               collinear neighbourhood gets some unit vector orthogonal to the line.
+ * All three are stream-ordered (no host synchronisation).  SSRLCV_ERR_INVALID_ARG (before any launch): k out of range,
+ * n < k + 1, a required pointer NULL.  SSRLCV_ERR_WORKSPACE: workspaceBytes below the query. */
+#define SSRLCV_KNN_MAX_K 32
+size_t ssrlcv_hip_knn_workspace_bytes(uint32_t numPoints, uint32_t k);
+/* neighbors_out: n k uint32, row i = the neighbours of i; dist2_out (NULL: none): n k floats, their d2.
+ * cellSize: the grid cell edge in the points' units (raised to the largest extent / 2^20 when smaller); 0 = automatic
+ * (from the bounding box and n, re-sized once to about k points per occupied cell).  Queries still open after the grid's
+ * ring cap are answered exactly by a scan over all points; farQueries (NULL: not wanted) receives their count (one
+ * device uint32).  A negative or non-finite cellSize: SSRLCV_ERR_INVALID_ARG. */
+int ssrlcv_hip_knn(const ssrlcv_float3* points, uint32_t numPoints, uint32_t k, float cellSize, uint32_t* neighbors_out,
+                   float* dist2_out, uint32_t* farQueries, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_neighbor_filter_workspace_bytes(uint32_t numPoints, uint32_t k);
+/* dist2: the n k distances of ssrlcv_hip_knn.  meanDist_out (NULL: none): n floats m_i.  stats_out: device double[3]
+ * {mu, std, t}.  pointsOut / indexOut: the kept points and their input indices, in input order (capacity n);
+ * normalsIn / normalsOut (both NULL or both set): n x 3 floats compacted the same way.  count_out: one device uint32.
+ * sigma: any finite value.  All device memory. */
+int ssrlcv_hip_neighbor_distance_filter(const ssrlcv_float3* points, uint32_t numPoints, const float* dist2, uint32_t k,
+                                        float sigma, float* meanDist_out, double* stats_out, ssrlcv_float3* pointsOut,
+                                        uint32_t* indexOut, const float* normalsIn, float* normalsOut, uint32_t* count_out,
+                                        void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+/* neighbors: the n k indices of ssrlcv_hip_knn; normals_out: n x 3 floats (device).  viewpoint (host value, finite):
+ * e.g. the mean camera position.  No workspace. */
+int ssrlcv_hip_point_normals(const ssrlcv_float3* points, uint32_t numPoints, const uint32_t* neighbors, uint32_t k,
+                             ssrlcv_float3 viewpoint, float* normals_out, ssrlcv_stream_t stream);
 
 /* ============================== M: matching ======================================================= */
 

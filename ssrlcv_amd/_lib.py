@@ -52,13 +52,19 @@ def load():
         if got != ABI_VERSION:
             raise HipAbiMismatch("%s has ABI version %d, this package binds version %d (include/ssrlcv_hip.h "
                                  "SSRLCV_HIP_ABI_VERSION): rebuild the library" % (LIB_PATH, got, ABI_VERSION))
+        # additions keep the ABI number (include/ssrlcv_hip.h): an older library of the same version lacks the newer entry
+        # points, refused here rather than at the first call
+        missing = [n for n in EXPORTED if not hasattr(lib, n)]
+        if missing:
+            raise HipAbiMismatch("%s lacks entry points this package binds: %s (rebuild the library)" % (LIB_PATH, ", ".join(missing)))
         _lib = lib
         _lib.ssrlcv_hip_version.restype = ctypes.c_char_p
         _lib.ssrlcv_hip_status_string.restype = ctypes.c_char_p
         for name in ("ssrlcv_hip_match_workspace_bytes", "ssrlcv_sift_plan_workspace_bytes",
                      "ssrlcv_hip_ba_sweep2_workspace_bytes", "ssrlcv_hip_sort_workspace_bytes",
                      "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes",
-                     "ssrlcv_hip_fmatrix_ransac_workspace_bytes"):
+                     "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_knn_workspace_bytes",
+                     "ssrlcv_hip_neighbor_filter_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
     return _lib
@@ -74,6 +80,8 @@ EXPORTED = [
     "ssrlcv_hip_pose_lm_terms", "ssrlcv_hip_pose_cost",
     "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_fmatrix_ransac", "ssrlcv_hip_fmatrix_score",
     "ssrlcv_hip_pose_from_fmatrix",
+    "ssrlcv_hip_knn_workspace_bytes", "ssrlcv_hip_knn", "ssrlcv_hip_neighbor_filter_workspace_bytes",
+    "ssrlcv_hip_neighbor_distance_filter", "ssrlcv_hip_point_normals",
     "ssrlcv_projection_matrix_host", "ssrlcv_hip_match_workspace_bytes", "ssrlcv_hip_set_match_arithmetic", "ssrlcv_hip_get_match_arithmetic", "ssrlcv_hip_seed_distances_u8x128",
     "ssrlcv_hip_match_u8x128", "ssrlcv_hip_compact_matches", "ssrlcv_hip_compact_matches_async", "ssrlcv_hip_keypoints_from_members",
     "ssrlcv_hip_matchset_from_matches", "ssrlcv_merge_matches_host", "ssrlcv_merge_matches_host_mode", "ssrlcv_host_free", "ssrlcv_assign_pairs_host",

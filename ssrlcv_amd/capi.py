@@ -229,6 +229,67 @@ def pose_from_fmatrix(matches_d, n, mask_d, F, query_cam_np, target_cam_np):
     return pose
 
 
+# ------------------------------------------------------------------ point cloud: k-NN, neighbour-distance filter, normals
+KNN_MAX_K = 32  # SSRLCV_KNN_MAX_K
+
+
+class Float3(ctypes.Structure):
+    _fields_ = [("x", c_f32), ("y", c_f32), ("z", c_f32)]
+
+
+def _cloud(points_d):
+    """(n, 3) float32 device tensor (or its flat view) -> (contiguous tensor, n)"""
+    assert points_d.is_cuda and points_d.dtype == torch.float32 and points_d.numel() % 3 == 0
+    p = points_d.contiguous()
+    return p, p.numel() // 3
+
+
+def knn(points_d, k, cell_size=0.0, dist2=True, far=False):
+    """ssrlcv_hip_knn -> (neighbours int32 [n, k] (UINT32_MAX reads as -1), dist2 float32 [n, k] or None, far-path query
+    count (int32 [1] device tensor) or None).  Stream-ordered: nothing here synchronises."""
+    p, n = _cloud(points_d)
+    ws = dev_bytes(LIB.ssrlcv_hip_knn_workspace_bytes(c_u32(n), c_u32(k)))
+    nbr = torch.empty((n, k), dtype=torch.int32, device="cuda")
+    d2 = torch.empty((n, k), dtype=torch.float32, device="cuda") if dist2 else None
+    fc = torch.zeros(1, dtype=torch.int32, device="cuda") if far else None
+    check(LIB.ssrlcv_hip_knn(ptr(p), c_u32(n), c_u32(k), c_f32(cell_size), ptr(nbr), ptr(d2), ptr(fc), ptr(ws),
+                             c_sz(ws.numel()), stream_ptr()))
+    return nbr, d2, fc
+
+
+def neighbor_distance_filter(points_d, dist2_d, k, sigma, normals_d=None):
+    """ssrlcv_hip_neighbor_distance_filter -> dict of device tensors: points [n, 3] and index int32 [n] (the first
+    `count` rows are the kept ones), mean float32 [n], stats float64 [3] = {mu, std, t}, count int32 [1], normals [n, 3]
+    or None.  Stream-ordered."""
+    p, n = _cloud(points_d)
+    ws = dev_bytes(LIB.ssrlcv_hip_neighbor_filter_workspace_bytes(c_u32(n), c_u32(k)))
+    out = {"points": torch.empty((n, 3), dtype=torch.float32, device="cuda"),
+           "index": torch.empty(n, dtype=torch.int32, device="cuda"),
+           "mean": torch.empty(n, dtype=torch.float32, device="cuda"),
+           "stats": torch.empty(3, dtype=torch.float64, device="cuda"),
+           "count": torch.empty(1, dtype=torch.int32, device="cuda"), "normals": None}
+    nin = None
+    if normals_d is not None:
+        nin = normals_d.contiguous()
+        assert nin.dtype == torch.float32 and nin.numel() == 3 * n
+        out["normals"] = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    check(LIB.ssrlcv_hip_neighbor_distance_filter(ptr(p), c_u32(n), ptr(dist2_d.contiguous()), c_u32(k), c_f32(sigma),
+                                                  ptr(out["mean"]), ptr(out["stats"]), ptr(out["points"]),
+                                                  ptr(out["index"]), ptr(nin), ptr(out["normals"]), ptr(out["count"]),
+                                                  ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return out
+
+
+def point_normals(points_d, neighbors_d, k, viewpoint):
+    """ssrlcv_hip_point_normals -> float32 [n, 3] device tensor; viewpoint: three numbers (host)."""
+    p, n = _cloud(points_d)
+    nrm = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    vp = Float3(*[float(v) for v in viewpoint])
+    check(LIB.ssrlcv_hip_point_normals(ptr(p), c_u32(n), ptr(neighbors_d.contiguous()), c_u32(k), vp, ptr(nrm),
+                                       stream_ptr()))
+    return nrm
+
+
 # ------------------------------------------------------------------ matching
 def projection_matrix(camera_np):
     cam = np.ascontiguousarray(camera_np).view(np.uint8).reshape(-1)[:80].copy()

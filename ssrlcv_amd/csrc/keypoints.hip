@@ -1228,6 +1228,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
       if (lane < 16) *reinterpret_cast<uint2*>(&f->values[lane * 8]) = *reinterpret_cast<const uint2*>(&s_bytes[wave][lane * 8]);
       if (lane == 16) {
         f->parent = -1;  // Feature() default (include/Feature.cuh:43-46); the reference kernel never writes it
+        reinterpret_cast<int*>(f)[1] = 0;  // the 4 padding bytes before the 8-aligned loc: every output byte defined
         f->theta = kp.theta;
         f->sigma = kp.sigma;
         f->loc.x = kp.loc.x * pixelWidth;

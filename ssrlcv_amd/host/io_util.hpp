@@ -24,4 +24,34 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, std
   of.close();
   if (origin == gpu) points->setMemoryState(gpu);
 }
+
+// The same writer with a normal per vertex (property float nx / ny / nz; MeshFactory::savePoints once normals exist).
+// Floats are written with 9 significant digits, so that they read back bit for bit.  Both Unitys come back to their
+// origin state.
+inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr::value<Unity<float3>> normals,
+                     std::string dir = "out/") {
+  if (normals->size() != points->size()) {
+    logger.err.printf("writePLY: %lu normals for %lu points", normals->size(), points->size());
+    return;
+  }
+  MemoryState origin = points->getMemoryState(), originN = normals->getMemoryState();
+  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
+  if (originN == gpu || normals->getFore() == gpu) normals->transferMemoryTo(cpu);
+  std::ofstream of;
+  of.open(dir + filename + ".ply");
+  of.precision(9);
+  of << "ply\nformat ascii 1.0\n";
+  of << "comment author: SSRLCV simple PLY writer (MI355X build)\n";
+  of << "element vertex " << points->size() << "\n";
+  of << "property float x\nproperty float y\nproperty float z\n";
+  of << "property float nx\nproperty float ny\nproperty float nz\n";
+  of << "end_header\n";
+  const float3* p = points->host.get();
+  const float3* n = normals->host.get();
+  for (unsigned long i = 0; i < points->size(); i++)
+    of << p[i].x << " " << p[i].y << " " << p[i].z << " " << n[i].x << " " << n[i].y << " " << n[i].z << "\n";
+  of.close();
+  if (origin == gpu) points->setMemoryState(gpu);
+  if (originN == gpu) normals->setMemoryState(gpu);
+}
 }  // namespace ssrlcv

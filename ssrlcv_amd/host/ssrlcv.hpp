@@ -7,4 +7,5 @@
 #include "MatchFactory.hpp"
 #include "PointCloudFactory.hpp"
 #include "io_util.hpp"
+#include "MeshFactory.hpp"
 #include "Pipeline.hpp"

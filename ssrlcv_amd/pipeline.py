@@ -332,6 +332,32 @@ def filter_match_set(mm_d, kp_d, n, n_kp, cameras, kind, cutoff=None, sigma=3.0,
     return mm_o[: 8 * kept], kp_o[: 16 * kept_kp], kept, kept_kp
 
 
+def filter_cloud(points, k=16, sigma=2.0, normals=None, cell_size=0.0):
+    """Statistical neighbour-distance outlier removal on a cloud (MeshFactory's neighbour filter; contract in
+    include/ssrlcv_hip.h): m_i = mean distance of point i to its k nearest neighbours, kept iff m_i <= mu + sigma * std
+    over the finite points.  points: (n, 3) float32 device tensor, e.g. what `reconstruct` / `triangulate` return;
+    normals: optional (n, 3) float32 device tensor compacted alongside.  At world size > 1 that cloud is already
+    replicated on every rank, so no collective is needed: every rank computes the same result.
+    -> dict(points (m, 3), index int64 (m,) original row of each kept point, in input order, mean_distance (n,),
+    stats (mu, std, t) floats, count m, normals (m, 3) or None).  One synchronisation (the count)."""
+    nbr, d2, _ = capi.knn(points, k, cell_size)
+    out = capi.neighbor_distance_filter(points, d2, k, sigma, normals)
+    m = int(out["count"].item())
+    return {"points": out["points"][:m], "index": out["index"][:m].long(), "mean_distance": out["mean"],
+            "stats": tuple(float(x) for x in out["stats"].cpu().tolist()), "count": m,
+            "normals": out["normals"][:m] if normals is not None else None}
+
+
+def cloud_normals(points, k=16, *, viewpoint, cell_size=0.0):
+    """Oriented unit normals of a cloud (MeshFactory's normal estimation; contract in include/ssrlcv_hip.h): smallest
+    eigenvector of the float64 covariance of each point and its k nearest neighbours, pointing towards `viewpoint`
+    (e.g. the mean camera position, in the cloud's frame).  points: (n, 3) float32 device tensor; the same on every rank
+    at world size > 1 (the cloud is replicated).  -> (n, 3) float32 device tensor; (0, 0, 0) for non-finite points and
+    coincident neighbourhoods.  Stream-ordered."""
+    nbr, _, _ = capi.knn(points, k, cell_size, dist2=False)
+    return capi.point_normals(points, nbr, k, viewpoint)
+
+
 def ba_parameter_sets(cameras2, h_lin=1e-5, h_step=(1e-4, 1e-4, 1e-4, 1e-5, 1e-5, 1e-5)):
     """The K = 612 camera-parameter vectors one BundleAdjustTwoView iteration evaluates: 24 for the central-difference
     gradient (h = 1e-5, src/PointCloudFactory.cu:1061-1062) and 588 for the Hessian (h = {1e-4 x3, 1e-5 x3} per camera,
