@@ -132,7 +132,9 @@ int ssrlcv_hip_pose_cost(const ssrlcv_match* matches, uint32_t numMatches, const
  *               splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9; z ^= z >> 27, z *= 0x94D049BB133111EB;
  *               z ^= z >> 31), index ((z >> 32) numMatches) >> 32; duplicates skipped until 7 distinct indices, at most
  *               64 draws (else no candidate).
- *   solver      float64: null space F1, F2 of the 7x9 system (Householder), real roots of det(a F1 + (1 - a) F2) in
+ *   solver      float64: null space F1, F2 of the 7x9 system A (Householder reflections from the right,
+ *               A H_0 ... H_6 = [L | 0], F1 = H_0 ... H_6 e_7, F2 = H_0 ... H_6 e_8: the order of the roots depends on
+ *               this basis), real roots of det(a F1 + (1 - a) F2) in
  *               ascending order (cubic through its values at a = 0, 1, -1, 2; when the leading coefficient is below
  *               1e-12 of the largest the lower-degree polynomial is solved), candidate r of sample h in slot 3 h + r,
  *               denormalised to pixels.  Empty slots: F all zero, count 0.

@@ -1,7 +1,9 @@
 // tests/cpp/pose_ransac_test.cpp -- PoseEstimator::estimatePoseRANSAC through the reference's class API.
-//   pose_ransac_test <pair.bin>   (GPU) pair.bin: uint64 n, two ssrlcv_camera records (query, target), n ssrlcv_match
+//   pose_ransac_test <pair.bin> [fallback]   (GPU) pair.bin: uint64 n, two ssrlcv_camera records (query, target),
+//                                            n ssrlcv_match
 // Prints "ransac <inliers at 2 px> <roll pitch yaw x y z>" and "lm <cost at the RANSAC angles> <cost after LM_optimize>"
-// (LM_optimize starts from the RANSAC angles and the cameras' baseline), then "ok".
+// (LM_optimize starts from the RANSAC angles and the cameras' baseline), then "ok".  `fallback`: the pair must have no
+// valid F, so estimatePoseRANSAC takes its fallback (the cameras' relative pose); prints the "ransac" line, then "ok".
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -31,7 +33,8 @@ static float poseCost(const ptr::value<Unity<Match>>& matches, const Pose& pose,
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: %s <pair.bin>\n", argv[0]); return 2; }
+  if (argc < 2) { std::fprintf(stderr, "usage: %s <pair.bin> [fallback]\n", argv[0]); return 2; }
+  const bool fallback = argc > 2 && std::string(argv[2]) == "fallback";
   std::FILE* f = std::fopen(argv[1], "rb");
   if (!f) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
   uint64_t n = 0;
@@ -49,12 +52,16 @@ int main(int argc, char** argv) {
   }
   PoseEstimator estim(images[0], images[1], matches);
   const FMatrixInliers fm = estim.estimateFMatrixRANSAC(4096, 2.0f);
-  CHECK(fm.valid && matches->getMemoryState() == cpu);
+  CHECK(fm.valid != fallback && matches->getMemoryState() == cpu);
   Pose pose = estim.estimatePoseRANSAC();
   CHECK(matches->getMemoryState() == cpu);  // origin state restored
   CHECK(std::isfinite(pose.roll) && std::isfinite(pose.pitch) && std::isfinite(pose.yaw) && std::isfinite(pose.x));
   std::printf("ransac %lu %.9g %.9g %.9g %.9g %.9g %.9g\n", fm.inliers, pose.roll, pose.pitch, pose.yaw, pose.x, pose.y,
               pose.z);
+  if (fallback) {
+    std::printf("ok\n");
+    return 0;
+  }
   Pose start = pose;
   const float3 b = estim.baselineInQueryFrame();
   start.x = b.x / 1000;

@@ -25,6 +25,30 @@ def sample_indices(seed, h, n):
     return None
 
 
+def draws_needed(seed, samples, n, cap=128):
+    """-> int array[samples]: the draw (1-based) on which sample h gets its 7th distinct index, 0 if not within `cap`
+    draws (the contract stops at 64).  The hash of sample_indices vectorised; n <= 64 (the seen set is a bit mask)."""
+    assert 7 <= n <= 64
+    with np.errstate(over="ignore"):
+        h = np.arange(samples, dtype=np.uint64)[:, None]
+        j = np.arange(cap, dtype=np.uint64)[None, :]
+        z = np.uint64(seed) + ((h << np.uint64(32)) + j + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+        idx = ((z >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)
+    seen = np.zeros(samples, np.uint64)
+    got = np.zeros(samples, np.int64)
+    done = np.zeros(samples, np.int64)
+    for d in range(cap):
+        bit = np.uint64(1) << idx[:, d]
+        new = (seen & bit) == 0
+        seen |= bit
+        got += new
+        done[(got == 7) & (done == 0)] = d + 1
+    return done
+
+
 def split(matches):
     q = matches["kp0_loc"].astype(np.float64)
     t = matches["kp1_loc"].astype(np.float64)
@@ -61,10 +85,34 @@ def rows(q, t):
     return np.stack([u * x, u * y, u, v * x, v * y, v, x, y, np.ones_like(x)], 1)
 
 
-def solve7(qn, tn):
-    """-> (list of normalised F, near_double_root): real roots of det(a F1 + (1 - a) F2) in ascending order"""
-    _, _, vt = np.linalg.svd(rows(qn, tn))
-    F1, F2 = vt[7].reshape(3, 3), vt[8].reshape(3, 3)
+def householder_null(A):
+    """-> (F1, F2): the null-space pair of the 7x9 system as the kernel builds it: Householder reflections from the right,
+    A H_0 ... H_6 = [L | 0], F1 = H_0 ... H_6 e_7, F2 = H_0 ... H_6 e_8 (the basis fixes what "ascending roots" orders)"""
+    A = np.array(A, np.float64)
+    V = np.zeros((7, 9))
+    for k in range(7):
+        nrm = np.sqrt(np.sum(A[k, k:] ** 2))
+        if nrm == 0:
+            continue
+        V[k, k:] = A[k, k:]
+        V[k, k] += -nrm if A[k, k] < 0 else nrm
+        vv = np.sum(V[k, k:] ** 2)
+        A[k:, k:] -= np.outer(2 * (A[k:, k:] @ V[k, k:]) / vv, V[k, k:])
+        V[k] /= np.sqrt(vv)
+    N = np.eye(9)[7:].copy()
+    for k in range(6, -1, -1):
+        N -= 2 * np.outer(N @ V[k], V[k])
+    return N[0].reshape(3, 3), N[1].reshape(3, 3)
+
+
+def solve7(qn, tn, householder=False):
+    """-> (list of normalised F, near_double_root): real roots of det(a F1 + (1 - a) F2) in ascending order; F1, F2 the
+    last two right singular vectors, or with `householder` the kernel's own basis (householder_null)"""
+    if householder:
+        F1, F2 = householder_null(rows(qn, tn))
+    else:
+        _, _, vt = np.linalg.svd(rows(qn, tn))
+        F1, F2 = vt[7].reshape(3, 3), vt[8].reshape(3, 3)
     d = [np.linalg.det(F2 + a * (F1 - F2)) for a in (0.0, 1.0, -1.0, 2.0)]
     c0, c2 = d[0], 0.5 * (d[1] + d[2]) - d[0]
     c3 = (d[3] - 4 * c2 - c0 - (d[1] - d[2])) / 6
@@ -126,6 +174,29 @@ def ransac(matches, samples, thr, seed=0):
     return (refit, mr) if mr.sum() >= m.sum() else (best, m)
 
 
+def best_slot(counts):
+    """-> (slot, count): the lowest slot with the largest count; (None, 0) when every count is 0 (no best)"""
+    counts = np.asarray(counts)
+    c = int(counts.max()) if len(counts) else 0
+    return (int(np.argmax(counts)), c) if c > 0 else (None, 0)
+
+
+def refit(matches, mask):
+    """the contract's refit of the masked matches: the 9x9 normal matrix A^T A in normalised coordinates, the
+    eigenvector of its smallest eigenvalue, rank 2 through the 3x3 SVD, back to pixels (ransac() states it by SVD)"""
+    q, t, valid = split(matches)
+    cq, ct, s = normalisation(q, t, valid)
+    m = np.asarray(mask, bool) & valid
+    A = rows((q[m] - cq) * s, (t[m] - ct) * s)
+    _, V = np.linalg.eigh(A.T @ A)
+    return to_pixel(rank2(V[:, 0].reshape(3, 3)), cq, ct, s)
+
+
+def sampson_gap(Fa, Fb, q, t):
+    """max over the matches of | Sampson distance under Fa - under Fb | in pixels (float64)"""
+    return float(np.max(np.abs(np.sqrt(sampson_d2(Fa, q, t)) - np.sqrt(sampson_d2(Fb, q, t)))))
+
+
 # ------------------------------------------------------------------ camera model of pose_residual (csrc/pose.hip)
 def rot(a):
     x, y, z = a
@@ -180,6 +251,22 @@ def pose_from_F(F, q, t, use, Kq, Kt):
     return best
 
 
+def axis_rotations(R):
+    """getAxisRotations (host/matrix_util.hpp) in float64: (roll, pitch, yaw) of R = rot((roll, pitch, yaw))"""
+    x = np.arctan2(R[2, 1], R[2, 2])
+    return np.array([x, np.arctan2(-R[2, 0], R[2, 2] / np.cos(x)), np.arctan2(R[1, 0], R[0, 0])])
+
+
+def pose6(F, matches, mask, cams):
+    """the whole output of ssrlcv_hip_pose_from_fmatrix in float64: pose_from_F over the valid matches with mask != 0
+    (mask None: every valid match), getAxisRotations of Rp, unit C times |target.cam_pos - query.cam_pos| / 1000"""
+    q, t, valid = split(matches)
+    use = valid if mask is None else valid & (np.asarray(mask) != 0)
+    Rp, C = pose_from_F(F, q, t, use, K_of(cams[0:1]), K_of(cams[1:2]))
+    d = cams["cam_pos"][1].astype(np.float64) - cams["cam_pos"][0].astype(np.float64)
+    return np.concatenate([axis_rotations(Rp), C * np.linalg.norm(d) / 1000.0])
+
+
 def rotation_error_deg(Ra, Rb):
     return np.degrees(np.arccos(np.clip((np.trace(Ra.T @ Rb) - 1) / 2, -1, 1)))
 
@@ -191,32 +278,39 @@ def angle_deg(a, b):
 # ------------------------------------------------------------------ synthetic two-view scene
 TRUE_ANGLES = np.array([0.10, -0.10, 0.08])  # roll, pitch, yaw: about 9.3 degrees
 TRUE_C = np.array([3.6, 0.9, 1.2])           # baseline ~3.9 against a mean depth of 20: about 1/5
+# the poses the pose tests recover: (roll, pitch, yaw), target centre C in the query frame
+POSES = {"default": (TRUE_ANGLES, TRUE_C), "yaw": ((0.10, -0.10, 2.5), TRUE_C), "pitch": ((0.10, -0.6, 0.08), TRUE_C),
+         "forward": (TRUE_ANGLES, (0.0, 0.0, 3.0)), "backward": (TRUE_ANGLES, (0.0, 0.0, -3.0)),
+         "sideways": (TRUE_ANGLES, (4.0, 0.0, 0.0)), "vertical": (TRUE_ANGLES, (0.0, 4.0, 0.0)),
+         "short": (TRUE_ANGLES, 0.2 * TRUE_C / np.linalg.norm(TRUE_C))}  # a baseline of 1/100 of the mean depth
 
 
-def synthetic_cameras():
+def synthetic_cameras(C=TRUE_C):
     cams = np.zeros(2, H.CAMERA)
     f_pix = 2048.0 / np.tan(np.radians(20.0))  # 4096 px across 40 degrees
     cams["foc"] = 0.05
     cams["dpix"] = 0.05 / f_pix
     cams["fov"] = np.radians(40.0)
     cams["size"] = 4096
-    cams["cam_pos"][1] = 1000.0 * TRUE_C  # LM_optimize's unit: the pose position is 1/1000 of the cameras'
+    cams["cam_pos"][1] = 1000.0 * np.asarray(C)  # LM_optimize's unit: the pose position is 1/1000 of the cameras'
     return cams
 
 
-def synthetic(n, seed=1, outliers=0.4, noise=0.5):
+def synthetic(n, seed=1, outliers=0.4, noise=0.5, angles=TRUE_ANGLES, C=TRUE_C):
     """-> (MATCH[n], cameras, truth dict(Rp, C, inlier)): points with depth 10..30 seen by both cameras, 0.5 px noise,
-    a fraction `outliers` of the target locations replaced by uniform ones"""
+    a fraction `outliers` of the target locations replaced by uniform ones; the target camera has rotation
+    rot(angles) and centre C in the query frame"""
     rng = np.random.default_rng(seed)
-    cams = synthetic_cameras()
+    C = np.asarray(C, np.float64)
+    cams = synthetic_cameras(C)
     Kq, Kt = K_of(cams[0:1]), K_of(cams[1:2])
-    Rp = rot(TRUE_ANGLES)
+    Rp = rot(np.asarray(angles, np.float64))
     q_all, t_all = np.zeros((0, 2)), np.zeros((0, 2))
     while len(q_all) < n:
         m = 2 * n + 64
         z = rng.uniform(10.0, 30.0, m)
         X = np.stack([rng.uniform(-1, 1, m) * z * 0.4, rng.uniform(-1, 1, m) * z * 0.4, z], 1)
-        Xt = (X - TRUE_C) @ Rp  # Rp^T (X - C)
+        Xt = (X - C) @ Rp  # Rp^T (X - C)
         ok = Xt[:, 2] > 0
         qh, th = X @ Kq.T, Xt @ Kt.T
         q, t = qh[:, :2] / qh[:, 2:], th[:, :2] / th[:, 2:]
@@ -228,4 +322,4 @@ def synthetic(n, seed=1, outliers=0.4, noise=0.5):
     mt = np.zeros(n, H.MATCH)
     mt["kp0_loc"], mt["kp1_loc"] = q.astype(np.float32), t.astype(np.float32)
     mt["kp0_parent"], mt["kp1_parent"] = 0, 1
-    return mt, cams, {"Rp": Rp, "C": TRUE_C.copy(), "inlier": ~bad}
+    return mt, cams, {"Rp": Rp, "C": C.copy(), "inlier": ~bad}

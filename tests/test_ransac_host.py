@@ -92,3 +92,74 @@ def test_reference_recovers_synthetic_geometry():
     # the true F passes the same inliers (the scene is what the tests think it is)
     Ft = R.F_of_pose(truth["Rp"], truth["C"], R.K_of(cams[0:1]), R.K_of(cams[1:2]))
     assert (R.inliers(Ft, q, t, matches["invalid"] == 0, 2.0) & inl).sum() >= 0.99 * inl.sum()
+
+
+def test_refit_eigh_matches_svd():
+    """refit() (eigenvector of the normal matrix, the contract's form) and ransac()'s SVD of the rows give one F."""
+    matches, _, truth = R.synthetic(2000, seed=3)
+    q, t, valid = R.split(matches)
+    cq, ct, s = R.normalisation(q, t, valid)
+    mask = truth["inlier"]
+    _, _, vt = np.linalg.svd(R.rows((q[mask] - cq) * s, (t[mask] - ct) * s))
+    F_svd = R.to_pixel(R.rank2(vt[8].reshape(3, 3)), cq, ct, s)
+    F_eigh = R.refit(matches, mask)
+    assert np.abs(F_svd - F_eigh).max() < 1e-9
+    assert R.sampson_gap(F_svd, F_eigh, q[mask], t[mask]) < 1e-9
+
+
+def test_best_slot_is_lowest_of_the_largest():
+    assert R.best_slot([0, 5, 3, 5, 5]) == (1, 5)
+    assert R.best_slot([7]) == (0, 7)
+    assert R.best_slot([0, 0, 0]) == (None, 0)
+
+
+def test_axis_rotations_invert_rot():
+    rng = np.random.default_rng(4)
+    a = np.stack([rng.uniform(-np.pi, np.pi, 200), rng.uniform(-1.39, 1.39, 200), rng.uniform(-np.pi, np.pi, 200)], 1)
+    for x in np.concatenate([a, [[0.0, 0.0, 0.0], [0.1, -0.6, 2.5], [-3.0, 1.39, -3.1]]]):
+        assert np.abs(R.axis_rotations(R.rot(x)) - x).max() < 1e-12, x
+
+
+def test_draws_needed_matches_sample_indices():
+    """the vectorised hash of the 64-draw cap search agrees with sample_indices, sample by sample"""
+    d = R.draws_needed(0, 65536, 7)
+    assert (d == 64).any() and (d == 65).any()  # seed 0 at n = 7 reaches both sides of the cap
+    for h in list(range(64)) + list(np.flatnonzero((d >= 63) & (d <= 66))):
+        idx = R.sample_indices(0, int(h), 7)
+        assert (idx is not None) == (1 <= d[h] <= 64), (h, d[h])
+    d2 = R.draws_needed(2 ** 64 - 1, 256, 50)
+    for h in range(256):
+        assert (R.sample_indices(2 ** 64 - 1, h, 50) is not None) == (1 <= d2[h] <= 64)
+
+
+def test_pose6_recovers_exact_poses():
+    """pose6 of the exact F of each pose gives back its angles and its scaled baseline direction (float64)."""
+    for name, (angles, C) in R.POSES.items():
+        matches, cams, truth = R.synthetic(2000, seed=11, outliers=0.0, angles=angles, C=C)
+        F = R.F_of_pose(truth["Rp"], truth["C"], R.K_of(cams[0:1]), R.K_of(cams[1:2]))
+        p = R.pose6(F, matches, None, cams)
+        assert np.abs(p[:3] - np.asarray(angles)).max() < 1e-12, (name, p)
+        length = np.linalg.norm(cams["cam_pos"][1].astype(np.float64) - cams["cam_pos"][0]) / 1000.0
+        assert np.abs(p[3:] - truth["C"] / np.linalg.norm(truth["C"]) * length).max() < 1e-12 * length, (name, p)
+
+
+def test_householder_null_space():
+    """householder_null spans the 7x9 system's null space with an orthonormal pair, and solve7 finds the same F in
+    either basis (only the parameter, and so the order of the roots, depends on it)."""
+    matches, _, truth = R.synthetic(500, seed=5)
+    q, t, valid = R.split(matches)
+    cq, ct, s = R.normalisation(q, t, valid)
+    for h in range(50):
+        idx = R.sample_indices(0, h, 500)
+        qn, tn = (q[idx] - cq) * s, (t[idx] - ct) * s
+        F1, F2 = R.householder_null(R.rows(qn, tn))
+        N = np.stack([F1.reshape(-1), F2.reshape(-1)])
+        assert np.abs(R.rows(qn, tn) @ N.T).max() < 1e-12 and np.abs(N @ N.T - np.eye(2)).max() < 1e-12
+        a, near_a = R.solve7(qn, tn)
+        b, near_b = R.solve7(qn, tn, householder=True)
+        assert len(a) == len(b) or near_a or near_b
+        if len(a) == len(b):
+            ua = [F.reshape(-1) / np.linalg.norm(F) for F in a]
+            for F in b:
+                f = F.reshape(-1) / np.linalg.norm(F)
+                assert min(min(np.linalg.norm(f - g), np.linalg.norm(f + g)) for g in ua) < 1e-6
