@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void k_gauss_pair(PairArgs a) {
 // Whether the pair kernel serves levels 0 + 1 of a w x h octave: 13 + 17 taps, sizes that are multiples of 8 (row tiles, u8
 // rows of whole dwords), wide enough that a mirrored column lies in the strip that reads it, 32-bit element offsets.
 bool pair_usable(uint32_t w, uint32_t h, int taps0, int taps1, const float* in, const float* outA, const float* outB) {
-  static const bool off = svdev::env("SSRLCV_NO_GAUSS_PAIR") != nullptr || svdev::env("SSRLCV_GAUSS_VALU") != nullptr || svdev::env("SSRLCV_GAUSS_MFMA") != nullptr;
+  const bool off = svdev::sw().noGaussPair || svdev::sw().gaussValu || svdev::sw().gaussMfma;
   return !off && taps0 == 13 && taps1 == 17 && (w & 7) == 0 && (h & 7) == 0 && w >= 512 && h >= 64 &&
          (uint64_t)w * h < ((uint64_t)1 << 31) && (reinterpret_cast<size_t>(in) & 15) == 0 && (reinterpret_cast<size_t>(outA) & 3) == 0 &&
          (reinterpret_cast<size_t>(outB) & 3) == 0;
@@ -468,7 +468,7 @@ int launch_pair(const float* in, const uint8_t* u8src, float* outA, float* outB,
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu[0], (const void*)k_gauss_pair<6, false>, 256, 0) != hipSuccess || perCu[0] < 1) perCu[0] = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu[1], (const void*)k_gauss_pair<6, true>, 256, 0) != hipSuccess || perCu[1] < 1) perCu[1] = 1;
   }
-  static const int rowsForced = svdev::env("SSRLCV_PAIR_ROWS") ? atoi(svdev::env("SSRLCV_PAIR_ROWS")) : 0;
+  const int rowsForced = svdev::sw().pairRows;
   const uint32_t strips = (w + 239) / 240;
   uint32_t by = (uint32_t)(perCu[u8src ? 1 : 0] * cus) / strips;
   by = by < 1 ? 1 : by;

@@ -541,8 +541,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 }
 
 bool pair_rm_usable(uint32_t w, uint32_t h) {
-  static const bool off = svdev::env("SSRLCV_NO_GAUSS_PAIR_RM") != nullptr;
-  return !off && (w & 15) == 0 && (h & 15) == 0 && w >= 512 && h >= 64;
+  return !svdev::sw().noGaussPairRm && (w & 15) == 0 && (h & 15) == 0 && w >= 512 && h >= 64;
 }
 
 // the matrix-pipe form of launch_pair (same arguments, same results); the caller has checked pair_usable and pair_rm_usable
@@ -580,7 +579,7 @@ int launch_pair_rm(const float* in, const uint8_t* u8src, float* outA, float* ou
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu[0], (const void*)k_gauss_pair_rm<false>, 256, ldsBytes) != hipSuccess || perCu[0] < 1) perCu[0] = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu[1], (const void*)k_gauss_pair_rm<true>, 256, ldsBytes) != hipSuccess || perCu[1] < 1) perCu[1] = 1;
   }
-  static const int rowsForced = svdev::env("SSRLCV_PAIR_ROWS") ? atoi(svdev::env("SSRLCV_PAIR_ROWS")) : 0;
+  const int rowsForced = svdev::sw().pairRows;
   const uint32_t strips = (w + 239) / 240;
   uint32_t by = (uint32_t)(perCu[u8src ? 1 : 0] * cus) / strips;  // one round of resident blocks
   by = by < 1 ? 1 : by;

@@ -172,7 +172,7 @@ int ssrlcv_merge_matches_host_mode(uint32_t numImages, const uint32_t* numFeatur
   mem.clear();
   L.V = numImages;
   const uint32_t V = numImages;
-  static const bool timing = svdev::env("SSRLCV_MERGE_TIMING") != nullptr;
+  const bool timing = svdev::sw().mergeTiming;
   auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!timing) return;
@@ -304,10 +304,7 @@ int ssrlcv_merge_matches_host(uint32_t numImages, const uint32_t* numFeatures, u
   // burst spends it, and the main thread is then throttled through the copies that follow (single H2D copies of 2 MB
   // measured at 9-22 ms right after it; with a team of 16 the merge itself jittered between 10 and 180 ms).  So the
   // default is the sequential walk; SSRLCV_MERGE_THREADS=<n> enables the parallel one where the cores are really there.
-  static const int threads = [] {
-    if (const char* e = svdev::env("SSRLCV_MERGE_THREADS")) return std::atoi(e) > 0 ? std::atoi(e) : 1;
-    return 1;
-  }();
+  const int threads = svdev::sw().mergeThreads;
   if (threads <= 1)
     return ssrlcv_merge_matches_host_mode(numImages, numFeatures, numPairs, pairCounts, pairs, matches_out, members_out,
                                           numMatches, numMembers, 1);

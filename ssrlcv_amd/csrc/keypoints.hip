@@ -1580,19 +1580,8 @@ inline RangeTable* theta_tab(const ssrlcv_sift_plan* plan, char* ws, int g) { re
 inline RangeTable* desc_tab(const ssrlcv_sift_plan* plan, char* ws, int g) { return (RangeTable*)(ws + plan->off_groups + 256 * (svp::kSampleGroups + g)); }
 inline GroupCtl* group_ctl(const ssrlcv_sift_plan* plan, char* ws, int o) { return (GroupCtl*)(ws + plan->off_groups + 2048) + o; }
 
-// lanes per key point of the orientation kernel, as a shift (see k_thetas).  Developer build: SSRLCV_THETAS_LANES=1|2|4.
-#ifndef SSRLCV_THETAS_LANES_SHIFT
-#define SSRLCV_THETAS_LANES_SHIFT 2
-#endif
-inline int thetas_lanes_shift() {
-  static const int shift = [] {
-    const char* e = svdev::env("SSRLCV_THETAS_LANES");
-    if (!e) return SSRLCV_THETAS_LANES_SHIFT;
-    const int lanes = atoi(e);
-    return lanes >= 4 ? 2 : (lanes >= 2 ? 1 : 0);
-  }();
-  return shift;
-}
+// lanes per key point of the orientation kernel, as a shift (see k_thetas): -DSSRLCV_THETAS_LANES_SHIFT, and in the developer
+// build SSRLCV_THETAS_LANES=1|2|4 (svdev::sw().thetasLanesShift)
 // upper bound of the orientation kernel's grid: one block per 64 >> shift key points of a range
 inline unsigned thetas_grid(const ssrlcv_sift_plan* plan, int oFirst, int oLast, int shift) {
   unsigned blocks = 20;
@@ -1666,11 +1655,8 @@ int queue_rest_orientations(const ssrlcv_sift_plan* plan, char* ws, hipStream_t 
   OctaveState* states = (OctaveState*)(ws + plan->off_state);
   const uint32_t maxO = plan->params.maxOrientations;
   OctaveSet set = make_set(plan, ws);
-  uint32_t thetaSel = 0xFFFFFu;
-#ifdef SSRLCV_INSTRUMENTED_BUILD
-  if (const char* e = svdev::env("SSRLCV_TIMING_THETAS_SEL")) thetaSel = (uint32_t)strtoul(e, nullptr, 16);
-#endif
-  const int lanesShift = thetas_lanes_shift();
+  const uint32_t thetaSel = svdev::sw().timingThetasSel;
+  const int lanesShift = svdev::sw().thetasLanesShift;
   RangeTable* restRanges = theta_tab(plan, ws, 1);
   hipLaunchKernelGGL(k_build_ranges, dim3(1), dim3(1), 0, st, states, restRanges, 6 - lanesShift, 0xFFFFFu & ~0x1Fu & thetaSel);
   launch_thetas(maxO, lanesShift, thetas_grid(plan, 1, svp::kOctaves - 1, lanesShift), st, (const OctaveState*)states, (const RangeTable*)restRanges,
@@ -1693,12 +1679,9 @@ inline hipStream_t expand_stream(svp::PlanAsync* as, hipStream_t caller, int o) 
 // the expansions will run on -- the clearing of their tile descriptors.
 int orientations_prologue(const ssrlcv_sift_plan* plan, char* ws, hipStream_t caller, svp::PlanAsync* as) {
   OctaveState* states = (OctaveState*)(ws + plan->off_state);
-  uint32_t thetaSel = 0xFFFFFu;
-#ifdef SSRLCV_INSTRUMENTED_BUILD
-  if (const char* e = svdev::env("SSRLCV_TIMING_THETAS_SEL")) thetaSel = (uint32_t)strtoul(e, nullptr, 16);
-#endif
+  const uint32_t thetaSel = svdev::sw().timingThetasSel;
   SSRLCV_HIP_TRY(hipMemsetAsync(group_ctl(plan, ws, 0), 0, sizeof(GroupCtl) * svp::kOctaves, caller));
-  hipLaunchKernelGGL(k_build_ranges, dim3(1), dim3(1), 0, caller, states, theta_tab(plan, ws, 0), 6 - thetas_lanes_shift(), thetaSel);
+  hipLaunchKernelGGL(k_build_ranges, dim3(1), dim3(1), 0, caller, states, theta_tab(plan, ws, 0), 6 - svdev::sw().thetasLanesShift, thetaSel);
   if (as) {
     SSRLCV_HIP_TRY(hipEventRecord(as->expandFork, caller));
     for (int o = 1; o < svp::kOctaves; ++o) SSRLCV_HIP_TRY(hipStreamWaitEvent(expand_stream(as, caller, o), as->expandFork, 0));
@@ -1716,12 +1699,8 @@ int stage_orientations(const ssrlcv_sift_plan* plan, char* ws, hipStream_t calle
   const uint32_t maxO = plan->params.maxOrientations;
   OctaveSet set = make_set(plan, ws);
   RangeTable* thetaRanges = theta_tab(plan, ws, 0);
-  uint32_t thetaSel = 0xFFFFFu;
-#ifdef SSRLCV_INSTRUMENTED_BUILD
-  // timing only (results not valid): orientations of the selected (octave, blur segment) ranges alone -- bit o * 5 + seg
-  if (const char* e = svdev::env("SSRLCV_TIMING_THETAS_SEL")) thetaSel = (uint32_t)strtoul(e, nullptr, 16);
-#endif
-  const int lanesShift = thetas_lanes_shift();
+  const uint32_t thetaSel = svdev::sw().timingThetasSel;  // every range, unless an instrumented build selects some (timing only)
+  const int lanesShift = svdev::sw().thetasLanesShift;
   const float lambdaO = plan->params.orientationContribWidth, othr = plan->params.orientationThreshold;
   // (Round 3 built this kernel with two and with four lanes per key point -- the 36 bins split between the lanes of a
   // group, each bin keeping its sequential chain, the samples' weights shared by DPP: bit-identical, and the same 0.58 ms
@@ -1815,7 +1794,7 @@ int stage_sampling_pipelined(const ssrlcv_sift_plan* plan, char* ws, ssrlcv_sift
   OctaveSet setD = make_set(plan, ws);  // the expanded lists
   for (int o = 0; o < svp::kOctaves; ++o) plan->listInB[o] ^= 1;  // (launch_expand reads the un-flipped state)
   const hipStream_t gs[svp::kSampleGroups] = {caller, as->chain, as->chain2, as->table};
-  const int lanesShift = thetas_lanes_shift();
+  const int lanesShift = svdev::sw().thetasLanesShift;
   unsigned thetaBlocks[svp::kSampleGroups], descBlocks[svp::kSampleGroups], constBlocks[svp::kSampleGroups];
   for (int g = 0; g < svp::kSampleGroups; ++g) {
     const int oFirst = g < kOct0Groups ? 0 : 1, oLast = g < kOct0Groups ? 0 : svp::kOctaves - 1;
@@ -1827,7 +1806,7 @@ int stage_sampling_pipelined(const ssrlcv_sift_plan* plan, char* ws, ssrlcv_sift
   SSRLCV_HIP_TRY(hipMemsetAsync(group_ctl(plan, ws, 0), 0, sizeof(GroupCtl) * svp::kOctaves, caller));
   SSRLCV_HIP_TRY(hipMemsetAsync(featBase, 0, 4 * svp::kOctaves, caller));  // octave 0's features start at 0, known now
   // (developer build: SSRLCV_SAMPLING_IRREGULAR=1 takes the fallback for blur indices that are not an ordered partition)
-  static const bool forceIrregular = svdev::env("SSRLCV_SAMPLING_IRREGULAR") != nullptr;
+  const bool forceIrregular = svdev::sw().samplingIrregular;
   hipLaunchKernelGGL(k_build_group_ranges, dim3(1), dim3(1), 0, caller, (const OctaveState*)states, theta_tab(plan, ws, 0), group_ctl(plan, ws, 0), 6 - lanesShift,
                      forceIrregular);
   SSRLCV_HIP_TRY(hipEventRecord(as->groupFork, caller));
@@ -1928,8 +1907,7 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
   const hipStream_t caller = (hipStream_t)stream;
   // Developer build, SSRLCV_THETAS_SPLIT=1 (round 6; exact, measured, NOT the default -- describe 3.09-3.11 ms per image either
   // way, profiles/r06_kernel_ab.txt): the small octaves' tables first and their orientations beside octave 0's tables.
-  static const bool splitWanted = svdev::env("SSRLCV_THETAS_SPLIT") != nullptr;
-  static const bool pipelinedSampling = svdev::env("SSRLCV_SAMPLING_PIPELINED") != nullptr;
+  const bool splitWanted = svdev::sw().thetasSplit, pipelinedSampling = svdev::sw().samplingPipelined;
   const bool splitRest = as && stop >= 6 && !plan->polarInFlight && splitWanted && !pipelinedSampling;
   if (splitRest) SSRLCV_HIP_TRY(hipMemsetAsync(group_ctl(plan, ws, 0), 0, sizeof(GroupCtl) * svp::kOctaves, caller));
   if (as) {
@@ -1937,9 +1915,9 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->chain, as->fork, 0));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->chain2, as->fork, 0));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->table, as->fork, 0));
-    if ((svp::stream_priority_mode() & 1)) SSRLCV_HIP_TRY(hipStreamWaitEvent(as->polar, as->fork, 0));
+    if ((svdev::sw().prio & 1)) SSRLCV_HIP_TRY(hipStreamWaitEvent(as->polar, as->fork, 0));
     if (stop >= 6 && !plan->polarInFlight) {
-      const hipStream_t ps = (svp::stream_priority_mode() & 1) ? as->polar : as->table;
+      const hipStream_t ps = (svdev::sw().prio & 1) ? as->polar : as->table;
       if (splitRest) {  // the small octaves' tables first: their orientations start behind them (below)
         launch_polar(plan, ws, ps, 1, svp::kOctaves - 1);
         SSRLCV_HIP_TRY(hipEventRecord(as->polarDone[1], ps));
@@ -1983,7 +1961,7 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
     if (rc) return rc;
   }
   if (as) {  // the polar stream joins too (its tables are read by the sampling kernels below)
-    SSRLCV_HIP_TRY(hipEventRecord(as->join[svp::kOctaves], (svp::stream_priority_mode() & 1) ? as->polar : as->table));
+    SSRLCV_HIP_TRY(hipEventRecord(as->join[svp::kOctaves], (svdev::sw().prio & 1) ? as->polar : as->table));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->join[svp::kOctaves], 0));
     if (plan->polarInFlight) {  // queued by build_dog of the same fused extract (one launch per octave on `polar`)
       for (int o = 0; o < svp::kOctaves; ++o) SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->polarDone[o], 0));

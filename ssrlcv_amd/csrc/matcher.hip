@@ -791,7 +791,7 @@ __global__ __launch_bounds__(256) void k_seed_finalize(const unsigned long long*
 // Which formulation of the distance contraction the matcher calls use (process-wide; ssrlcv_hip_set_match_arithmetic):
 // both are exact, so the choice never changes a result.  The developer build starts from SSRLCV_MATCH_F16.
 std::atomic<int>& match_arithmetic() {
-  static std::atomic<int> a(svdev::env("SSRLCV_MATCH_F16") != nullptr ? SSRLCV_MATCH_ARITH_F16 : SSRLCV_MATCH_ARITH_I8);
+  static std::atomic<int> a(svdev::sw().matchF16 ? SSRLCV_MATCH_ARITH_F16 : SSRLCV_MATCH_ARITH_I8);
   return a;
 }
 
@@ -860,12 +860,11 @@ int run_match(const ssrlcv_sift_feature* query, uint32_t nq, const ssrlcv_sift_f
   if (band) {
     // the frame of the pair and the two orders (see "band culling"): bands of the queries in caller order -> u ->
     // targets by (strip across u, position along u) -> queries by where their band lies
-    static const float forceDeg = svdev::env("SSRLCV_BAND_DIR") ? (float)atof(svdev::env("SSRLCV_BAND_DIR")) : 1e30f;
+    const float forceDeg = svdev::sw().bandDir;
     // strip width: 0.4 epsilon within [4, 16] px (the bands are 2 epsilon thick; end of round 4, epsilon 25 on the 4-view
     // 4096^2 flow: 6 px 6.48 ms, 8 6.57, 10 6.54, 12 6.58, 16 6.87, 20 7.43, 24 7.2; queries at half or twice the targets'
     // width no better)
-    static const float stripEnvT = svdev::env("SSRLCV_BAND_STRIP") ? (float)atof(svdev::env("SSRLCV_BAND_STRIP")) : 0.0f;
-    static const float stripEnvQ = svdev::env("SSRLCV_BAND_STRIP_Q") ? (float)atof(svdev::env("SSRLCV_BAND_STRIP_Q")) : 0.0f;
+    const float stripEnvT = svdev::sw().bandStrip, stripEnvQ = svdev::sw().bandStripQ;
     const float epsAbs = fabsf(p->epsilon);
     const float stripAuto = !(epsAbs == epsAbs) ? (float)SSRLCV_BAND_STRIP : fminf(16.0f, fmaxf(4.0f, 0.4f * epsAbs));
     const float stripT = stripEnvT > 0.0f ? stripEnvT : stripAuto;

@@ -1288,9 +1288,6 @@ template <int NPX, int first, int last, int mmFirst, bool orFlags>
 #ifndef SSRLCV_DOGX_RING
 #define SSRLCV_DOGX_RING 1
 #endif
-#ifndef SSRLCV_PAIR_F32_MINPX
-#define SSRLCV_PAIR_F32_MINPX (~(size_t)0)  // float-sourced octaves keep their two launches (see build_dog)
-#endif
 __global__ __launch_bounds__(256, SSRLCV_DOGX_MINWAVES) void k_dogx(DogxArgs a) {
   typedef float vec __attribute__((ext_vector_type(NPX)));
   const int lane = threadIdx.x & 63;
@@ -1557,7 +1554,7 @@ int launch_dogx(const float* const levels[svp::kGauss], const float* levelMinMax
   a.w = (int)w;
   a.h = (int)h;
   a.minAbs = minAbs;
-  static const int forceNpx = svdev::env("SSRLCV_DOGX_NPX") ? atoi(svdev::env("SSRLCV_DOGX_NPX")) : 0;
+  const int forceNpx = svdev::sw().dogxNpx;
   bool aligned16 = (w & 3) == 0, aligned8 = (w & 1) == 0;
   for (int b = first; b <= last; ++b) {
     aligned16 = aligned16 && (reinterpret_cast<size_t>(levels[b]) & 15) == 0;
@@ -1604,7 +1601,7 @@ int launch_dogx(const float* const levels[svp::kGauss], const float* levelMinMax
 // u8src (nullable): the convolution's input is the 2x upsample of this u8 image (w/2 x h/2) and `in` is not read; only
 // honoured where upsample_fusable() says so (row-staged VALU kernel on full, aligned strips)
 bool upsample_fusable(uint32_t w, uint32_t h, int taps) {
-  static const bool off = svdev::env("SSRLCV_NO_UPSAMPLE_FUSION") != nullptr || svdev::env("SSRLCV_GAUSS_MFMA") != nullptr;
+  const bool off = svdev::sw().noUpsampleFusion || svdev::sw().gaussMfma;
   return !off && taps / 2 <= 8 && w % kTX == 0 && (w & 3) == 0 && (h & 1) == 0;
 }
 
@@ -1650,26 +1647,11 @@ void launch_valu(ConvArgs a, int RT, uint32_t firstColumn, hipStream_t st) {
 // rows there, a quarter to a half of them warm-up) -- but inside build_dog, where octave 1 runs beside the DoG / extrema pass
 // of octave 0, the stage is 10-20 us shorter with them than without (median of 30, three alternations: 1.766-1.783 against
 // 1.787-1.797 ms).  Default: radii 12, 16 and 24 from 2^24 pixels up.
-// SSRLCV_GAUSS_RM=<mask>, SSRLCV_GAUSS_RM_MINPX=<pixels>, SSRLCV_GAUSS_RM_ROWS=<rows per block> override; lab drivers
-// overwrite them in place.  (The first level of octave 0 -- u8 upsample in the loader -- was built on this kernel too:
-// bit-identical, and the stage took the same 1.76-1.77 ms as with k_gauss_strip<6, true>; not kept.)
-int& rm_mask() {
-  static int m = svdev::env("SSRLCV_GAUSS_RM") ? atoi(svdev::env("SSRLCV_GAUSS_RM")) : (4 | 8 | 16);
-  return m;
-}
-size_t& rm_min_px() {
-  static size_t v = svdev::env("SSRLCV_GAUSS_RM_MINPX") ? (size_t)atoll(svdev::env("SSRLCV_GAUSS_RM_MINPX")) : ((size_t)1 << 24);
-  return v;
-}
-// which radii take the one-barrier form of the register-marching kernel (two H buffers, see RmCfg): same bits as rm_mask()
-int& rm_oneb_mask() {
-  static int m = svdev::env("SSRLCV_GAUSS_RM_ONEB") ? atoi(svdev::env("SSRLCV_GAUSS_RM_ONEB")) : 0;
-  return m;
-}
-int& rm_rows() {
-  static int r = svdev::env("SSRLCV_GAUSS_RM_ROWS") ? atoi(svdev::env("SSRLCV_GAUSS_RM_ROWS")) : 0;
-  return r;
-}
+// SSRLCV_GAUSS_RM=<mask>, SSRLCV_GAUSS_RM_MINPX=<pixels>, SSRLCV_GAUSS_RM_ROWS=<rows per block> override (svdev::sw().gaussRm,
+// gaussRmMinPx, gaussRmRows); SSRLCV_GAUSS_RM_ONEB=<mask>: which radii take the one-barrier form of the kernel (two H
+// buffers, see RmCfg).  Lab drivers overwrite the fields in place.  (The first level of octave 0 -- u8 upsample in the
+// loader -- was built on this kernel too: bit-identical, and the stage took the same 1.76-1.77 ms as with
+// k_gauss_strip<6, true>; not kept.)
 
 // binOut (nullable): where the 2x2 bin of the result may be written by the convolution itself; *binned tells whether it was
 // (only k_gauss_mfma2 / k_gauss_tile do it, for even sizes with W % 4 == 0 and no partial strip) -- otherwise the caller
@@ -1689,11 +1671,10 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
   a.x0base = 0;
   a.rowsPerBlock = h;
   a.binOut = nullptr;
-  static const bool noXcdStrips = svdev::env("SSRLCV_NO_XCD_STRIPS") != nullptr;  // (developer build: the plain block order)
-  a.xcdStrips = noXcdStrips ? 0u : 1u;
+  const auto& sw = svdev::sw();
+  a.xcdStrips = sw.noXcdStrips ? 0u : 1u;  // (developer build: the plain block order)
   if (binned) *binned = false;
-  static const bool noBinFold = svdev::env("SSRLCV_NO_BIN_FUSION") != nullptr;
-  const bool canBin = binOut && !noBinFold && (w & 3) == 0 && (h & 1) == 0 && (reinterpret_cast<size_t>(binOut) & 7) == 0;
+  const bool canBin = binOut && !sw.noBinFusion && (w & 3) == 0 && (h & 1) == 0 && (reinterpret_cast<size_t>(binOut) & 7) == 0;
 #ifdef SSRLCV_STAMPS
   a.stamps = g_lab_stamps;
 #endif
@@ -1712,17 +1693,15 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
   // -- the band wastes (16 + 2R - taps) / (16 + 2R) of the matrix pipe, more than half at R = 6, and the VALU kernel is
   // within 12 % of copy speed there.  Default: MFMA from 23 taps up.  SSRLCV_GAUSS_VALU=1 / SSRLCV_GAUSS_MFMA=1 force
   // one of them for every radius.
-  static const bool forceValu = svdev::env("SSRLCV_GAUSS_VALU") != nullptr, forceMfma = svdev::env("SSRLCV_GAUSS_MFMA") != nullptr;
-  static const int mfmaMinR = svdev::env("SSRLCV_GAUSS_MFMA_MINR") ? atoi(svdev::env("SSRLCV_GAUSS_MFMA_MINR")) : 11;
-  const bool useMfma = forceMfma || (!forceValu && !u8src && RT >= mfmaMinR);
+  const bool forceValu = sw.gaussValu, forceMfma = sw.gaussMfma;
+  const bool useMfma = forceMfma || (!forceValu && !u8src && RT >= sw.gaussMfmaMinR);
   // small levels (<= 1024^2): the tile kernel (no marching).  Measured inside build_dog on a 4096^2 image (octave 3 =
   // 1024^2, octave 2 = 2048^2): marching kernels everywhere 2.079 ms, tile kernel for octave 3 2.065, for octaves 2 and
   // 3 2.133 (a 2048^2 level is 1024 tiles, four rounds of one-per-CU blocks).  SSRLCV_GAUSS_TILE_MAXPX=<pixels> moves
   // the threshold (0 = never).  Levels with a side below 64 pixels always go here: it is the one kernel that mirrors with
   // the reference's modulo (the marching kernels reflect once, which needs a side of at least 2R).
-  static const size_t tileMaxPx = svdev::env("SSRLCV_GAUSS_TILE_MAXPX") ? (size_t)atoll(svdev::env("SSRLCV_GAUSS_TILE_MAXPX")) : ((size_t)1 << 20);
   const bool tiny = w < 64 || h < 64;
-  if (tiny || (!u8src && !forceValu && (size_t)w * h <= tileMaxPx)) {
+  if (tiny || (!u8src && !forceValu && (size_t)w * h <= sw.gaussTileMaxPx)) {
     if (u8src) return SSRLCV_ERR_INVALID_ARG;
     if (canBin) { a.binOut = binOut; if (binned) *binned = true; }
 #define SSRLCV_LAUNCH_TILE(RR)                                                                                     \
@@ -1748,10 +1727,10 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
     return SSRLCV_OK;
   }
   // the register-marching kernel (gauss_rm.inc): 256-column strips
-  const int rmMask = rm_mask(), rmRows = rm_rows();
+  const int rmMask = sw.gaussRm, rmRows = sw.gaussRmRows;
   const int R2 = R <= 6 ? 6 : R <= 8 ? 8 : R <= 12 ? 12 : R <= 16 ? 16 : R <= 24 ? 24 : 32;  // radii padded to even values
   const int r2bit = R2 == 6 ? 1 : R2 == 8 ? 2 : R2 == 12 ? 4 : R2 == 16 ? 8 : R2 == 24 ? 16 : 32;
-  if ((rmMask & r2bit) && !forceValu && !forceMfma && (size_t)w * h >= rm_min_px() && !u8src && w >= 256 && h >= 64 && (w & 3) == 0 && (h & 3) == 0 && (reinterpret_cast<size_t>(in) & 15) == 0 &&
+  if ((rmMask & r2bit) && !forceValu && !forceMfma && (size_t)w * h >= sw.gaussRmMinPx && !u8src && w >= 256 && h >= 64 && (w & 3) == 0 && (h & 3) == 0 && (reinterpret_cast<size_t>(in) & 15) == 0 &&
       (reinterpret_cast<size_t>(out) & 15) == 0 && (uint64_t)w * h * 4 < ((uint64_t)1 << 32)) {
     const uint32_t nS = w / 256, cov = nS * 256;
     ConvArgs r = a;
@@ -1782,7 +1761,7 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
   } while (0)
 #define SSRLCV_LAUNCH_RM(RR)                                  \
   do {                                                        \
-    if (rm_oneb_mask() & r2bit) SSRLCV_LAUNCH_RM_V(RR, true); \
+    if (sw.gaussRmOneb & r2bit) SSRLCV_LAUNCH_RM_V(RR, true); \
     else SSRLCV_LAUNCH_RM_V(RR, false);                       \
   } while (0)
     switch (R2) {
@@ -1805,8 +1784,7 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
   // against 0.608 / 0.673 / 0.771 ms per 16384^2 level at 23 / 33 / 47 taps), but octaves >= 1 run beside the DoG pass
   // of the previous octave, whose resident blocks keep the big ones off the CUs: the narrow strips are used for the
   // smaller levels (build_dog 2.57 -> 2.48 ms per 4096^2 image).  SSRLCV_GAUSS_WIDE=1 / SSRLCV_GAUSS_NARROW=1 force one.
-  static const bool forceWide = svdev::env("SSRLCV_GAUSS_WIDE") != nullptr, forceNarrow = svdev::env("SSRLCV_GAUSS_NARROW") != nullptr;
-  const bool wide = R > 24 || forceWide || (!forceNarrow && (size_t)w * h >= ((size_t)1 << 25));
+  const bool wide = R > 24 || sw.gaussWide || (!sw.gaussNarrow && (size_t)w * h >= ((size_t)1 << 25));
   const uint32_t tw = wide ? 256u : 128u;
   const bool mfmaOk = useMfma && (w & 3) == 0 && (reinterpret_cast<size_t>(in) & 15) == 0 && (reinterpret_cast<size_t>(out) & 15) == 0 &&
                       (uint64_t)w * h * 4 < ((uint64_t)1 << 32) && w >= tw;
@@ -1863,16 +1841,12 @@ inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 namespace svp {
-int stream_priority_mode() {
-  static const int m = svdev::env("SSRLCV_PRIO") ? atoi(svdev::env("SSRLCV_PRIO")) : 0;
-  return m;
-}
 PlanAsync* plan_async(const ssrlcv_sift_plan* plan) {
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   if (plan->asyncState == 0) {
     plan->asyncState = -1;
-    if (!svdev::env("SSRLCV_SIFT_SERIAL")) {
+    if (!svdev::sw().siftSerial) {
       PlanAsync* a = new (std::nothrow) PlanAsync();
       bool ok = a != nullptr;
       auto mk = [&](hipEvent_t& e) { ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; };
@@ -1887,11 +1861,11 @@ PlanAsync* plan_async(const ssrlcv_sift_plan* plan) {
           Side pr{nullptr, nullptr, nullptr, nullptr};
           int least = 0, greatest = 0;
           (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-          const int tablePrio = svdev::env("SSRLCV_SIDE_LOW_PRIORITY") ? least : 0;
+          const int tablePrio = svdev::sw().sideLowPriority ? least : 0;
           // SSRLCV_PRIO (developer build): 1 = the gradient tables of describe on their own LOW-priority stream, so that the list
           // chains' short launches get the CU slots the tables' thousands of short-lived blocks keep freeing; 2 = and the
-          // chains' side streams at HIGH priority (see svp::stream_priority_mode)
-          const int prioMode = svp::stream_priority_mode();
+          // chains' side streams at HIGH priority
+          const int prioMode = svdev::sw().prio;
           ok = hipStreamCreateWithPriority(&pr.chain, hipStreamNonBlocking, (prioMode & 2) ? greatest : 0) == hipSuccess &&
                hipStreamCreateWithPriority(&pr.table, hipStreamNonBlocking, tablePrio) == hipSuccess &&
                hipStreamCreateWithPriority(&pr.chain2, hipStreamNonBlocking, (prioMode & 2) ? greatest : 0) == hipSuccess &&
@@ -2233,29 +2207,6 @@ int ssrlcv_sift_plan_level(const ssrlcv_sift_plan* plan, void* workspace, int ki
 }
 
 // ScaleSpace::ScaleSpace with makeDOG = true (src/FeatureFactory.cu:338-440) + searchForExtrema's findExtrema (:847-882)
-namespace {
-// Schedule of the fused DoG / extrema pass (k_dogx).  It needs the levels complete (global min / max), so it follows the
-// convolutions of its octave, on a side stream beside the convolutions of the next octave.  A split form exists: the part
-// that needs only levels 0..3 (DoG 0..2: their min / max and the extrema of DoG level 1) starts as soon as gaussian level 3
-// is complete, beside the convolutions of levels 4 and 5; the rest (DoG 1..4 from levels 1..5: extrema of levels 2 and 3,
-// min / max of 3 and 4) follows after level 5 and ORs its bits into the flag bytes.  With the materialising DoG kernel of
-// round 2 (HBM bound) the split paid on the 2^26-pixel octave; the fused pass is VALU bound and reads levels 1..3 twice in
-// the split form: measured on a 4096^2 image 2.14 ms split on octave 0 against 1.96 ms whole, so the default is whole.
-// SSRLCV_DOG_SPLIT=1: split on every octave (0: never).  SSRLCV_DOGX_WAVES: waves per launch (default 14336: build_dog of a
-// 4096^2 image, median of 30, two sweeps: 8192 waves 1.760-1.776 ms, 10240 1.73-1.75, 12288 1.70-1.71, 14336 1.698-1.699,
-// 16384 1.70-1.71, 20480 1.72-1.73, 24576 1.71-1.72).
-struct DogSchedule {
-  int split;  // 0 never (default), 1 always
-  unsigned waves;
-  DogSchedule() {
-    split = 0;
-    if (const char* e = svdev::env("SSRLCV_DOG_SPLIT")) split = atoi(e) != 0 ? 1 : 0;
-    waves = 14336;
-    if (const char* e = svdev::env("SSRLCV_DOGX_WAVES")) waves = (unsigned)atoi(e) > 0 ? (unsigned)atoi(e) : 14336;
-  }
-};
-}  // namespace
-
 int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixels, void* workspace,
                               ssrlcv_stream_t stream) {
   if (!plan || !pixels || !workspace) return SSRLCV_ERR_INVALID_ARG;
@@ -2268,20 +2219,26 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
   // two sets of gaussian buffers so that octave o+1 never overwrites what DoG(o) is still reading.
   svp::PlanAsync* as = svp::plan_async(plan);
   hipStream_t sd = as ? as->table : st;
-  static const DogSchedule sched;
-  static const bool overlapOctaves = svdev::env("SSRLCV_NO_OCTAVE_OVERLAP") == nullptr;
-  static const int overlapFrom = svdev::env("SSRLCV_OCTAVE_OVERLAP_FROM") ? atoi(svdev::env("SSRLCV_OCTAVE_OVERLAP_FROM")) : 1;
-  static const int deferDog0 = [] {  // 1 or 2 (octave 3 has no successor to wait for), 0: off
-    const int n = svdev::env("SSRLCV_DOGX0_AFTER") ? atoi(svdev::env("SSRLCV_DOGX0_AFTER")) : 0;
-    return n == 1 || n == 2 ? n : 0;
-  }();
+  // Schedule of the fused DoG / extrema pass (k_dogx).  It needs the levels complete (global min / max), so it follows the
+  // convolutions of its octave, on a side stream beside the convolutions of the next octave.  A split form exists: the part
+  // that needs only levels 0..3 (DoG 0..2: their min / max and the extrema of DoG level 1) starts as soon as gaussian level 3
+  // is complete, beside the convolutions of levels 4 and 5; the rest (DoG 1..4 from levels 1..5: extrema of levels 2 and 3,
+  // min / max of 3 and 4) follows after level 5 and ORs its bits into the flag bytes.  With the materialising DoG kernel of
+  // round 2 (HBM bound) the split paid on the 2^26-pixel octave; the fused pass is VALU bound and reads levels 1..3 twice in
+  // the split form: measured on a 4096^2 image 2.14 ms split on octave 0 against 1.96 ms whole, so the default is whole.
+  // SSRLCV_DOG_SPLIT=1: split on every octave (0: never).  SSRLCV_DOGX_WAVES: waves per launch (default 14336: build_dog of a
+  // 4096^2 image, median of 30, two sweeps: 8192 waves 1.760-1.776 ms, 10240 1.73-1.75, 12288 1.70-1.71, 14336 1.698-1.699,
+  // 16384 1.70-1.71, 20480 1.72-1.73, 24576 1.71-1.72).
+  const auto& sw = svdev::sw();
+  const bool overlapOctaves = !sw.noOctaveOverlap;
+  const int overlapFrom = sw.octaveOverlapFrom;
+  const int deferDog0 = sw.dogx0After;  // 1 or 2 (octave 3 has no successor to wait for), 0: off
   // Developer build, SSRLCV_EARLY_POLAR=1: a fused extract starts an octave's gradient tables (k_polar, the first thing the
   // key-point stage needs) on a side stream as soon as that octave's DoG pass is through, beside the small octaves' launches.
   // Exact, measured in round 5 and NOT the default: the scale-space stage grows by 0.36 ms per 4096^2 image (the tables'
   // 16 384 short blocks crowd the small octaves' latency-bound launches) and the key-point stage shrinks by 0.10
   // (profiles/r05_schedule_ab.txt: step 10.19 -> 10.67 ms).
-  static const bool wantEarlyPolar = svdev::env("SSRLCV_EARLY_POLAR") != nullptr;
-  const bool earlyPolar = as && plan->fusedCall && plan->stopStage >= 6 && wantEarlyPolar;
+  const bool earlyPolar = as && plan->fusedCall && plan->stopStage >= 6 && sw.earlyPolar;
   plan->polarInFlight = 0;
   plan->chain0InFlight = 0;  // (a describe that failed half-way may have left it set)
   if (earlyPolar) {  // the tables may still be read by the sampling kernels of the previous extract on this plan: behind the caller's stream
@@ -2318,7 +2275,7 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
   // A_0 .. A_3); what hangs off it (levels 4-5 and the DoG / extrema pass of octave o: phase B_o) goes to side streams and
   // may be held back until the chain is n octaves ahead (B_o waits for the bin of octave o + n), so that the long-lived
   // blocks of the big levels do not sit on the CUs while the chain's short launches look for room.
-  static const int phased = svdev::env("SSRLCV_PHASED") ? atoi(svdev::env("SSRLCV_PHASED")) : 0;
+  const int phased = sw.phased;
   if (as && phased > 0) {
     const int ahead = phased - 1;
     const float* octIn = in;
@@ -2357,7 +2314,7 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
       }
       float* dogPartial = (float*)(ws + plan->off_dogPartial) + (size_t)o * 2 * svp::kDog * svp::kDogMaxWaves;
       rc = launch_dogx(lv, mm, oc.w, oc.h, (uint8_t*)(ws + oc.off_flags), mm + 2 * svp::kGauss, dogPartial, 0, svp::kDog, 0, false, firstNoise,
-                       sched.waves, sb);
+                       sw.dogxWaves, sb);
       if (rc) return rc;
       SSRLCV_HIP_TRY(hipEventRecord(as->dogDone[o], sb));
       if (earlyPolar) {
@@ -2390,23 +2347,21 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
     const float* src = in;
     const float* lv[svp::kGauss] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int b = 0; b < svp::kGauss; ++b) lv[b] = (const float*)(ws + offGauss[b]);
-    const bool split = as && sched.split == 1;
+    const bool split = as && sw.dogSplit == 1;
     // (Round 3 handed the row chunks of odd levels out bottom-up, so that a level starts on the rows its predecessor wrote
     // last and finds them in the 256 MB memory-side cache: build_dog 2.07-2.11 ms against 2.05-2.08 top-down, no gain.)
     // Levels 0 + 1 in one launch (gauss_pair_rm.inc) where that wins: the u8-sourced first octave from 2^26 pixels up (per
     // 8192^2 level pair 220 us against 253 for the two launches; a 4096^2 pair 77 against 68, and with a float source the
     // fused form only breaks even at 8192^2: tools/gauss_pair_lab.hip, profiles/r06_kernel_ab.txt).
     // SSRLCV_GAUSS_PAIR_MINPX=<pixels> moves the threshold (developer build), SSRLCV_NO_GAUSS_PAIR=1 turns it off.
-    static const size_t pairMinPx = svdev::env("SSRLCV_GAUSS_PAIR_MINPX") ? (size_t)atoll(svdev::env("SSRLCV_GAUSS_PAIR_MINPX")) : ((size_t)1 << 26);
-    // float-sourced octaves (o >= 1): SSRLCV_GAUSS_PAIR_MINPX_F32=<pixels>
-    static const size_t pairMinPxF32 = svdev::env("SSRLCV_GAUSS_PAIR_MINPX_F32") ? (size_t)atoll(svdev::env("SSRLCV_GAUSS_PAIR_MINPX_F32")) : SSRLCV_PAIR_F32_MINPX;
+    // float-sourced octaves (o >= 1): SSRLCV_GAUSS_PAIR_MINPX_F32=<pixels> (default: -DSSRLCV_PAIR_F32_MINPX, never)
     int firstLevel = 0;
-    const bool u8Pair = o == 0 && fuseUpsample && (size_t)oc.w * oc.h >= pairMinPx;
-    const bool f32Pair = !(o == 0 && fuseUpsample) && (size_t)oc.w * oc.h >= pairMinPxF32;
+    const bool u8Pair = o == 0 && fuseUpsample && (size_t)oc.w * oc.h >= sw.gaussPairMinPx;
+    const bool f32Pair = !(o == 0 && fuseUpsample) && (size_t)oc.w * oc.h >= sw.gaussPairMinPxF32;
     if ((u8Pair || f32Pair) && pair_rm_usable(oc.w, oc.h) &&
         pair_usable(oc.w, oc.h, oc.taps[0], oc.taps[1], f32Pair ? in : (const float*)(ws + offGauss[0]), (float*)(ws + offGauss[0]), (float*)(ws + offGauss[1]))) {
       // (developer build, SSRLCV_GAUSS_PAIR_FORM=valu: the vector formulation of the fused pair, gauss_pair.inc -- exact, slower)
-      static const bool valuForm = svdev::env("SSRLCV_GAUSS_PAIR_FORM") != nullptr && svdev::env("SSRLCV_GAUSS_PAIR_FORM")[0] == 'v';
+      const bool valuForm = sw.gaussPairValuForm;
       const float* pin = f32Pair ? in : nullptr;
       const uint8_t* pu8 = f32Pair ? nullptr : pixels;
       rc = valuForm ? launch_pair(pin, pu8, (float*)(ws + offGauss[0]), (float*)(ws + offGauss[1]), oc.w, oc.h, oc.weights[0], oc.weights[1], mm, mm + 2, so)
@@ -2441,7 +2396,7 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
           for (int q = 0; q < svp::kGauss; ++q) lv0[q] = (const float*)(ws + plan->off_gauss[0][q]);
           SSRLCV_HIP_TRY(hipStreamWaitEvent(sd, as->binDone[o], 0));
           rc = launch_dogx(lv0, mmAll, o0.w, o0.h, (uint8_t*)(ws + o0.off_flags), mmAll + 2 * svp::kGauss, (float*)(ws + plan->off_dogPartial), 0,
-                           svp::kDog, 0, false, firstNoise, sched.waves, sd);
+                           svp::kDog, 0, false, firstNoise, sw.dogxWaves, sd);
           if (rc) return rc;
           SSRLCV_HIP_TRY(hipEventRecord(as->dogDone[0], sd));
         }
@@ -2449,7 +2404,7 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
       if (split && b == 3) {  // DoG 0..2: extrema of level 1, min / max of 0..2
         SSRLCV_HIP_TRY(hipEventRecord(as->levelDone[o][b], so));
         SSRLCV_HIP_TRY(hipStreamWaitEvent(sdo, as->levelDone[o][b], 0));
-        rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 0, 3, 0, false, firstNoise, sched.waves, sdo);
+        rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 0, 3, 0, false, firstNoise, sw.dogxWaves, sdo);
         if (rc) return rc;
       }
     }
@@ -2458,8 +2413,8 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
       SSRLCV_HIP_TRY(hipStreamWaitEvent(sdo, as->convDone[o], 0));
     }
     if (deferDog0 && as && o == 0) continue;  // (its DoG pass is queued from octave deferDog0's iteration, see above)
-    if (split) rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 1, svp::kDog, 3, true, firstNoise, sched.waves, sdo);
-    else rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 0, svp::kDog, 0, false, firstNoise, sched.waves, sdo);
+    if (split) rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 1, svp::kDog, 3, true, firstNoise, sw.dogxWaves, sdo);
+    else rc = launch_dogx(lv, mm, oc.w, oc.h, flags, mm + 2 * svp::kGauss, dogPartial, 0, svp::kDog, 0, false, firstNoise, sw.dogxWaves, sdo);
     if (rc) return rc;
     if (as) SSRLCV_HIP_TRY(hipEventRecord(as->dogDone[o], sdo));
 #if SSRLCV_EARLY_CHAIN0
@@ -2470,8 +2425,7 @@ int ssrlcv_hip_sift_build_dog(const ssrlcv_sift_plan* plan, const uint8_t* pixel
     // tail shares the machine now), the key-point stage shrinks by 0.13.  Octave 1's chain as well (mask 3: 10.19 / 10.25)
     // or all four (mask 15: 10.27 / 10.26) lose: behind octave 0's chain on the same stream they give up their own.
     // Developer build: SSRLCV_NO_EARLY_CHAIN=1 keeps every chain in describe.
-    static const bool noEarlyChain = svdev::env("SSRLCV_NO_EARLY_CHAIN") != nullptr;
-    if (as && !noEarlyChain && ((SSRLCV_EARLY_CHAIN0 >> o) & 1) && plan->fusedCall && plan->stopStage >= 6) {
+    if (as && !sw.noEarlyChain && ((SSRLCV_EARLY_CHAIN0 >> o) & 1) && plan->fusedCall && plan->stopStage >= 6) {
       SSRLCV_HIP_TRY(hipStreamWaitEvent(as->chain2, as->dogDone[o], 0));
       rc = svp::launch_chain_octave(plan, ws, o, as->chain2);
       if (rc) return rc;

@@ -6,6 +6,7 @@ cpu_baseline leg may import this module's `oracle()`.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -125,9 +126,19 @@ def limit_openmp():
     return n
 
 
+def dev_switch_names():
+    """The developer switches the library reads: the quoted names of the table in ssrlcv_amd/csrc/dev_switch.h."""
+    header = open(os.path.join(ROOT, "ssrlcv_amd", "csrc", "dev_switch.h")).read()
+    return set(re.findall(r'"(SSRLCV_[A-Z0-9_]+)"', header))
+
+
 def dev_env(**switches):
     """Environment of a child process that loads the DEVELOPER build of the HIP library (ssrlcv_amd/_lib.py: the default
-    is the release build, in which every SSRLCV_* switch is compiled out) with the given switches set."""
+    is the release build, in which every SSRLCV_* switch is compiled out) with the given switches set.  A switch the
+    library does not declare is an error: the child would run the default path and a formulation test would pass on it."""
+    unknown = set(switches) - dev_switch_names()
+    if unknown:
+        raise KeyError("not a developer switch of csrc/dev_switch.h: %s" % ", ".join(sorted(unknown)))
     env = dict(os.environ, SSRLCV_DEV_BUILD="1")
     env.pop("SSRLCV_HIP_LIB", None)
     env.update(switches)

@@ -97,25 +97,60 @@ def test_sift_plan_layout_is_host_only():
                                        ctypes.byref(plan)) == -4
 
 
+def _switch_strings(path):
+    """every whole C string of the form SSRLCV_[A-Z0-9_]+ in a binary"""
+    return {m.decode() for m in re.findall(rb"(?<![\x20-\x7e])(SSRLCV_[A-Z0-9_]+)\x00", open(path, "rb").read())}
+
+
+INSTRUMENTED_ONLY = {"SSRLCV_TIMING_THETAS_SEL"}  # read by `make instrumented` builds alone
+
+
 def test_release_build_has_no_developer_switches():
     """`make release` (csrc/Makefile, -DSSRLCV_RELEASE): the same exports, and none of the SSRLCV_* switch names of the
-    developer build survive in it -- svdev::env() (csrc/dev_switch.h) is a constant nullptr there, so a caller's environment
-    cannot choose a code path of the drop-in library."""
+    developer build survive in it -- svdev::sw() (csrc/dev_switch.h) is a compile-time constant holding every default
+    there, so a caller's environment cannot choose a code path of the drop-in library.  The developer build holds exactly
+    the names the table of dev_switch.h declares, and that header is the only place in csrc/ that reads the environment."""
+    import glob
     import subprocess
     from ssrlcv_amd import _lib
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "ssrlcv_amd", "csrc"), "release"])
+    csrc = os.path.join(ROOT, "ssrlcv_amd", "csrc")
+    subprocess.check_call(["make", "-s", "-C", csrc, "release"])
     rel = os.path.join(ROOT, "ssrlcv_amd", "libssrlcv_hip_release.so")
     lib = ctypes.CDLL(rel)
     for name in _lib.EXPORTED:
         assert hasattr(lib, name), name
+    declared = H.dev_switch_names()
+    assert len(declared) == 42 and INSTRUMENTED_ONLY < declared, sorted(declared)
     blob = open(rel, "rb").read()
     dev = open(os.path.join(ROOT, "ssrlcv_amd", "libssrlcv_hip.so"), "rb").read()
-    for name in (b"SSRLCV_GAUSS_VALU", b"SSRLCV_DOGX_NPX", b"SSRLCV_MATCH_F16", b"SSRLCV_SIFT_SERIAL", b"SSRLCV_MERGE_THREADS"):
-        assert name in dev and name not in blob, name
-    # no raw getenv of a switch is left in the hot-path sources
-    for f in ("pyramid.hip", "keypoints.hip", "matcher.hip", "merge.hip", "filter.hip", "pointcloud.hip", "pose.hip", "host_merge.cpp"):
-        src = open(os.path.join(ROOT, "ssrlcv_amd", "csrc", f)).read()
-        assert not re.search(r'(?<![A-Za-z_:])getenv\(', src), f
+    for name in sorted(declared - INSTRUMENTED_ONLY):
+        assert name.encode() in dev and name.encode() not in blob, name
+    assert _switch_strings(os.path.join(ROOT, "ssrlcv_amd", "libssrlcv_hip.so")) == declared - INSTRUMENTED_ONLY
+    assert _switch_strings(rel) == set()
+    # no raw getenv is left in the library's sources, and the switches are read in dev_switch.h alone
+    sources = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.inc")) + glob.glob(os.path.join(csrc, "*.cpp")))
+    names = {os.path.basename(f) for f in sources}
+    assert {"pyramid.hip", "keypoints.hip", "matcher.hip", "merge.hip", "filter.hip", "pointcloud.hip", "pose.hip", "ransac.hip",
+            "cloud.hip", "host_merge.cpp", "gauss_pair.inc", "gauss_pair_rm.inc", "gauss_rm.inc", "matcher_i8.inc"} <= names
+    for f in sources + sorted(glob.glob(os.path.join(csrc, "*.h"))):
+        src = open(f).read()
+        if os.path.basename(f) != "dev_switch.h":
+            assert not re.search(r'(?<![A-Za-z_:])getenv\(', src), f
+            assert "svdev::env(" not in src, f
+
+
+def test_dev_env_refuses_a_switch_the_library_does_not_declare():
+    """tests/helpers.py dev_env() is how the formulation tests choose a code path: a name that csrc/dev_switch.h does not
+    declare would leave the child on the default path and the test would pass on it."""
+    env = H.dev_env(SSRLCV_GAUSS_VALU="1")
+    assert env["SSRLCV_GAUSS_VALU"] == "1" and env["SSRLCV_DEV_BUILD"] == "1"
+    for wrong in ("SSRLCV_GAUSS_VALUE", "SSRLCV_GAUS_VALU", "GAUSS_VALU", "SSRLCV_DEV_BUILD"):
+        try:
+            H.dev_env(**{wrong: "1"})
+        except KeyError as e:
+            assert wrong in str(e)
+        else:
+            raise AssertionError("dev_env accepted %s" % wrong)
 
 
 def test_the_default_library_is_the_release_build():

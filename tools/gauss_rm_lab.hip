@@ -10,9 +10,9 @@
 int main(int argc, char** argv) {
   const uint32_t W = argc > 1 ? (uint32_t)atoi(argv[1]) : 8192;
   const uint32_t H = argc > 2 ? (uint32_t)atoi(argv[2]) : W;
-  rm_rows() = argc > 3 ? atoi(argv[3]) : 0;
-  rm_min_px() = 0;
-  rm_oneb_mask() = getenv("RM_LAB_ONEB") ? atoi(getenv("RM_LAB_ONEB")) : 0;
+  svdev::sw().gaussRmRows = argc > 3 ? atoi(argv[3]) : 0;
+  svdev::sw().gaussRmMinPx = 0;
+  svdev::sw().gaussRmOneb = getenv("RM_LAB_ONEB") ? atoi(getenv("RM_LAB_ONEB")) : 0;
   const size_t n = (size_t)W * H;
   float *in, *outA, *outB, *binA, *binB, *mm;
   hipMalloc(&in, n * 4); hipMalloc(&outA, n * 4); hipMalloc(&outB, n * 4);
@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
     bool binnedA = false, binnedB = false;
     float ms[2];
     for (int v = 0; v < 2; ++v) {
-      rm_mask() = v ? 63 : 0;
+      svdev::sw().gaussRm = v ? 63 : 0;
       float* out = v ? outB : outA;
       float* bin = v ? binB : binA;
       hipMemset(out, 0xff, n * 4);
@@ -62,7 +62,7 @@ int main(int argc, char** argv) {
     {  // one more launch of the register-marching kernel with s_memtime stamps (100 MHz ticks) in one block
       hipMemset(stamps, 0, ns * 8);
       g_lab_stamps = stamps;
-      rm_mask() = 63;
+      svdev::sw().gaussRm = 63;
       launch_conv(in, outB, nullptr, W, H, ksz, w, nullptr, nullptr, nullptr, binB, nullptr);
       hipDeviceSynchronize();
       g_lab_stamps = nullptr;
