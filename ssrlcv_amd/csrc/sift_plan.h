@@ -78,6 +78,11 @@ struct OctavePlan {
 // and plan the chains were measured waiting for each other behind a shared queue.  Starting octave 0's chain and the
 // polar tables earlier, beside the convolutions of octaves 1-3, was measured too: the convolutions lose as much as the
 // chain gains (every one of these kernels fills the chip on its own), so the order below is kept.
+// Round 7: in a fused extract octave 0's chain already runs on `chain2` (queued by build_dog), so describe has nothing for
+// the caller's stream until the orientation kernel: the polar tables run THERE (one hop behind build_dog's join instead of a
+// second one to `table`), `chain2` runs k_orient_prologue behind the last chain (after waiting for octave 1's on `chain`), and
+// that one event is all the caller's stream waits for; from the tables on the stage is a plain run of kernels on the caller's
+// stream.  A stand-alone describe keeps octave 0's chain and the prologue on the caller's stream and the tables on `table`.
 // One call per plan may be in flight at a time.
 constexpr unsigned kDogMaxBlocks = 16384;               // grid bound of the streaming DoG kernel (256-thread blocks)
 constexpr unsigned kDogMaxWaves = kDogMaxBlocks * 4;
@@ -114,7 +119,7 @@ struct ssrlcv_sift_plan {
   size_t off_state;    // OctaveState[kOctaves]
   size_t off_extremaCounts;  // scratch for the pixel-domain partition
   size_t off_dogPartial;     // per-wave {min, max} partials of the streaming DoG kernel: float[2 * kDog][kDogMaxWaves]
-  size_t off_groups;         // 4 KB: range tables and control words of the pipelined sampling groups (keypoints.hip)
+  size_t off_groups;         // 4 KB: range tables and control words of the sampling kernels and the expansions (keypoints.hip GroupBlock)
   size_t total;
   uint32_t maxFeatures;
   int stopStage;

@@ -11,7 +11,7 @@ import json
 import sys
 
 DESCRIBE = ("k_count", "k_scan", "k_scatter", "k_refine", "k_flag_", "k_book_", "k_state_reset", "k_polar",
-            "k_build_ranges", "k_thetas", "k_desc_consts", "k_descriptors")
+            "k_build_ranges", "k_orient_prologue", "k_thetas", "k_expand_orient", "k_desc_consts", "k_descriptors")
 VALU_PEAK_GINST = 1024 * 2.4 / 2.0
 HBM_PEAK_GBS = 8000.0
 
