@@ -43,7 +43,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      set/get_match_arithmetic, ssrlcv_sift_plan_set_stage_event added
  *   3  round 6: ssrlcv_hip_abi_version itself
  *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added;
- *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals */
+ *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals;
+ *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128 */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -263,6 +264,50 @@ int ssrlcv_hip_seed_distances_u8x128(const ssrlcv_sift_feature* query, uint32_t 
 int ssrlcv_hip_match_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery, const ssrlcv_sift_feature* target,
                             uint32_t numTarget, const float* seedDistances, const ssrlcv_match_params* params_host,
                             int outKind, void* out, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- two nearest neighbours, Lowe's ratio test and the mutual check.
+ * PARITY UNPINNED: upstream rejects a match by an absolute threshold or by its ratio against a seed image only; it has no
+ * second neighbour and no cross check, so this contract is the library's own.
+ *   order       the neighbours of query q are the two targets smallest by the key (distance, f mod 32, f) -- the key of
+ *               ssrlcv_hip_match_u8x128, so neighbour 1 is that call's brute-force (mode 0) winner at an infinite
+ *               threshold.  distance = the exact integer squared L2 of the descriptors (< 2^23).
+ *   missing     a neighbour that does not exist (numTarget 0 or 1): index UINT32_MAX, distance +inf.
+ *   ratio       passes iff (float)d1 < (ratio * ratio) * (float)d2, each product rounded to float32 in that order.  A
+ *               missing second neighbour passes; ratio == 0: no test.  0 <= ratio <= 1 and finite, anything else
+ *               SSRLCV_ERR_INVALID_ARG.  d1 == d2 fails for every ratio > 0 (duplicate targets are ambiguous).
+ *   absolute    a match with d1 >= absoluteThreshold is rejected, as in ssrlcv_hip_match_u8x128.
+ *   mutual      != 0: the match (q, j) is kept only if q is neighbour 1 of target j among ALL queries -- same key, with
+ *               (q mod 32, q); no threshold and no ratio applies to that reverse pass.
+ *   outputs     the structs of ssrlcv_hip_match_u8x128 (outKind), a kept or rejected entry laid out as that call writes
+ *               it: distance = d1 (absoluteThreshold when there is no neighbour); a rejected uint2_pair has b = a, a rejected
+ *               DMatch / Match invalid = 1 and zero key points; padding bytes are zero.  ssrlcv_hip_compact_matches[_async]
+ *               and ssrlcv_hip_matchset_from_matches take them unchanged.
+ *   workspace   ssrlcv_hip_match2_workspace_bytes(numQuery, numTarget) bytes.  It BEGINS with the layout of
+ *               ssrlcv_hip_match_workspace_bytes(numQuery, numTarget), so the same buffer is a valid workspace for
+ *               compacting the numQuery results; the partial keys of the target splits and the (numTarget, numQuery)
+ *               layout of the mutual check's reverse pass follow.
+ *   determinism both calls are stream-ordered without host synchronisation (kernels only, one chain on `stream`: they may
+ *               be captured into a graph) and use no atomics for their results: two calls on the same inputs give
+ *               bit-equal outputs.
+ *   arguments   checked before any launch: query, out / index_out, workspace, params_host NULL, target NULL with
+ *               numTarget > 0, outKind outside 0..2, ratio, a NaN absoluteThreshold -> SSRLCV_ERR_INVALID_ARG; then
+ *               numQuery == 0 -> SSRLCV_OK; then a workspace too small -> SSRLCV_ERR_WORKSPACE.
+ * The distance contraction is int8 MFMA whatever ssrlcv_hip_set_match_arithmetic says (both arithmetics are exact); the
+ * reverse pass of the mutual check is the one-nearest matcher and follows that setting. */
+size_t ssrlcv_hip_match2_workspace_bytes(uint32_t numQuery, uint32_t numTarget);
+/* index_out: numQuery x 2 uint32; dist_out (NULL: none): numQuery x 2 float. */
+int ssrlcv_hip_match_knn2_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery, const ssrlcv_sift_feature* target,
+                                 uint32_t numTarget, uint32_t* index_out, float* dist_out, void* workspace,
+                                 size_t workspaceBytes, ssrlcv_stream_t stream);
+typedef struct {
+  uint32_t queryImageID, targetImageID; /* written into the outputs */
+  float ratio;
+  float absoluteThreshold;
+  int mutual;
+} ssrlcv_ratio_params;
+int ssrlcv_hip_match_ratio_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery, const ssrlcv_sift_feature* target,
+                                  uint32_t numTarget, const ssrlcv_ratio_params* params_host, int outKind, void* out,
+                                  void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* validateMatches (src/MatchFactory.cu:32-108): stable removal of invalid entries (thrust::remove_if).  In place;
  * *count_host receives the survivors.  Synchronous (returns after the count is on the host, like the reference). */

@@ -64,7 +64,7 @@ def load():
                      "ssrlcv_hip_ba_sweep2_workspace_bytes", "ssrlcv_hip_sort_workspace_bytes",
                      "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes",
                      "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_knn_workspace_bytes",
-                     "ssrlcv_hip_neighbor_filter_workspace_bytes"):
+                     "ssrlcv_hip_neighbor_filter_workspace_bytes", "ssrlcv_hip_match2_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
     return _lib
@@ -83,7 +83,8 @@ EXPORTED = [
     "ssrlcv_hip_knn_workspace_bytes", "ssrlcv_hip_knn", "ssrlcv_hip_neighbor_filter_workspace_bytes",
     "ssrlcv_hip_neighbor_distance_filter", "ssrlcv_hip_point_normals",
     "ssrlcv_projection_matrix_host", "ssrlcv_hip_match_workspace_bytes", "ssrlcv_hip_set_match_arithmetic", "ssrlcv_hip_get_match_arithmetic", "ssrlcv_hip_seed_distances_u8x128",
-    "ssrlcv_hip_match_u8x128", "ssrlcv_hip_compact_matches", "ssrlcv_hip_compact_matches_async", "ssrlcv_hip_keypoints_from_members",
+    "ssrlcv_hip_match_u8x128", "ssrlcv_hip_match2_workspace_bytes", "ssrlcv_hip_match_knn2_u8x128", "ssrlcv_hip_match_ratio_u8x128",
+    "ssrlcv_hip_compact_matches", "ssrlcv_hip_compact_matches_async", "ssrlcv_hip_keypoints_from_members",
     "ssrlcv_hip_matchset_from_matches", "ssrlcv_merge_matches_host", "ssrlcv_merge_matches_host_mode", "ssrlcv_host_free", "ssrlcv_assign_pairs_host",
     "ssrlcv_hip_merge_workspace_bytes", "ssrlcv_hip_merge_matches",
     "ssrlcv_hip_sort_workspace_bytes", "ssrlcv_hip_sort_keys_u32",

@@ -349,6 +349,44 @@ def match(query_d, nq, target_d, nt, params, out_kind=OUT_DMATCH, seed_d=None, w
     return out
 
 
+# ------------------------------------------------------------------ two nearest neighbours, ratio test, mutual check
+class RatioParams(ctypes.Structure):
+    _fields_ = [("queryImageID", c_u32), ("targetImageID", c_u32), ("ratio", c_f32), ("absoluteThreshold", c_f32),
+                ("mutual", c_int)]
+
+
+def match2_workspace(nq, nt):
+    """Workspace of match_knn2 / match_ratio; it begins with match_workspace(nq, nt)'s layout, so compact_matches takes it."""
+    return dev_bytes(LIB.ssrlcv_hip_match2_workspace_bytes(c_u32(nq), c_u32(nt)))
+
+
+def match_knn2(query_d, nq, target_d, nt, dist=True, workspace=None):
+    """ssrlcv_hip_match_knn2_u8x128 -> (index int32 [nq, 2] (UINT32_MAX reads as -1), distance float32 [nq, 2] or None):
+    the two targets smallest by (distance, f mod 32, f).  Stream-ordered."""
+    ws = workspace if workspace is not None else match2_workspace(nq, nt)
+    idx = torch.empty((nq, 2), dtype=torch.int32, device="cuda")
+    d = torch.empty((nq, 2), dtype=torch.float32, device="cuda") if dist else None
+    check(LIB.ssrlcv_hip_match_knn2_u8x128(ptr(query_d), c_u32(nq), ptr(target_d) if nt else c_vp(0), c_u32(nt), ptr(idx), ptr(d),
+                                           ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return idx, d
+
+
+def make_ratio_params(query_id, target_id, ratio=0.8, absolute=3.0e9, mutual=False):
+    return RatioParams(query_id, target_id, ratio, absolute, 1 if mutual else 0)
+
+
+def match_ratio(query_d, nq, target_d, nt, params, out_kind=OUT_DMATCH, workspace=None, out=None):
+    """ssrlcv_hip_match_ratio_u8x128: nearest neighbour kept by Lowe's ratio test, the absolute threshold and (params.mutual)
+    the cross check -> nq records of out_kind, laid out as match() writes them."""
+    ws = workspace if workspace is not None else match2_workspace(nq, nt)
+    if out is None:
+        out = dev_bytes(nq * _OUT_SIZE[out_kind])
+    check(LIB.ssrlcv_hip_match_ratio_u8x128(ptr(query_d), c_u32(nq), ptr(target_d) if nt else c_vp(0), c_u32(nt),
+                                            ctypes.byref(params), c_int(out_kind), ptr(out), ptr(ws), c_sz(ws.numel()),
+                                            stream_ptr()))
+    return out
+
+
 def compact_matches(out_kind, matches_d, n, workspace):
     cnt = c_u32(0)
     check(LIB.ssrlcv_hip_compact_matches(c_int(out_kind), ptr(matches_d), c_u32(n), ctypes.byref(cnt), ptr(workspace),

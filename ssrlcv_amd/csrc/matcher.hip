@@ -728,6 +728,7 @@ __global__ __launch_bounds__(256, SSRLCV_MATCH_WPS) void k_match(const _Float16*
 }
 
 #include "matcher_i8.inc"
+#include "matcher_knn2.inc"
 
 // ---- finalisation: key -> reference output structs ----------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_finalize(const unsigned long long* __restrict__ bestKey, uint32_t nq,
@@ -834,8 +835,17 @@ Layout make_layout(uint32_t nq, uint32_t nt) {
   return L;
 }
 
+// run_match's key array starts at kNoKey by hipMemsetAsync; keysByKernel does the same with this kernel: a memset node of a
+// captured graph was seen to leave other bytes than 0xff from the second replay on (HIP runtime of ROCm 7, MI355X), and
+// ssrlcv_hip_match_ratio_u8x128 promises a call that replays.
+__global__ __launch_bounds__(256) void k_fill_keys(unsigned long long* __restrict__ keys, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keys[i] = kNoKey;
+}
+
 int run_match(const ssrlcv_sift_feature* query, uint32_t nq, const ssrlcv_sift_feature* target, uint32_t nt, int mode,
-              const ssrlcv_match_params* p, float absThreshold, char* ws, const Layout& L, hipStream_t st, bool seedOnly = false) {
+              const ssrlcv_match_params* p, float absThreshold, char* ws, const Layout& L, hipStream_t st, bool seedOnly = false,
+              bool keysByKernel = false) {
   _Float16* pq = (_Float16*)(ws + L.off_pq);
   _Float16* pt = (_Float16*)(ws + L.off_pt);
   float* nqv = (float*)(ws + L.off_nq);
@@ -902,7 +912,10 @@ int run_match(const ssrlcv_sift_feature* query, uint32_t nq, const ssrlcv_sift_f
     hipLaunchKernelGGL(k_pack_i8, dim3((L.nt_pad * 16 + 255) / 256), dim3(256), 0, st, target, nt, L.nt_pad, 1, permT,
                        (uint8_t*)pt, (int*)(ws + L.off_nt), lt, 1);
   }
-  SSRLCV_HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)L.nq_pad * 8, st));
+  if (keysByKernel)
+    hipLaunchKernelGGL(k_fill_keys, dim3((L.nq_pad + 255) / 256), dim3(256), 0, st, keys, L.nq_pad);
+  else
+    SSRLCV_HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)L.nq_pad * 8, st));
   const float eps = mode != 0 ? p->epsilon : 0.0f;
   launch_geom(permQ);  // (packed order; no-op in mode 0)
   if (band)
@@ -955,6 +968,56 @@ int run_match(const ssrlcv_sift_feature* query, uint32_t nq, const ssrlcv_sift_f
                          (const uint32_t*)nullptr, (const Box*)nullptr, (const Box*)nullptr, (const BandR*)nullptr,
                          (const uint32_t*)nullptr);
   }
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+// ---- two nearest neighbours (matcher_knn2.inc) -------------------------------------------------------------------------
+// Workspace: the layout of ssrlcv_hip_match_workspace_bytes(nq, nt) first (packed rows of the forward pass; its scratch
+// region serves compact_matches on the nq results), then the partial keys [splits][2 lane halves][nq_pad], the merged pairs
+// [nq_pad], then the (nt, nq) layout of the mutual check's reverse pass.
+struct Layout2 {
+  Layout fwd, rev;
+  uint32_t splits, tilesPerSplit;
+  size_t off_partial, off_best, off_rev, total;
+};
+
+Layout2 make_layout2(uint32_t nq, uint32_t nt) {
+  Layout2 M;
+  M.fwd = make_layout(nq, nt);
+  M.rev = make_layout(nt, nq);
+  // the split rule of the brute-force pass: until the grid has >= 1024 blocks or tiles run out
+  const uint32_t qblocks = M.fwd.nq_pad / kQPerBlock8Knn2, numTiles = M.fwd.nt_pad / 32;
+  M.splits = 1;
+  while (qblocks * M.splits < 1024 && M.splits * 2 <= numTiles && numTiles / (M.splits * 2) >= 16) M.splits *= 2;
+  M.tilesPerSplit = (numTiles + M.splits - 1) / M.splits;
+  size_t o = M.fwd.total;
+  auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
+  M.off_partial = take((size_t)M.splits * 2 * M.fwd.nq_pad * sizeof(Key2));
+  M.off_best = take((size_t)M.fwd.nq_pad * sizeof(Key2));
+  M.off_rev = take(M.rev.total);
+  M.total = o;
+  return M;
+}
+
+// pack -> k_match2_i8 -> k_knn2_merge: the two smallest keys of every query at ws + M.off_best.  One chain of kernels.
+int run_knn2(const ssrlcv_sift_feature* query, uint32_t nq, const ssrlcv_sift_feature* target, uint32_t nt, char* ws,
+             const Layout2& M, hipStream_t st) {
+  const Layout& L = M.fwd;
+  uint8_t* pq = (uint8_t*)(ws + L.off_pq);
+  uint8_t* pt = (uint8_t*)(ws + L.off_pt);
+  int* nqv = (int*)(ws + L.off_nq);
+  int* ntn = (int*)(ws + L.off_nt);
+  Key2* partial = (Key2*)(ws + M.off_partial);
+  Key2* best = (Key2*)(ws + M.off_best);
+  hipLaunchKernelGGL(k_pack_i8, dim3((L.nq_pad * 16 + 255) / 256), dim3(256), 0, st, query, nq, L.nq_pad, 0,
+                     (const uint32_t*)nullptr, pq, nqv, (ssrlcv_float2*)nullptr, 0);
+  hipLaunchKernelGGL(k_pack_i8, dim3((L.nt_pad * 16 + 255) / 256), dim3(256), 0, st, target, nt, L.nt_pad, 1,
+                     (const uint32_t*)nullptr, pt, ntn, (ssrlcv_float2*)nullptr, 1);
+  hipLaunchKernelGGL((k_match2_i8<kQT8Knn2>), dim3(L.nq_pad / kQPerBlock8Knn2, M.splits), dim3(256), 0, st, (const uint8_t*)pq,
+                     (const uint8_t*)pt, (const int*)nqv, (const int*)ntn, L.nq_pad, nt, M.tilesPerSplit, partial);
+  hipLaunchKernelGGL(k_knn2_merge, dim3((nq + 255) / 256), dim3(256), 0, st, (const Key2*)partial, nq, L.nq_pad, M.splits * 2,
+                     best);
   SSRLCV_LAUNCH_CHECK();
   return SSRLCV_OK;
 }
@@ -1102,6 +1165,54 @@ int ssrlcv_hip_match_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery,
                      params_host->queryImageID, params_host->targetImageID, params_host->relativeThreshold,
                      params_host->absoluteThreshold, outKind, params_host->mode,
                      params_host->mode != 0 ? (const uint32_t*)((char*)workspace + L.off_permq) : (const uint32_t*)nullptr, out);
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+size_t ssrlcv_hip_match2_workspace_bytes(uint32_t numQuery, uint32_t numTarget) {
+  return make_layout2(numQuery, numTarget).total;
+}
+
+int ssrlcv_hip_match_knn2_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery, const ssrlcv_sift_feature* target,
+                                 uint32_t numTarget, uint32_t* index_out, float* dist_out, void* workspace,
+                                 size_t workspaceBytes, ssrlcv_stream_t stream) {
+  if (!query || !index_out || !workspace || (numTarget && !target)) return SSRLCV_ERR_INVALID_ARG;
+  if (numQuery == 0) return SSRLCV_OK;
+  const Layout2 M = make_layout2(numQuery, numTarget);
+  if (workspaceBytes < M.total) return SSRLCV_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = run_knn2(query, numQuery, target, numTarget, (char*)workspace, M, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_knn2_out, dim3((numQuery + 255) / 256), dim3(256), 0, st, (const Key2*)((char*)workspace + M.off_best),
+                     numQuery, index_out, dist_out);
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+int ssrlcv_hip_match_ratio_u8x128(const ssrlcv_sift_feature* query, uint32_t numQuery, const ssrlcv_sift_feature* target,
+                                  uint32_t numTarget, const ssrlcv_ratio_params* params_host, int outKind, void* out,
+                                  void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream) {
+  if (!query || !out || !workspace || !params_host || (numTarget && !target)) return SSRLCV_ERR_INVALID_ARG;
+  if (outKind < 0 || outKind > 2) return SSRLCV_ERR_INVALID_ARG;
+  const float ratio = params_host->ratio, absThreshold = params_host->absoluteThreshold;
+  if (!(ratio >= 0.0f && ratio <= 1.0f) || absThreshold != absThreshold) return SSRLCV_ERR_INVALID_ARG;
+  if (numQuery == 0) return SSRLCV_OK;
+  const Layout2 M = make_layout2(numQuery, numTarget);
+  if (workspaceBytes < M.total) return SSRLCV_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int rc = run_knn2(query, numQuery, target, numTarget, ws, M, st);
+  if (rc) return rc;
+  // mutual check: the plain one-nearest match with the roles swapped, no threshold (no targets: nothing to check)
+  const unsigned long long* reverseKey = nullptr;
+  if (params_host->mutual && numTarget) {
+    rc = run_match(target, numTarget, query, numQuery, 0, nullptr, FLT_MAX, ws + M.off_rev, M.rev, st, false, true);
+    if (rc) return rc;
+    reverseKey = (const unsigned long long*)(ws + M.off_rev + M.rev.off_key);
+  }
+  hipLaunchKernelGGL(k_finalize_ratio, dim3((numQuery + 255) / 256), dim3(256), 0, st, (const Key2*)(ws + M.off_best), numQuery,
+                     reverseKey, query, target, params_host->queryImageID, params_host->targetImageID, ratio,
+                     absThreshold, outKind, out);
   SSRLCV_LAUNCH_CHECK();
   return SSRLCV_OK;
 }

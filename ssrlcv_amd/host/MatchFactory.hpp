@@ -112,6 +112,46 @@ class MatchFactory {
     return matches;
   }
 
+  // Two nearest neighbours, Lowe's ratio test and the mutual check (ssrlcv_hip_match_ratio_u8x128; no upstream
+  // counterpart), through the validate-and-shrink tail of run<>.  The two-nearest workspace begins with the one-nearest
+  // layout, so the compaction takes the same buffer.
+  template <typename OUT>
+  ptr::value<Unity<OUT>> runRatio(int outKind, ptr::value<Image> query, ptr::value<Unity<Feature<T>>> queryFeatures,
+                                  ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures, float ratio,
+                                  bool mutual) {
+    static_assert(std::is_same<T, SIFT_Descriptor>::value, "MatchFactory is provided for SIFT_Descriptor");
+    MemoryState origin[2] = {queryFeatures->getMemoryState(), targetFeatures->getMemoryState()};
+    if (origin[0] != gpu) queryFeatures->setMemoryState(gpu);
+    if (origin[1] != gpu) targetFeatures->setMemoryState(gpu);
+    uint32_t nq = (uint32_t)queryFeatures->size(), nt = (uint32_t)targetFeatures->size();
+    ssrlcv_ratio_params p;
+    p.queryImageID = (uint32_t)query->id;
+    p.targetImageID = (uint32_t)target->id;
+    p.ratio = ratio;
+    p.absoluteThreshold = absoluteThreshold;
+    p.mutual = mutual ? 1 : 0;
+    size_t wsBytes = ssrlcv_hip_match2_workspace_bytes(nq, nt);
+    unsigned char* ws = workspace(wsBytes);
+    ptr::value<Unity<OUT>> matches(nullptr, (unsigned long)nq, gpu);
+    HipSafeCall(ssrlcv_hip_match_ratio_u8x128(reinterpret_cast<const ssrlcv_sift_feature*>(queryFeatures->device.get()), nq,
+                                              reinterpret_cast<const ssrlcv_sift_feature*>(targetFeatures->device.get()), nt,
+                                              &p, outKind, matches->device.get(), ws, wsBytes, nullptr));
+    HipCheckError();
+    uint32_t left = 0;
+    HipSafeCall(ssrlcv_hip_compact_matches(outKind, matches->device.get(), nq, &left, ws, wsBytes, nullptr));
+    if (left == 0) {
+      logger.info << "No valid matches found";
+    } else {
+      logger.info.printf("%d valid matches found out of %lu original matches", (int)left, (unsigned long)nq);
+      ptr::device<OUT> validated((long)left);
+      HipSafeCall(ssrlcv_hip_memcpy(validated.get(), matches->device.get(), (size_t)left * sizeof(OUT), 2));
+      matches->setData(validated, left, gpu);
+    }
+    if (origin[0] != gpu) queryFeatures->setMemoryState(origin[0]);
+    if (origin[1] != gpu) targetFeatures->setMemoryState(origin[1]);
+    return matches;
+  }
+
  public:
   float absoluteThreshold;
   float relativeThreshold;
@@ -137,6 +177,24 @@ class MatchFactory {
     HipCheckError();
     if (origin != gpu) features->setMemoryState(origin);
     return out;
+  }
+
+  // brute force with the second nearest neighbour: kept when d1 < ratio^2 d2 (ratio 0: no test), d1 < absoluteThreshold and,
+  // with `mutual`, the query is the target's nearest among all queries (include/ssrlcv_hip.h, "two nearest neighbours")
+  ptr::value<Unity<Match>> generateMatchesRatio(ptr::value<Image> query, ptr::value<Unity<Feature<T>>> queryFeatures,
+                                                ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures,
+                                                float ratio, bool mutual) {
+    return runRatio<Match>(SSRLCV_OUT_MATCH, query, queryFeatures, target, targetFeatures, ratio, mutual);
+  }
+  ptr::value<Unity<DMatch>> generateDistanceMatchesRatio(ptr::value<Image> query, ptr::value<Unity<Feature<T>>> queryFeatures,
+                                                         ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures,
+                                                         float ratio, bool mutual) {
+    return runRatio<DMatch>(SSRLCV_OUT_DMATCH, query, queryFeatures, target, targetFeatures, ratio, mutual);
+  }
+  ptr::value<Unity<uint2_pair>> generateMatchesRatioIndexOnly(ptr::value<Image> query, ptr::value<Unity<Feature<T>>> queryFeatures,
+                                                              ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures,
+                                                              float ratio, bool mutual) {
+    return runRatio<uint2_pair>(SSRLCV_OUT_UINT2_PAIR, query, queryFeatures, target, targetFeatures, ratio, mutual);
   }
 
   // brute force (src/MatchFactory.cu:504-547, :754-800)

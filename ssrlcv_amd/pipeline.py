@@ -47,6 +47,7 @@ class Workspace:
         self._plan_bytes = {}
         self.match_ws = None
         self.match_out = None
+        self.match2_ws = None
         self.seed = None
         self.seed_key = None
         self.times = {}
@@ -126,12 +127,22 @@ def exchange_features(local, num_images):
 
 
 def match_pairs(features, cameras, seed_features=None, epsilon=25.0, delta=5.0, rel=0.6, absolute=200.0 * 200.0, mode=1,
-                ws=None, owners=None):
+                ws=None, owners=None, ratio=None, mutual=False):
     """Exhaustive matching (generateMatchesExhaustive; GEO_ORBIT double-constrained for mode 1, brute force for mode 0)
     of the pairs this rank owns (`owners`: rank per pair index, default dist.assign_pairs).  features: list of uint8 CUDA
     tensors (all images).  Every pair is queued -- match, validation / compaction with the count left on the device --
-    and the stream is synchronised once for all the counts.  Returns {pair index: validated uint2_pair bytes}."""
+    and the stream is synchronised once for all the counts.  Returns {pair index: validated uint2_pair bytes}.
+    ratio (Lowe's ratio test against the second nearest target, 0 < ratio <= 1) and / or mutual (cross check): every pair
+    goes through capi.match_ratio instead -- brute force only (mode 0), no seed image."""
     ws = ws or Workspace()
+    if ratio is not None or mutual:
+        if seed_features is not None and ratio is not None:
+            raise ValueError("match_pairs: the ratio test against the second neighbour replaces the seed-image ratio; pass one of them")
+        if seed_features is not None:
+            raise ValueError("match_pairs: the mutual check has no seed-image form")
+        if mode != 0:
+            raise ValueError("match_pairs: ratio / mutual need the brute-force matcher (mode 0), got mode %d" % mode)
+        return _match_pairs_ratio(features, 0.0 if ratio is None else float(ratio), bool(mutual), absolute, ws, owners)
     world, rank = _world()
     num_images = len(features)
     pairs = sd.pair_list(num_images)
@@ -166,6 +177,57 @@ def match_pairs(features, cameras, seed_features=None, epsilon=25.0, delta=5.0, 
         capi.compact_matches_async(capi.OUT_UINT2_PAIR, bufs[p], nq, mws, counts[k:k + 1])
     n = counts.cpu().tolist()  # the one synchronisation
     return {p: bufs[p][: n[k] * 16] for k, p in enumerate(mine)}
+
+
+def _match_pairs_ratio(features, ratio, mutual, absolute, ws, owners):
+    """match_pairs through the two-nearest matcher: per owned pair match_ratio + compaction on the same workspace, all
+    queued, one synchronisation for the counts."""
+    world, rank = _world()
+    pairs = sd.pair_list(len(features))
+    if owners is None:
+        owners = sd.assign_pairs([f.numel() // FEATURE_BYTES for f in features], world)
+    mine = [p for p in range(len(pairs)) if owners[p] == rank]
+    counts = torch.zeros(max(len(mine), 1), dtype=torch.int32, device="cuda")
+    shapes = [(features[pairs[p][0]].numel() // FEATURE_BYTES, features[pairs[p][1]].numel() // FEATURE_BYTES) for p in mine]
+    need = max([capi.LIB.ssrlcv_hip_match2_workspace_bytes(capi.c_u32(nq), capi.c_u32(nt)) for nq, nt in shapes] or [1])
+    if ws.match2_ws is None or ws.match2_ws.numel() < need:
+        ws.match2_ws = capi.dev_bytes(need)
+    bufs = {}
+    for k, p in enumerate(mine):
+        qi, ti = pairs[p]
+        nq, nt = shapes[k]
+        params = capi.make_ratio_params(qi, ti, ratio=ratio, absolute=absolute, mutual=mutual)
+        bufs[p] = capi.dev_bytes(nq * 16)
+        capi.match_ratio(features[qi], nq, features[ti], nt, params, capi.OUT_UINT2_PAIR, workspace=ws.match2_ws, out=bufs[p])
+        capi.compact_matches_async(capi.OUT_UINT2_PAIR, bufs[p], nq, ws.match2_ws, counts[k:k + 1])
+    n = counts.cpu().tolist()  # the one synchronisation
+    return {p: bufs[p][: n[k] * 16] for k, p in enumerate(mine)}
+
+
+def two_view_uncalibrated(feat_q, feat_t, ratio=0.8, samples=2048, threshold=1.0, epsilon=2.0, seed=0, absolute=3.0e9):
+    """Two views without trusted cameras: ratio + mutual brute-force matches -> 7-point RANSAC for F -> the F-constrained
+    matcher (mode 2, band `epsilon` px around the epipolar line) with the F found.  feat_q, feat_t: feature bytes on the
+    device.  The putative matches are validated (compacted) before the RANSAC: a sample that draws a flagged entry yields
+    no candidate, and two of three entries are flagged.  F comes to the host because mode 2 takes it from there.
+    -> dict(F [3, 3] float32, inliers, putative (validated Match bytes), num_putative, matches (validated DMatch bytes),
+    count).  No F (fewer than 7 putative matches, or no candidate with an inlier): inliers 0, no matches."""
+    nq, nt = feat_q.numel() // FEATURE_BYTES, feat_t.numel() // FEATURE_BYTES
+    ws2 = capi.match2_workspace(nq, nt)
+    putative = capi.match_ratio(feat_q, nq, feat_t, nt, capi.make_ratio_params(0, 1, ratio=ratio, absolute=absolute, mutual=True),
+                                capi.OUT_MATCH, workspace=ws2)
+    n_put = capi.compact_matches(capi.OUT_MATCH, putative, nq, ws2)
+    putative = putative[: n_put * 40]
+    r = capi.fmatrix_ransac(putative, n_put, samples, threshold, seed=seed)
+    out = {"F": r["F"], "inliers": r["count"], "putative": putative, "num_putative": n_put,
+           "matches": capi.dev_bytes(0)[:0], "count": 0}
+    if r["count"] == 0:
+        return out
+    params = capi.make_match_params(2, 0, 1, epsilon=epsilon, absolute=absolute, fundamental=r["F"])
+    mws = capi.match_workspace(nq, nt)
+    dm = capi.match(feat_q, nq, feat_t, nt, params, capi.OUT_DMATCH, workspace=mws)
+    out["count"] = capi.compact_matches(capi.OUT_DMATCH, dm, nq, mws)
+    out["matches"] = dm[: out["count"] * 48]
+    return out
 
 
 def exchange_pairs(local, num_pairs, owners=None):
