@@ -44,7 +44,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *   3  round 6: ssrlcv_hip_abi_version itself
  *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added;
  *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals;
- *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128 */
+ *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128;
+ *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8 */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -519,6 +520,51 @@ int ssrlcv_hip_sift_stage(const ssrlcv_sift_plan* plan, void* workspace, int sta
 int ssrlcv_sift_plan_set_stage_event(ssrlcv_sift_plan* plan, void* event);
 int ssrlcv_hip_sift_extract(const ssrlcv_sift_plan* plan, const uint8_t* pixels, void* workspace,
                             ssrlcv_sift_feature* features, uint32_t* numFeatures, ssrlcv_stream_t stream);
+
+/* ---- dense SIFT: SIFT_FeatureFactory::generateFeatures(image, dense = true, maxOrientations, orientationThreshold) -------
+ * Key points on a regular grid of the image itself, all at one scale; no scale space.  The reference's sources are not
+ * at hand here, so its dense branch is not restated line by line: the contract below is this project's own.  It keeps the
+ * reference's signature and the arithmetic of the reference's kernels as the per-kernel entry points further down state
+ * it; the result is DEFINED as this chain of them (pixelWidth = 1 throughout), and the kernels of csrc/dense.hip -- which
+ * are not that chain -- are held to it bit for bit (tests/dense_ref.py, tests/test_gpu_dense.py):
+ *   1 level        L = ssrlcv_hip_u8_to_f32(pixels), normalised in place by ssrlcv_hip_minmax + ssrlcv_hip_normalize.  The
+ *                  descriptor's fixed-point vote scale assumes gradient magnitudes <= 1.4143, which the normalisation gives.
+ *                  A constant image (max == min) is outside the contract: its level is 0 / 0.
+ *   2 gradients    G = ssrlcv_hip_pixel_gradients(L)
+ *   3 grid         wo = ceilf(sigma * 3.0f * orientationContribWidth), wd = ceilf(sigma * descriptorContribWidth) (float
+ *                  arithmetic, as the kernels compute their windows), margin = max(wo, wd).  Key points at the integer
+ *                  locations x = margin + i stride <= w - 2 - margin, y = margin + j stride <= h - 2 - margin: nx x ny of
+ *                  them in row-major order, y outer; each an SSKeyPoint {octave 0, blur 0, sigma, discard 0}.  With this
+ *                  margin every one passes the window tests of compute_thetas and check_keypoints, and every descriptor
+ *                  sample lies inside the image.
+ *   4 orientations ssrlcv_hip_compute_thetas (lambda = orientationContribWidth), ssrlcv_hip_compact_thetas /
+ *                  _compact_addresses, ssrlcv_hip_expand_keypoints: up to maxOrientations oriented key points per grid
+ *                  point, strongest first, in grid order, then slot order.  An all-zero histogram contributes none.
+ *   5 descriptors  ssrlcv_hip_fill_descriptors (lambda = descriptorContribWidth); parent = -1, as the sparse path writes it
+ *   6 count        *numFeatures (device) = the full count; only the first min(count, capacity) records are written, in
+ *                  order, and nothing behind features[capacity) is touched.
+ * Decided on the host before any launch, the parameters before the buffers: SSRLCV_ERR_INVALID_ARG for params NULL, stride 0,
+ * sigma or a width not finite and positive, maxOrientations outside 1..8, nx ny maxOrientations >= 2^31; SSRLCV_ERR_UNSUPPORTED
+ * for wo > 32 or wd > 32; then SSRLCV_ERR_INVALID_ARG for a NULL buffer (features may be NULL with capacity 0);
+ * SSRLCV_ERR_WORKSPACE for a short workspace.  An image too small for one grid point is no error: nx = ny = 0, count 0.
+ * Workspace (ssrlcv_hip_sift_dense_workspace_bytes; 0 for parameters the call refuses): 13 bytes per pixel (L, the polar
+ * table {magnitude, atan2}, the histogram bin) + 4 maxOrientations + 8 bytes per grid point (orientations, counts, offsets)
+ * + the window's weight table and the scan's tile descriptors.  Asynchronous on `stream`; no host synchronisation. */
+typedef struct {
+  uint32_t stride;                  /* grid step in pixels, >= 1 */
+  float sigma;                      /* scale of every key point, > 0 (host mirror default 1.6) */
+  uint32_t maxOrientations;         /* 1..8 */
+  float orientationThreshold;       /* 0.8 */
+  float orientationContribWidth;    /* 1.5 */
+  float descriptorContribWidth;     /* 6.0 */
+} ssrlcv_dense_params;
+/* host only, no device touched; margin / nx / ny may be NULL */
+int ssrlcv_sift_dense_grid(uint32_t w, uint32_t h, const ssrlcv_dense_params* params, uint32_t* margin, uint32_t* nx, uint32_t* ny);
+uint32_t ssrlcv_sift_dense_max_features(uint32_t w, uint32_t h, const ssrlcv_dense_params* params); /* nx ny maxOrientations */
+size_t ssrlcv_hip_sift_dense_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_dense_params* params);
+int ssrlcv_hip_sift_dense_u8(const uint8_t* pixels, uint32_t w, uint32_t h, const ssrlcv_dense_params* params, void* workspace,
+                             size_t workspaceBytes, ssrlcv_sift_feature* features, uint32_t capacity, uint32_t* numFeatures,
+                             ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

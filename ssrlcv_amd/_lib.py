@@ -64,9 +64,11 @@ def load():
                      "ssrlcv_hip_ba_sweep2_workspace_bytes", "ssrlcv_hip_sort_workspace_bytes",
                      "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes",
                      "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_knn_workspace_bytes",
-                     "ssrlcv_hip_neighbor_filter_workspace_bytes", "ssrlcv_hip_match2_workspace_bytes"):
+                     "ssrlcv_hip_neighbor_filter_workspace_bytes", "ssrlcv_hip_match2_workspace_bytes",
+                     "ssrlcv_hip_sift_dense_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
+        _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
     return _lib
 
 
@@ -101,4 +103,5 @@ EXPORTED = [
     "ssrlcv_hip_compact_keypoints", "ssrlcv_hip_fill_extrema", "ssrlcv_hip_flag_noise", "ssrlcv_hip_refine_location",
     "ssrlcv_hip_flag_edges", "ssrlcv_hip_check_keypoints", "ssrlcv_hip_pixel_gradients", "ssrlcv_hip_compute_thetas",
     "ssrlcv_hip_expand_keypoints", "ssrlcv_hip_fill_descriptors",
+    "ssrlcv_sift_dense_grid", "ssrlcv_sift_dense_max_features", "ssrlcv_hip_sift_dense_workspace_bytes", "ssrlcv_hip_sift_dense_u8",
 ]

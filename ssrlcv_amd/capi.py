@@ -521,6 +521,41 @@ def math_eval(fn, a, b=None):
     return out.cpu().numpy()
 
 
+# ------------------------------------------------------------------ dense SIFT
+class DenseParams(ctypes.Structure):
+    _fields_ = [("stride", c_u32), ("sigma", c_f32), ("maxOrientations", c_u32), ("orientationThreshold", c_f32),
+                ("orientationContribWidth", c_f32), ("descriptorContribWidth", c_f32)]
+
+
+def dense_grid(w, h, params):
+    """-> (margin, nx, ny) of the dense grid (host only); raises for parameters the library refuses."""
+    m, nx, ny = c_u32(), c_u32(), c_u32()
+    check(LIB.ssrlcv_sift_dense_grid(c_u32(w), c_u32(h), ctypes.byref(params), ctypes.byref(m), ctypes.byref(nx), ctypes.byref(ny)))
+    return m.value, nx.value, ny.value
+
+
+def dense_workspace(w, h, params):
+    return dev_bytes(int(LIB.ssrlcv_hip_sift_dense_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(params))))
+
+
+def sift_dense(pix_d, stride=1, sigma=1.6, max_orientations=2, orientation_threshold=0.8, orientation_contrib_width=1.5,
+               descriptor_contrib_width=6.0, capacity=None, workspace=None):
+    """Dense SIFT (ssrlcv_hip_sift_dense_u8) of a u8 CUDA tensor (H, W): one key point every `stride` pixels, all at scale
+    `sigma`.  -> (feature bytes [min(count, capacity) * 152], count).  capacity defaults to the grid's maximum."""
+    h, w = pix_d.shape
+    p = DenseParams(stride, sigma, max_orientations, orientation_threshold, orientation_contrib_width, descriptor_contrib_width)
+    dense_grid(w, h, p)
+    cap = int(LIB.ssrlcv_sift_dense_max_features(c_u32(w), c_u32(h), ctypes.byref(p))) if capacity is None else int(capacity)
+    need = int(LIB.ssrlcv_hip_sift_dense_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    ws = workspace if workspace is not None and workspace.numel() >= need else dev_bytes(need)
+    feats = dev_bytes(cap * 152)
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_sift_dense_u8(ptr(pix_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()), ptr(feats),
+                                       c_u32(cap), ptr(count), stream_ptr()))
+    n = int(count.item())
+    return feats[: min(n, cap) * 152], n
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

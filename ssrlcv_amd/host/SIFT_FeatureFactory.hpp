@@ -5,7 +5,9 @@
 // state before returning; the result is a fresh Unity<Feature<SIFT_Descriptor>> in state gpu; zero key points is
 // logger.err + exit(0) (src/SIFT_FeatureFactory.cu:118-121).  The whole sparse branch is one asynchronous C-ABI call
 // (ssrlcv_hip_sift_extract) followed by ONE synchronisation to learn the feature count; upstream synchronises after
-// each of its ~200 launches.  dense = true (never used by the pipeline, src/Pipeline.cu:25,44) is not provided.
+// each of its ~200 launches.  dense = true (never used by the reference pipeline, src/Pipeline.cu:25,44) is the grid of
+// include/ssrlcv_hip.h "dense SIFT" (ssrlcv_hip_sift_dense_u8): one key point every setDenseStride() pixels, all at scale
+// setDenseSigma(), on the image itself; same pixel treatment, same result type, same zero-key-point exit.
 // Colour input goes through convertToBW like upstream (src/SIFT_FeatureFactory.cu:26-29).
 #pragma once
 #include <map>
@@ -48,6 +50,9 @@ class SIFT_FeatureFactory : public FeatureFactory {
   typedef std::tuple<unsigned, unsigned, unsigned, float, float, float> Key;
   std::shared_ptr<std::map<Key, std::shared_ptr<Slot>>> pool;
 
+  unsigned int denseStride = 1;
+  float denseSigma = 1.6f;
+
   void build(Slot& slot, uint2 size, const ssrlcv_sift_params& params) {
     if (slot.plan) ssrlcv_sift_plan_destroy(slot.plan);
     slot.plan = nullptr;
@@ -77,14 +82,14 @@ class SIFT_FeatureFactory : public FeatureFactory {
   // drops the cached plans / workspaces (they are also released with the last copy of the factory)
   void releaseWorkspaces() { pool->clear(); }
 
+  // the dense branch's grid step (pixels, >= 1) and the scale of its key points
+  void setDenseStride(unsigned int stride) { denseStride = stride; }
+  void setDenseSigma(float sigma) { denseSigma = sigma; }
+
   ptr::value<Unity<Feature<SIFT_Descriptor>>> generateFeatures(ptr::value<Image> image, bool dense,
                                                                unsigned int maxOrientations,
                                                                float orientationThreshold = 0.8) {
     logger.info.printf("Generating SIFT features for image %d", image->id);
-    if (dense) {
-      logger.err << "ERROR: dense SIFT is not part of the MI355X hot path (the pipeline always passes dense = false)";
-      std::exit(-1);
-    }
     MemoryState origin = image->pixels->getMemoryState();
     // Upstream moves the pixels to the device with a hard setMemoryState(gpu) and back with setMemoryState(origin)
     // (src/SIFT_FeatureFactory.cu:22-24,166): the second is a device-to-host copy of bytes the host had a moment ago.  The
@@ -98,6 +103,43 @@ class SIFT_FeatureFactory : public FeatureFactory {
     if (image->colorDepth != 1) {
       convertToBW(image->pixels, image->colorDepth);
       image->colorDepth = 1;
+    }
+    if (dense) {
+      ssrlcv_dense_params dp;
+      dp.stride = denseStride;
+      dp.sigma = denseSigma;
+      dp.maxOrientations = maxOrientations;
+      dp.orientationThreshold = orientationThreshold;
+      dp.orientationContribWidth = this->orientationContribWidth;
+      dp.descriptorContribWidth = this->descriptorContribWidth;
+      uint32_t margin = 0, nx = 0, ny = 0;
+      const int rc = ssrlcv_sift_dense_grid(image->size.x, image->size.y, &dp, &margin, &nx, &ny);
+      if (rc == SSRLCV_ERR_UNSUPPORTED) {
+        logger.err << "ERROR: dense SIFT windows above 32 px (sigma x contribution widths) are outside what the MI355X kernels support";
+        std::exit(-1);
+      }
+      HipSafeCall(rc);
+      const uint32_t cap = ssrlcv_sift_dense_max_features(image->size.x, image->size.y, &dp);
+      const size_t wsBytes = ssrlcv_hip_sift_dense_workspace_bytes(image->size.x, image->size.y, &dp);
+      ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+      ptr::device<Feature<SIFT_Descriptor>> staging((long)(cap ? cap : 1));
+      ptr::device<uint32_t> countDev(1);
+      uint32_t count = 0;
+      HipSafeCall(ssrlcv_hip_sift_dense_u8(image->pixels->device.get(), image->size.x, image->size.y, &dp, workspace.get(), wsBytes,
+                                           reinterpret_cast<ssrlcv_sift_feature*>(staging.get()), cap, countDev.get(), nullptr));
+      HipCheckError();
+      HipSafeCall(ssrlcv_hip_memcpy(&count, countDev.get(), sizeof count, 1));
+      if (keepHost) image->pixels->clear(gpu);
+      else if (origin != gpu) image->pixels->setMemoryState(origin);
+      if (count == 0) {
+        logger.err << "ERROR: something went wrong and there are 0 keypoints";
+        std::exit(0);
+      }
+      logger.info.printf("total keypoints found = %d", count);
+      if (count == cap) return ptr::value<Unity<Feature<SIFT_Descriptor>>>(staging, (unsigned long)count, gpu);
+      ptr::device<Feature<SIFT_Descriptor>> exact((long)count);
+      HipSafeCall(ssrlcv_hip_memcpy(exact.get(), staging.get(), (size_t)count * sizeof(Feature<SIFT_Descriptor>), 2));
+      return ptr::value<Unity<Feature<SIFT_Descriptor>>>(exact, (unsigned long)count, gpu);
     }
 
     ssrlcv_sift_params params;

@@ -119,6 +119,24 @@ def extract_features(pixel_tensors, ws=None, plan_budget_bytes=None):
     return out
 
 
+def extract_features_dense(pixel_tensors, stride=1, sigma=1.6, max_orientations=2, orientation_threshold=0.8,
+                           orientation_contrib_width=1.5, descriptor_contrib_width=6.0):
+    """Dense SIFT on the images this rank owns: one key point every `stride` pixels, all at scale `sigma`, on the image itself
+    (capi.sift_dense).  Same shape as extract_features -- {image index: u8 CUDA tensor (H, W)} -> {index: feature bytes} --
+    so the result goes into match_pairs / two_view_uncalibrated unchanged.  One workspace serves images of one size."""
+    out, workspaces = {}, {}
+    for v, pix in pixel_tensors.items():
+        h, w = pix.shape
+        p = capi.DenseParams(stride, sigma, max_orientations, orientation_threshold, orientation_contrib_width, descriptor_contrib_width)
+        capi.dense_grid(w, h, p)
+        if (w, h) not in workspaces:
+            workspaces[(w, h)] = capi.dense_workspace(w, h, p)
+        feats, n = capi.sift_dense(pix, stride, sigma, max_orientations, orientation_threshold, orientation_contrib_width,
+                                   descriptor_contrib_width, workspace=workspaces[(w, h)])
+        out[v] = feats[: n * FEATURE_BYTES].clone()
+    return out
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:
