@@ -11,16 +11,16 @@
 //   k_dense_weights  the (2 wo + 1)^2 Gaussian weights of the orientation window: they depend on the integer offset alone
 //   k_dense_orient   a block owns a tile of grid points and stages the tile's pixels + halo wo (magnitude, bin) in LDS
 //                    once; one lane per grid point walks its window in raster order -- the single fmaf chain per bin of
-//                    the reference kernel -- into a histogram column in LDS (no 36-way select chain); the reference's
-//                    peak insertion loop; survivors are written slot-compacted with their count
+//                    the reference kernel -- into a histogram column in LDS (no 36-way select chain), picks its peaks
+//                    (svf::pick_orientations) and writes the survivors slot-compacted with their count
 //   (scan)           exclusive scan of the counts (scan_lookback.h): where each grid point's features start
 //   k_dense_desc     a block owns the same kind of tile with halo wd (magnitude, angle) in LDS; one wave per oriented key
-//                    point gathers its rotated window from LDS; the votes, integer bin sums and the two norms are the
-//                    expressions of k_x_descriptors; records leave through LDS as 16-byte stores
+//                    point gathers its rotated window from LDS; records leave through LDS as 16-byte stores
 //
-// What the reformulation keeps because it is part of the result (keypoints.hip, k_x_thetas): a histogram bin is one
-// fmaf(mag, wgt, hist[bin]) chain over the window, y outer, x inner; floorf(angle / rad10) can come out as 36, and such
-// a sample votes nowhere.
+// Every result-defining expression -- gradient stencil, polar form, bin, window widths, weights, peak picking, votes, norms,
+// bytes -- is the one function of sift_sampling.h that k_x_gradients / k_x_thetas / k_x_descriptors call as well.  What the
+// reformulation keeps besides (keypoints.hip, k_x_thetas): a histogram bin is one fmaf(mag, wgt, hist[bin]) chain over the
+// window, y outer, x inner; a sample whose bin comes out as 36 votes nowhere.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -28,12 +28,13 @@
 #include "ssrlcv_hip.h"
 #include "device_math.h"
 #include "scan_lookback.h"
+#include "sift_sampling.h"
 
 namespace {
 
 constexpr uint32_t kMaxHalo = 32;          // wo, wd <= 32: the largest tile of one grid point is 65 x 65 pixels
 constexpr size_t kLdsBudget = 60 * 1024;   // dynamic LDS of one block (64 KB with the static arrays)
-constexpr uint32_t kNoBin = 36;            // floorf(angle / rad10) == 36: votes nowhere
+constexpr uint32_t kNoBin = 36;            // svf::orientation_bin == 36: votes nowhere
 
 struct DenseGeom {
   uint32_t w, h, stride, margin, nx, ny, wo, wd;
@@ -47,14 +48,14 @@ struct TileShape {
 
 inline bool finite_pos(float v) { return v > 0.0f && v <= FLT_MAX; }
 
-// the window widths as the kernels of the chain compute them (k_x_thetas, k_x_descriptors; pixelWidth = 1)
+// the window widths are the chain's (sift_sampling.h; pixelWidth = 1)
 int dense_geom(uint32_t w, uint32_t h, const ssrlcv_dense_params* p, DenseGeom* g) {
   if (!p) return SSRLCV_ERR_INVALID_ARG;
   if (p->stride == 0 || !finite_pos(p->sigma) || !finite_pos(p->orientationContribWidth) || !finite_pos(p->descriptorContribWidth) ||
       p->maxOrientations < 1 || p->maxOrientations > 8)
     return SSRLCV_ERR_INVALID_ARG;
-  const float wo = ceilf(p->sigma * 3.0f * p->orientationContribWidth / 1.0f);
-  const float wd = ceilf(p->sigma * p->descriptorContribWidth / 1.0f);
+  const float wo = svf::orientation_window(p->sigma, p->orientationContribWidth, 1.0f);
+  const float wd = svf::descriptor_window(p->sigma, p->descriptorContribWidth, 1.0f);
   if (!(wo <= (float)kMaxHalo) || !(wd <= (float)kMaxHalo)) return SSRLCV_ERR_UNSUPPORTED;
   g->w = w;
   g->h = h;
@@ -138,25 +139,9 @@ __global__ __launch_bounds__(256) void k_dense_polar(const uint8_t* __restrict__
   const int x = (int)(id % W), y = (int)(id / W);
   const float mn = (float)mm[0], mx = (float)mm[1];
   const sv::Divisor range = sv::make_divisor(mx - mn);
-  int xc0 = x + 1, xc1 = x - 1, yc0 = y + 1, yc1 = y - 1;
-  if (xc1 == -1) { xc0 += 1; xc1 += 1; }
-  else if (xc0 == W) { xc0 -= 1; xc1 -= 1; }
-  if (yc1 == -1) { yc0 += 1; yc1 += 1; }
-  else if (yc0 == H) { yc0 -= 1; yc1 -= 1; }
-  const float lx0 = sv::div_by((float)px[(size_t)y * W + xc0] - mn, range), lx1 = sv::div_by((float)px[(size_t)y * W + xc1] - mn, range);
-  const float ly0 = sv::div_by((float)px[(size_t)yc0 * W + x] - mn, range), ly1 = sv::div_by((float)px[(size_t)yc1 * W + x] - mn, range);
   level[id] = sv::div_by((float)px[id] - mn, range);
-  float2 g;
-  g.x = lx0 - lx1;
-  g.y = ly0 - ly1;
-  const float pi = 3.1415927f;
-  const float rad10 = pi / 18.0f;
-  const float at = sv_atan2f(g.y, g.x);
-  const float angle = fmodf(at + (2.0f * pi), 2.0f * pi);
-  const int bin = (int)floorf(angle / rad10);
-  float2 r;
-  r.x = sqrtf((g.x * g.x) + (g.y * g.y));
-  r.y = at;
+  const float2 r = svf::polar_of(svf::gradient_taps(x, y, W, H, [&](size_t a) { return sv::div_by((float)px[a] - mn, range); }));
+  const int bin = svf::orientation_bin(r.y);
   polar[id] = r;
   bins[id] = (uint8_t)((unsigned)bin < kNoBin ? bin : (int)kNoBin);
 }
@@ -165,9 +150,7 @@ __global__ __launch_bounds__(256) void k_dense_weights(float* __restrict__ wtab,
   const int side = 2 * wo + 1;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= side * side) return;
-  const float tx = (float)(i % side - wo), ty = (float)(i / side - wo);
-  const float weight = 2.0f * lambda * lambda * sigma * sigma;
-  wtab[i] = sv_expf(-((tx * tx) + (ty * ty)) / weight);
+  wtab[i] = svf::orientation_weight((float)(i % side - wo), (float)(i / side - wo), svf::orientation_weight_denom(sigma, lambda));
 }
 
 struct TileArgs {
@@ -219,37 +202,9 @@ __global__ __launch_bounds__(256) void k_dense_orient(TileArgs a, const float2* 
       if (bin < kNoBin) hist[bin * nPts] = __builtin_fmaf(mrow[dx], wrow[dx], hist[bin * nPts]);
     }
   }
-#define SV_HIST(b) hist[(b) * nPts]
-  const float pi = 3.1415927f;
-  const float rad10 = pi / 18.0f;
   const int regNumOrient = (int)(maxO > 8u ? 8u : maxO);
-  float maxHist = 0.0f;
-  for (int i = 0; i < 36; ++i)
-    if (SV_HIST(i) > maxHist) maxHist = SV_HIST(i);
-  maxHist *= orientationThreshold;
   float bx[8], by[8];
-  for (int i = 0; i < 8; ++i) { bx[i] = 0.0f; by[i] = 0.0f; }
-  for (int b = 0; b < 36; ++b) {
-    const float hb = SV_HIST(b), hp = SV_HIST(b == 0 ? 35 : b - 1), hn = SV_HIST(b == 35 ? 0 : b + 1);
-    if (hb < maxHist || hb < hp || hb < hn || hb < bx[regNumOrient - 1]) continue;
-    float tx = hb;
-    float ty = (hp - hn) / (hp - (2.0f * hb) + hn);
-    ty *= (pi / 36.0f);
-    ty += (b * rad10);
-    ty = fmodf(ty + (2.0f * pi), 2.0f * pi);
-    for (int i = 0; i < regNumOrient; ++i) {
-      if (tx > bx[i]) {
-        for (int ii = i; ii < regNumOrient; ++ii) {
-          const float sx = bx[ii], sy = by[ii];
-          bx[ii] = tx;
-          by[ii] = ty;
-          tx = sx;
-          ty = sy;
-        }
-      }
-    }
-  }
-#undef SV_HIST
+  svf::pick_orientations([&](int b) { return hist[b * nPts]; }, regNumOrient, orientationThreshold, bx, by);
   // what compact_thetas / compact_addresses leave of this key point's slots, in slot order
   const size_t g = (size_t)gy * a.nx + gx;
   uint32_t kept = 0;
@@ -287,7 +242,6 @@ __global__ __launch_bounds__(256) void k_dense_desc(TileArgs a, const float2* __
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned* bins = s_bins[wave];
-  const float pi = 3.1415927f;
   const float pixelWidth = 1.0f;
   for (int pt = wave; pt < nPts; pt += 4) {
     const uint32_t gx = tileX * a.px + (uint32_t)pt % a.px, gy = tileY * a.py + (uint32_t)pt / a.px;
@@ -302,81 +256,48 @@ __global__ __launch_bounds__(256) void k_dense_desc(TileArgs a, const float2* __
       bins[lane] = 0u;
       bins[lane + 64] = 0u;
       wave_sync();
-      // ---- k_x_descriptors' body; the gradient's magnitude and direction come from the tile
-      const float windowWidth = ceilf(sigma * lambda / pixelWidth);
-      const float binWidth = windowWidth / 2.0f, rad45 = pi / 4.0f;
-      const float c = sv_cosf(-theta), s = sv_sinf(-theta);
-      int boundExp;
-      (void)frexpf(1.4143f * ((windowWidth + 2.0f) * (windowWidth + 2.0f)), &boundExp);
-      const float voteScale = ldexpf(1.0f, 31 - boundExp);
-      const int iw = (int)windowWidth, side = 2 * iw + 1;
+      // ---- k_x_descriptors' body from sift_sampling.h; the gradient's magnitude and direction come from the tile
+      const svf::DescriptorFrame fr = svf::descriptor_frame(sigma, theta, lambda, pixelWidth);
+      const int iw = (int)fr.windowWidth, side = 2 * iw + 1;
       for (int sIdx = lane; sIdx < side * side; sIdx += 64) {
-        const float y = (float)(sIdx / side - iw), x = (float)(sIdx % side - iw);
-        const float cx = (x * c) + (y * s), cy = (-x * s) + (y * c);
-        if (fabsf(cx) > windowWidth || fabsf(cy) > windowWidth) continue;
+        float cx, cy;
+        if (!svf::rotate_sample(fr, (float)(sIdx % side - iw), (float)(sIdx / side - iw), cx, cy)) continue;
         const int sx = (int)llroundf(cx + kx) - x0, sy = (int)llroundf(cy + ky) - y0;
         float2 p = make_float2(0.0f, 0.0f);
         if (sx >= 0 && sx < tw && sy >= 0 && sy < th) p = s_pol[sy * tw + sx];  // (always: |cx|, |cy| <= wd)
-        const float mag = p.x * sv_expf(-((cx * cx) + (cy * cy)) / (2.0f * windowWidth * windowWidth));
-        const float ang = fmodf(p.y - theta + (2.0f * pi), 2.0f * pi);
+        const float mag = p.x * svf::sample_weight(fr, cx, cy);
+        const float ang = svf::relative_angle(p.y, theta);
         // k_x_descriptors walks the sixteen cells and, inside a cell it votes in, the eight directions -- a wave then runs
         // every cell and direction ANY of its lanes votes in.  Here a lane first collects the cells (at most nine) and
-        // directions (at most two) that pass the same tests, then walks its own; the votes are the same expressions, and
+        // directions (at most two) that pass the same tests, then walks its own; the votes are the same functions, and
         // their integer sums do not depend on the order.
         unsigned cells = 0u, dirs = 0u;
+        float hx, hy, angle;
 #pragma unroll
-        for (int nx = 0; nx < 4; ++nx) {
-#pragma unroll
-          for (int ny = 0; ny < 4; ++ny) {
-            float hx = ((float)nx * 0.5f - 0.75f) * windowWidth, hy = ((float)ny * 0.5f - 0.75f) * windowWidth;
-            const float rx = (hx * c) + (hy * s), ry = (-hx * s) + (hy * c);
-            hx = fabsf(rx - cx);
-            hy = fabsf(ry - cy);
-            if (hx <= binWidth && hy <= binWidth) cells |= 1u << (nx * 4 + ny);
-          }
-        }
+        for (int cell = 0; cell < 16; ++cell)
+          if (svf::cell_offsets(fr, cell >> 2, cell & 3, cx, cy, hx, hy)) cells |= 1u << cell;
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-          if (fabsf(ang - ((float)k * rad45)) < rad45) dirs |= 1u << k;
+          if (svf::direction_offset(ang, k, angle)) dirs |= 1u << k;
         while (cells != 0u) {
           const int cell = __ffs(cells) - 1;
           cells &= cells - 1u;
-          const int nx = cell >> 2, ny = cell & 3;
-          float hx = ((float)nx * 0.5f - 0.75f) * windowWidth, hy = ((float)ny * 0.5f - 0.75f) * windowWidth;
-          const float rx = (hx * c) + (hy * s), ry = (-hx * s) + (hy * c);
-          hx = fabsf(rx - cx);
-          hy = fabsf(ry - cy);
-          hx = hx / binWidth;
-          hy = hy / binWidth;
+          (void)svf::cell_offsets(fr, cell >> 2, cell & 3, cx, cy, hx, hy);
           for (unsigned left = dirs; left != 0u; left &= left - 1u) {
             const int k = __ffs(left) - 1;
-            float angle = fabsf(ang - ((float)k * rad45));
-            angle /= rad45;
-            const float temp = (1.0f - hx) * (1.0f - hy) * (1.0f - angle) * mag;
-            const float q = temp * voteScale, f = floorf(q);
-            atomicAdd(&bins[cell * 8 + k], (unsigned)f + ((q - f) >= 0.5f ? 1u : 0u));
+            (void)svf::direction_offset(ang, k, angle);
+            atomicAdd(&bins[cell * 8 + k], svf::vote_fixed(hx, hy, angle, mag, fr.voteScale));
           }
         }
       }
       wave_sync();
-      // bins in [nx][ny][k] order: lane l holds elements l and l + 64; both norms as balanced trees (pairs 64 apart first)
-      float v0 = (float)bins[lane], v1 = (float)bins[lane + 64];
-      float sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
-      v0 /= sq;
-      v1 /= sq;
-      v0 = v0 > 0.2f ? 0.2f : v0;
-      v1 = v1 > 0.2f ? 0.2f : v1;
-      sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
-      // the record through LDS: values[(ny * 4 + nx) * 8 + k] = bin[nx][ny][k]
+      float v0 = (float)bins[lane], v1 = (float)bins[lane + 64];  // elements lane and lane + 64 of the bins in [nx][ny][k] order
+      const float sq = svf::normalise_pair(v0, v1);
       char* out = reinterpret_cast<char*>(features + fi);
       const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 8u);  // records are 8-byte aligned, 152 bytes long
       uint8_t* rec = reinterpret_cast<uint8_t*>(s_rec[wave]) + shift;
-      {
-        const int e0 = lane, e1 = lane + 64;
-        const int nx0 = e0 >> 5, ny0 = (e0 >> 3) & 3, k0 = e0 & 7, nx1 = e1 >> 5, ny1 = (e1 >> 3) & 3, k1 = e1 & 7;
-        rec[24 + (ny0 * 4 + nx0) * 8 + k0] = (uint8_t)roundf(255.0f * v0 / sq);
-        rec[24 + (ny1 * 4 + nx1) * 8 + k1] = (uint8_t)roundf(255.0f * v1 / sq);
-      }
+      rec[24 + svf::descriptor_slot(lane)] = svf::descriptor_byte(v0, sq);
+      rec[24 + svf::descriptor_slot(lane + 64)] = svf::descriptor_byte(v1, sq);
       if (lane == 0) {
         uint32_t* r32 = reinterpret_cast<uint32_t*>(rec);
         r32[0] = 0xffffffffu;  // parent = -1, as the sparse path writes it

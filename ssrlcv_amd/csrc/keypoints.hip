@@ -24,6 +24,7 @@
 #include "scan_lookback.h"
 #include "device_math.h"
 #include "sift_plan.h"
+#include "sift_sampling.h"
 #include "ssrlcv_hip.h"
 
 using svp::OctaveState;
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(256) void k_polar(PolarJobs jobs) {
         const float dn = y == 0 ? v[i + 1] : (y == H - 1 ? v[i > 0 ? i - 1 : 0] : v[i]);
         g2.y = up - dn;
         float2 r;
-        r.x = sqrtf((g2.x * g2.x) + (g2.y * g2.y));
+        r.x = sqrtf((g2.x * g2.x) + (g2.y * g2.y));  // restates svf::gradient_taps (the taps above) and svf::polar_of
         r.y = sv_atan2f(g2.y, g2.x);
 #if SSRLCV_NT_STORES
         __builtin_nontemporal_store(f32x2p{r.x, r.y}, reinterpret_cast<f32x2p*>(o + (size_t)i * W));  // 2.2 GB per image, gathered later
@@ -460,7 +461,7 @@ __device__ __forceinline__ float2 polar_px(const float2* __restrict__ pl, int W,
 }
 // llroundf of a window coordinate v > -1: v_cvt_rpi_i32_f32 is floor(v + 0.5) evaluated exactly (tools/f64_rate.hip:
 // equal to round-half-up for every float in (-1, 2^31)), which is llroundf except at v == -0.5 (half away from zero)
-__device__ __forceinline__ int round_coord(float v) {
+__device__ __forceinline__ int round_coord(float v) {  // restates the llroundf of the export kernels' sample coordinates
   int r;
   asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(v));
   return v == -0.5f ? -1 : r;
@@ -659,14 +660,14 @@ __global__ __launch_bounds__(64) void k_thetas(const OctaveState* states, const 
   kp.sigma = 1.0f;
   if (have) kp = set.kps[octave][gi];
   const float kx = kp.loc.x, ky = kp.loc.y;
-  const float windowWidth = ceilf(kp.sigma * 3.0f * lambda / pixelWidth);
+  const float windowWidth = ceilf(kp.sigma * 3.0f * lambda / pixelWidth);  // restates svf::orientation_window
   const float minx = kx - windowWidth, miny = ky - windowWidth, maxx = kx + windowWidth, maxy = ky + windowWidth;
   // (key points live on DoG levels 1..3: refinement discards what would move to level 0 or 4)
   const bool inside = have && useg >= 1 && useg <= 3 &&
                       !(minx < 0.0f || miny < 0.0f || maxx >= (unsigned)(L.w - 1) || maxy >= (unsigned)(L.h - 1));
 #pragma unroll
   for (int i = 0; i < 36 * PER_BLOCK / 64; ++i) (&s_hist[0][0])[i * 64 + t] = 0.0f;
-  const float weight = 2.0f * lambda * lambda * kp.sigma * kp.sigma;
+  const float weight = 2.0f * lambda * lambda * kp.sigma * kp.sigma;  // restates svf::orientation_weight_denom
   const float rweight = 1.0f / weight;
   const int W = L.w;
   const size_t levelStride = svp::polar_level_stride(L.w, L.h);
@@ -796,7 +797,7 @@ __global__ __launch_bounds__(64) void k_thetas(const OctaveState* states, const 
       // (2) The histogram updates, strictly in raster order, branch-free within a lane: a sample that does not count
       // (past the row's end, or bin 36 from an angle one ulp below 2 pi, which the reference's array has no slot for)
       // adds fmaf(0, w, h) = h to bin 0.
-      auto weigh = [&](float ang, float xi, float& wgt, int& bin) {
+      auto weigh = [&](float ang, float xi, float& wgt, int& bin) {  // restates svf::orientation_bin, svf::orientation_weight
         const float angle = fmod_2pi_above(ang + (2.0f * pi), 2.0f * pi);
         bin = (int)floorf(sv::exact_div3(angle, rad10, inv10));
         const float tx = xi - kx;
@@ -859,7 +860,7 @@ __global__ __launch_bounds__(64) void k_thetas(const OctaveState* states, const 
   float outTheta[MAXO];
 #pragma unroll
   for (int i = 0; i < MAXO; ++i) outTheta[i] = -FLT_MAX;
-  if (inside && sub == 0) {
+  if (inside && sub == 0) {  // restates svf::pick_orientations with the slot count a compile-time constant
     float maxHist = 0.0f;
     for (int i = 0; i < 36; ++i) {
       const float h = s_hist[i][col];
@@ -960,12 +961,9 @@ __global__ __launch_bounds__(256) void k_desc_consts(const RangeTable* tab, Octa
     const float theta = kps[i].theta;
     d.c = sv_cosf(-theta);
     d.s = sv_sinf(-theta);
-    d.windowWidth = ceilf(kps[i].sigma * lambda / pixelWidth);
+    d.windowWidth = svf::descriptor_window(kps[i].sigma, lambda, pixelWidth);
     d.invExpDen = 1.0f / (2.0f * d.windowWidth * d.windowWidth);
-    // sqrt(2) * (windowWidth + 2)^2 * 2^k < 2^31
-    int boundExp;
-    (void)frexpf(1.4143f * ((d.windowWidth + 2.0f) * (d.windowWidth + 2.0f)), &boundExp);
-    d.voteScale = ldexpf(1.0f, 31 - boundExp);
+    d.voteScale = svf::vote_scale(d.windowWidth);
     d.invBin = 1.0f / (d.windowWidth / 2.0f);
     const unsigned wi = (unsigned)(int)d.windowWidth;
     d.magic = wi > 1u ? 0xFFFFFFFFu / wi + 1u : 0u;  // ceil(2^32 / w) (2^32 / w when w is a power of two); w = 1 is special-cased
@@ -979,7 +977,7 @@ __global__ __launch_bounds__(256) void k_desc_consts(const RangeTable* tab, Octa
 // oracle spells that out.  Plain truncation, which the first version used, biases every bin low by half a unit per
 // vote -- hundreds of units on bins that hold 1e5..1e6 of them, enough to move descriptor bytes and to lose 2 of the
 // reference's 13 534 golden matches.
-__device__ __forceinline__ unsigned vote_u32(float v) {
+__device__ __forceinline__ unsigned vote_u32(float v) {  // restates the rounding of svf::vote_fixed
   int r;
   asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(v));
   return (unsigned)r;
@@ -1071,7 +1069,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
     const int Wi = (int)windowWidth;
     const unsigned centreIdx = (unsigned)(Wi * (Wi + 1));
     const unsigned magic = dc.magic;  // ceil(2^32 / w)
-    auto sample = [&](unsigned idx, float& cx, float& cy, bool& ok) {
+    auto sample = [&](unsigned idx, float& cx, float& cy, bool& ok) {  // restates svf::rotate_sample for a whole orbit
       const unsigned yq = Wi == 1 ? idx : __umulhi(idx, magic);  // idx / w, exact for idx < 2^16
       const unsigned xq = idx - yq * (unsigned)Wi + 1u;
       const bool centre = idx >= centreIdx;
@@ -1093,7 +1091,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
     // t45 is within 1e-4 of an integer; its own error is below 1e-6): they take no part in the fast path and are
     // replayed literally afterwards.  The two weights are the reference's expressions: |ang - (float)k * rad45|, an
     // IEEE division by rad45, 1 - quotient.  A missing vote adds 0 to a valid word (a neighbouring cell's bin or the
-    // padding in front of / behind the histogram) instead of branching.
+    // padding in front of / behind the histogram) instead of branching.  (Restates svf::relative_angle, svf::direction_offset.)
     auto split = [&](float2 pg, bool live, float& w0, float& w1, unsigned*& pa, float& ang, bool& odd) {
       ang = fmod_2pi_above(pg.y - theta + (2.0f * pi), 2.0f * pi);
       const float t45 = ang * inv45;
@@ -1126,7 +1124,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
       sample(base + 64 + (unsigned)lane, ncx, ncy, nok);
       if (nok) gather4();
       // gaussian weight (shared by the orbit), the fixed-point scale folded in (a power of two: exact)
-      const float r2n = -((cx * cx) + (cy * cy));
+      const float r2n = -((cx * cx) + (cy * cy));  // restates svf::sample_weight
       const float g = sv::expf_nonpos(sv::exact_div3(r2n, expDen, invExpDen)) * voteScale;
       float a0, a1, b0, b1, c0, c1, d0, d1, angA, angB, angC, angD;
       bool oddA, oddB, oddC, oddD;
@@ -1151,7 +1149,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
         if (nx == 0 || ny == 0) continue;
         const int cellB = (3 - ny) * 4 + nx, cellC = 15 - cell, cellD = ny * 4 + (3 - nx);
         const float tx = fabsf(rc[cell].x - cx), ty = fabsf(rc[cell].y - cy);
-        if (fmaxf(tx, ty) <= bwl) {
+        if (fmaxf(tx, ty) <= bwl) {  // restates svf::cell_offsets; the votes below restate svf::vote_fixed (vote_u32)
           const float wxy = (1.0f - sv::exact_div3(tx, binWidth, invBin)) * (1.0f - sv::exact_div3(ty, binWidth, invBin));
           atomicAdd(pa + cell * 8 * kDescCopies, vote_u32((wxy * a0) * magA));
           atomicAdd(pa + cell * 8 * kDescCopies + kDescCopies, vote_u32((wxy * a1) * magA));
@@ -1163,7 +1161,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
           atomicAdd(pd + cellD * 8 * kDescCopies + kDescCopies, vote_u32((wxy * d1) * magD));
         }
       }
-      // the literal replay (:509-524) of the samples whose direction sits on a bin boundary: about one in 10^4
+      // the literal replay (:509-524; restates svf::cell_offsets, direction_offset, vote_fixed) of the samples whose direction sits on a bin boundary: about one in 10^4
       if (__ballot(oddA || oddB || oddC || oddD) != 0ull) {
 #pragma unroll 1
         for (int m = 0; m < 4; ++m) {
@@ -1207,20 +1205,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8), amdg
       t1 += bins[(lane + 64) * kDescCopies + cpy];
     }
     float v0 = (float)t0, v1 = (float)t1;
-    float sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
-    v0 = v0 / sq;
-    v1 = v1 / sq;
-    if (v0 > 0.2f) v0 = 0.2f;
-    if (v1 > 0.2f) v1 = 0.2f;
-    sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
-    // bins are [nx][ny][k]; the descriptor byte order is (ny*4 + nx)*8 + k (:542)
-    {
-      int b0 = lane, b1 = lane + 64;
-      int o0 = (((b0 >> 3) & 3) * 4 + (b0 >> 5)) * 8 + (b0 & 7);
-      int o1 = (((b1 >> 3) & 3) * 4 + (b1 >> 5)) * 8 + (b1 & 7);
-      s_bytes[wave][o0] = (uint8_t)roundf(255.0f * v0 / sq);
-      s_bytes[wave][o1] = (uint8_t)roundf(255.0f * v1 / sq);
-    }
+    const float sq = svf::normalise_pair(v0, v1);
+    s_bytes[wave][svf::descriptor_slot(lane)] = svf::descriptor_byte(v0, sq);
+    s_bytes[wave][svf::descriptor_slot(lane + 64)] = svf::descriptor_byte(v1, sq);
     __builtin_amdgcn_wave_barrier();
     const uint32_t fi = featBase[octave] + (uint32_t)gi;
     if (fi < maxFeatures) {
@@ -2198,7 +2185,9 @@ int ssrlcv_hip_sift_stage(const ssrlcv_sift_plan* plan, void* workspace, int sta
 // Octave::blurs[b]->pixels, Unity<SSKeyPoint> lists, extremaBlurIndices on the host) and swaps kernels one at a time.
 // These are the plain forms -- they read materialised DoG images and whole gradient arrays like the kernels they replace,
 // not the plan's fused workspace -- with the plan path's arithmetic: same device functions (refine_one,
-// edge_response_above, sv_math.h), the descriptor sums in the order-independent form of DESIGN.md section 2.
+// edge_response_above, sv_math.h), the descriptor sums in the order-independent form of DESIGN.md section 2.  The
+// orientation and descriptor arithmetic of k_x_gradients, k_x_thetas and k_x_descriptors is sift_sampling.h: every
+// result-defining sampling expression is written once, there, and dense.hip calls the same functions.
 }  // extern "C"
 namespace {
 // findExtrema (src/FeatureFactory.cu:847-882): non-strict 3x3x3 maximum / minimum; border pixels are not written
@@ -2263,21 +2252,10 @@ __global__ __launch_bounds__(256) void k_x_refine(uint32_t n, int W, int H, floa
   refine_one(kp, W, H, numBlurs, sigmaMin, mult, src);
   kps[i] = kp;
 }
-// calculatePixelGradients (src/Image.cu:1583-1598): a border pixel takes the stencil of its inner neighbour
-__device__ __forceinline__ float2 x_gradient(const float* __restrict__ px, int W, int H, int x, int y) {
-  int xc0 = x + 1, xc1 = x - 1, yc0 = y + 1, yc1 = y - 1;
-  if (xc1 == -1) { xc0 += 1; xc1 += 1; }
-  else if (xc0 == W) { xc0 -= 1; xc1 -= 1; }
-  if (yc1 == -1) { yc0 += 1; yc1 += 1; }
-  else if (yc0 == H) { yc0 -= 1; yc1 -= 1; }
-  float2 g;
-  g.x = px[(size_t)y * W + xc0] - px[(size_t)y * W + xc1];
-  g.y = px[(size_t)yc0 * W + x] - px[(size_t)yc1 * W + x];
-  return g;
-}
+// calculatePixelGradients (src/Image.cu:1583-1598)
 __global__ __launch_bounds__(256) void k_x_gradients(int W, int H, const float* __restrict__ px, float2* __restrict__ grad) {
   const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (id < (size_t)W * H) grad[id] = x_gradient(px, W, H, (int)(id % W), (int)(id / W));
+  if (id < (size_t)W * H) grad[id] = svf::gradient_taps((int)(id % W), (int)(id / W), W, H, [&](size_t a) { return px[a]; });
 }
 // computeThetas (src/FeatureFactory.cu:1004-1112): one thread per key point, the reference's own shape (its sequential
 // fmaf chain per bin is part of the result).  thetas / thetaNumbers: n x maxOrientations, -FLT_MAX / -1 = none.
@@ -2287,58 +2265,29 @@ __global__ __launch_bounds__(64) void k_x_thetas(uint32_t n, uint32_t start, int
                                                  float* __restrict__ thetas) {
   const uint32_t gi = blockIdx.x * 64 + threadIdx.x;
   if (gi >= n) return;
-  const float pi = 3.1415927f;
   const ssrlcv_sskeypoint kp = kps[start + gi];
   const int regNumOrient = (int)(maxO > 8u ? 8u : maxO);
   for (int i = 0; i < regNumOrient; ++i) { thetas[(size_t)gi * maxO + i] = -FLT_MAX; thetaNumbers[(size_t)gi * maxO + i] = -1; }
   const float kx = kp.loc.x, ky = kp.loc.y;
-  const float windowWidth = ceilf(kp.sigma * 3.0f * lambda / pixelWidth);
+  const float windowWidth = svf::orientation_window(kp.sigma, lambda, pixelWidth);
   const float minx = kx - windowWidth, miny = ky - windowWidth, maxx = kx + windowWidth, maxy = ky + windowWidth;
   if (minx < 0.0f || miny < 0.0f || maxx >= (unsigned)(W - 1) || maxy >= (unsigned)(H - 1)) return;
   float hist[36];
   for (int i = 0; i < 36; ++i) hist[i] = 0.0f;
-  const float weight = 2.0f * lambda * lambda * kp.sigma * kp.sigma;
-  const float rad10 = pi / 18.0f;
+  const float weight = svf::orientation_weight_denom(kp.sigma, lambda);
   for (float y = miny; y <= maxy; y += 1.0f) {
     for (float x = minx; x <= maxx; x += 1.0f) {
-      const float2 g = grad[(size_t)llroundf(y) * W + (size_t)llroundf(x)];
-      const float tx = x - kx, ty = y - ky;
-      const float angle = fmodf(sv_atan2f(g.y, g.x) + (2.0f * pi), 2.0f * pi);
-      const int bin = (int)floorf(angle / rad10);
-      const float mag = sqrtf((g.x * g.x) + (g.y * g.y));
-      const float wgt = sv_expf(-((tx * tx) + (ty * ty)) / weight);
+      const float2 p = svf::polar_of(grad[(size_t)llroundf(y) * W + (size_t)llroundf(x)]);
+      const int bin = svf::orientation_bin(p.y);
+      const float wgt = svf::orientation_weight(x - kx, y - ky, weight);
       // dynamic index into the per-thread histogram: a select chain keeps it in registers
 #pragma unroll
       for (int b = 0; b < 36; ++b)
-        if (b == bin) hist[b] = __builtin_fmaf(mag, wgt, hist[b]);
+        if (b == bin) hist[b] = __builtin_fmaf(p.x, wgt, hist[b]);
     }
   }
-  float maxHist = 0.0f;
-  for (int i = 0; i < 36; ++i)
-    if (hist[i] > maxHist) maxHist = hist[i];
-  maxHist *= orientationThreshold;
   float bx[8], by[8];
-  for (int i = 0; i < 8; ++i) { bx[i] = 0.0f; by[i] = 0.0f; }
-  for (int b = 0; b < 36; ++b) {
-    const float hb = hist[b], hp = hist[b == 0 ? 35 : b - 1], hn = hist[b == 35 ? 0 : b + 1];
-    if (hb < maxHist || hb < hp || hb < hn || hb < bx[regNumOrient - 1]) continue;
-    float tx = hb;
-    float ty = (hp - hn) / (hp - (2.0f * hb) + hn);
-    ty *= (pi / 36.0f);
-    ty += (b * rad10);
-    ty = fmodf(ty + (2.0f * pi), 2.0f * pi);
-    for (int i = 0; i < regNumOrient; ++i) {
-      if (tx > bx[i]) {
-        for (int ii = i; ii < regNumOrient; ++ii) {
-          const float sx = bx[ii], sy = by[ii];
-          bx[ii] = tx;
-          by[ii] = ty;
-          tx = sx;
-          ty = sy;
-        }
-      }
-    }
-  }
+  svf::pick_orientations([&](int b) { return hist[b]; }, regNumOrient, orientationThreshold, bx, by);
   for (int i = 0; i < regNumOrient; ++i) {
     if (bx[i] != 0.0f) {
       thetas[(size_t)gi * maxO + i] = by[i];
@@ -2354,9 +2303,8 @@ __global__ __launch_bounds__(256) void k_x_expand(uint32_t n, const ssrlcv_sskey
   kp.theta = thetas[i];
   out[i] = kp;
 }
-// fillDescriptors (src/SIFT_FeatureFactory.cu:475-549): one wave per key point; the votes are the reference's expressions,
-// the 128 bins are summed as integers (vote x 2^k rounded half up: order independent), the norms as
-// balanced trees -- the definition k_descriptors and the oracle share.
+// fillDescriptors (src/SIFT_FeatureFactory.cu:475-549): one wave per key point; votes (integers: order independent), norms
+// and bytes are sift_sampling.h's -- the definition k_descriptors and the oracle share.
 __global__ __launch_bounds__(64) void k_x_descriptors(uint32_t n, uint32_t start, int W, int H, float pixelWidth, float lambda,
                                                       const ssrlcv_sskeypoint* __restrict__ kps, const float2* __restrict__ grad,
                                                       ssrlcv_sift_feature* __restrict__ features) {
@@ -2364,68 +2312,39 @@ __global__ __launch_bounds__(64) void k_x_descriptors(uint32_t n, uint32_t start
   const uint32_t gi = blockIdx.x;
   if (gi >= n) return;
   const int lane = threadIdx.x;
-  const float pi = 3.1415927f;
   const ssrlcv_sskeypoint kp = kps[start + gi];
   s_bins[lane] = 0u;
   s_bins[lane + 64] = 0u;
   __syncthreads();
   const float kx = kp.loc.x, ky = kp.loc.y, theta = kp.theta;
-  const float windowWidth = ceilf(kp.sigma * lambda / pixelWidth);
-  const float binWidth = windowWidth / 2.0f, rad45 = pi / 4.0f;
-  const float c = sv_cosf(-theta), s = sv_sinf(-theta);
-  int boundExp;
-  (void)frexpf(1.4143f * ((windowWidth + 2.0f) * (windowWidth + 2.0f)), &boundExp);
-  const float voteScale = ldexpf(1.0f, 31 - boundExp);
-  const int iw = (int)windowWidth, side = 2 * iw + 1;
+  const svf::DescriptorFrame fr = svf::descriptor_frame(kp.sigma, theta, lambda, pixelWidth);
+  const int iw = (int)fr.windowWidth, side = 2 * iw + 1;
   for (int sIdx = lane; sIdx < side * side; sIdx += 64) {
-    const float y = (float)(sIdx / side - iw), x = (float)(sIdx % side - iw);
-    const float cx = (x * c) + (y * s), cy = (-x * s) + (y * c);
-    if (fabsf(cx) > windowWidth || fabsf(cy) > windowWidth) continue;
+    float cx, cy;
+    if (!svf::rotate_sample(fr, (float)(sIdx % side - iw), (float)(sIdx / side - iw), cx, cy)) continue;
     const long long flat = llroundf(cy + ky) * (long long)W + llroundf(cx + kx);
     float2 g;
     g.x = g.y = 0.0f;
     if (flat >= 0 && flat < (long long)W * H) g = grad[flat];
-    const float mag = sqrtf((g.x * g.x) + (g.y * g.y)) * sv_expf(-((cx * cx) + (cy * cy)) / (2.0f * windowWidth * windowWidth));
-    const float ang = fmodf(sv_atan2f(g.y, g.x) - theta + (2.0f * pi), 2.0f * pi);
+    const float2 p = svf::polar_of(g);
+    const float mag = p.x * svf::sample_weight(fr, cx, cy);
+    const float ang = svf::relative_angle(p.y, theta);
     for (int nx = 0; nx < 4; ++nx) {
       for (int ny = 0; ny < 4; ++ny) {
-        float hx = ((float)nx * 0.5f - 0.75f) * windowWidth, hy = ((float)ny * 0.5f - 0.75f) * windowWidth;
-        const float rx = (hx * c) + (hy * s), ry = (-hx * s) + (hy * c);
-        hx = fabsf(rx - cx);
-        hy = fabsf(ry - cy);
-        if (hx <= binWidth && hy <= binWidth) {
-          hx = hx / binWidth;
-          hy = hy / binWidth;
-          for (int k = 0; k < 8; ++k) {
-            float angle = fabsf(ang - ((float)k * rad45));
-            if (angle < rad45) {
-              angle /= rad45;
-              const float temp = (1.0f - hx) * (1.0f - hy) * (1.0f - angle) * mag;
-              const float q = temp * voteScale, f = floorf(q);
-              atomicAdd(&s_bins[(nx * 4 + ny) * 8 + k], (unsigned)f + ((q - f) >= 0.5f ? 1u : 0u));
-            }
-          }
-        }
+        float hx, hy, angle;
+        if (!svf::cell_offsets(fr, nx, ny, cx, cy, hx, hy)) continue;
+        for (int k = 0; k < 8; ++k)
+          if (svf::direction_offset(ang, k, angle)) atomicAdd(&s_bins[(nx * 4 + ny) * 8 + k], svf::vote_fixed(hx, hy, angle, mag, fr.voteScale));
       }
     }
   }
   __syncthreads();
-  // bins in [nx][ny][k] order: lane l holds elements l and l + 64; both norms as balanced trees (pairs 64 apart first)
+  // lane l holds elements l and l + 64 of the bins in [nx][ny][k] order
   float v0 = (float)s_bins[lane], v1 = (float)s_bins[lane + 64];
-  float sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
-  v0 /= sq;
-  v1 /= sq;
-  v0 = v0 > 0.2f ? 0.2f : v0;
-  v1 = v1 > 0.2f ? 0.2f : v1;
-  sq = sqrtf(sv::wave_sum((v0 * v0) + (v1 * v1)));
+  const float sq = svf::normalise_pair(v0, v1);
   ssrlcv_sift_feature* ft = features + gi;
-  // values[(ny * 4 + nx) * 8 + k] = bin[nx][ny][k]
-  {
-    const int e0 = lane, e1 = lane + 64;
-    const int nx0 = e0 >> 5, ny0 = (e0 >> 3) & 3, k0 = e0 & 7, nx1 = e1 >> 5, ny1 = (e1 >> 3) & 3, k1 = e1 & 7;
-    ft->values[(ny0 * 4 + nx0) * 8 + k0] = (uint8_t)roundf(255.0f * v0 / sq);
-    ft->values[(ny1 * 4 + nx1) * 8 + k1] = (uint8_t)roundf(255.0f * v1 / sq);
-  }
+  ft->values[svf::descriptor_slot(lane)] = svf::descriptor_byte(v0, sq);
+  ft->values[svf::descriptor_slot(lane + 64)] = svf::descriptor_byte(v1, sq);
   if (lane == 0) {
     ft->theta = kp.theta;
     ft->sigma = kp.sigma;

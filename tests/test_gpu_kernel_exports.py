@@ -192,6 +192,56 @@ def test_orientation_and_descriptor_exports(ctx, oracle_lib, o):
         assert np.array_equal(gf[f].view(np.uint32), want[f].view(np.uint32)), f
 
 
+@pytest.fixture(scope="module")
+def oracle_features_by_slots(ctx):
+    _, s, _ = ctx
+    return {m: s.features(max_orientations=m) for m in (1, 2, 4, 8)}
+
+
+@pytest.mark.parametrize("maxo", [1, 4, 8])
+def test_export_chain_at_other_orientation_counts(ctx, oracle_features_by_slots, maxo):
+    """The same chain (pixel_gradients, compute_thetas, the two compactions, expand_keypoints, fill_descriptors) over every
+    octave and blur segment in list order == OracleSift.features(max_orientations = 1, 4, 8): count, loc / sigma / theta as
+    bit patterns, all 128 descriptor bytes.  The dense path shares csrc/sift_sampling.h's peak picker and vote with these
+    exports, so the oracle is what holds the third and later peaks and the votes on them."""
+    capi, s, stages = ctx
+    by_m = oracle_features_by_slots
+    assert len(by_m[1]) < len(by_m[2]) < len(by_m[4]) < len(by_m[8])   # later peaks exist: the cases cannot degenerate
+    feats = []
+    for o in range(4):
+        w, h, pw, sig = s.octave_info(o)
+        l5, idx5 = _octave_slice(stages[5], o)
+        kp_d = _dev(l5)
+        for b in range(5):
+            cnt = int((idx5[b + 1] if b < 4 else idx5[5]) - idx5[b])
+            if cnt <= 0:
+                continue
+            px = _dev(s.level(2, o, b))
+            grad = capi.dev_bytes(8 * w * h)
+            capi.check(capi.LIB.ssrlcv_hip_pixel_gradients(u32(w), u32(h), capi.ptr(px), capi.ptr(grad), capi.stream_ptr()))
+            thetas = torch.zeros(cnt * maxo, dtype=torch.float32, device="cuda")
+            nums = torch.zeros(cnt * maxo, dtype=torch.int32, device="cuda")
+            capi.check(capi.LIB.ssrlcv_hip_compute_thetas(u32(cnt), u32(int(idx5[b])), u32(w), u32(h), f32(pw), f32(1.5), capi.ptr(kp_d),
+                                                          capi.ptr(grad), capi.ptr(nums), u32(maxo), f32(0.8), capi.ptr(thetas), capi.stream_ptr()))
+            nt = _compact(capi, capi.LIB.ssrlcv_hip_compact_thetas, thetas, cnt * maxo)
+            nn = _compact(capi, capi.LIB.ssrlcv_hip_compact_addresses, nums, cnt * maxo)
+            assert nt == nn
+            if nn == 0:
+                continue
+            out = capi.dev_bytes(32 * nn)
+            capi.check(capi.LIB.ssrlcv_hip_expand_keypoints(u32(nn), capi.ptr(kp_d), capi.ptr(out), capi.ptr(nums), capi.ptr(thetas),
+                                                            capi.stream_ptr()))
+            ft = torch.zeros(152 * nn, dtype=torch.uint8, device="cuda")
+            capi.check(capi.LIB.ssrlcv_hip_fill_descriptors(u32(nn), u32(0), u32(w), u32(h), capi.ptr(ft), f32(pw), f32(6.0), capi.ptr(out),
+                                                            capi.ptr(grad), capi.stream_ptr()))
+            feats.append(capi.to_host(ft, H.FEATURE, nn))
+    got, want = np.concatenate(feats), by_m[maxo]
+    assert len(got) == len(want), (len(got), len(want))
+    for f in ("loc", "sigma", "theta"):
+        assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), f
+    assert np.array_equal(got["values"], want["values"])
+
+
 def test_in_place_compaction_over_many_tiles(ctx):
     capi, _, _ = ctx
     rng = np.random.default_rng(9)
