@@ -526,7 +526,8 @@ int ssrlcv_hip_sift_extract(const ssrlcv_sift_plan* plan, const uint8_t* pixels,
  * at hand here, so its dense branch is not restated line by line: the contract below is this project's own.  It keeps the
  * reference's signature and the arithmetic of the reference's kernels as the per-kernel entry points further down state
  * it; the result is DEFINED as this chain of them (pixelWidth = 1 throughout), and the kernels of csrc/dense.hip -- which
- * are not that chain -- are held to it bit for bit (tests/dense_ref.py, tests/test_gpu_dense.py):
+ * are not that chain -- are held to it bit for bit (tests/dense_ref.py, tests/test_gpu_dense.py), and both to the CPU
+ * oracle's restatement of the items below (oracle_sift_dense, oracle/oracle_sift.c):
  *   1 level        L = ssrlcv_hip_u8_to_f32(pixels), normalised in place by ssrlcv_hip_minmax + ssrlcv_hip_normalize.  The
  *                  descriptor's fixed-point vote scale assumes gradient magnitudes <= 1.4143, which the normalisation gives.
  *                  A constant image (max == min) is outside the contract: its level is 0 / 0.
@@ -540,7 +541,10 @@ int ssrlcv_hip_sift_extract(const ssrlcv_sift_plan* plan, const uint8_t* pixels,
  *   4 orientations ssrlcv_hip_compute_thetas (lambda = orientationContribWidth), ssrlcv_hip_compact_thetas /
  *                  _compact_addresses, ssrlcv_hip_expand_keypoints: up to maxOrientations oriented key points per grid
  *                  point, strongest first, in grid order, then slot order.  An all-zero histogram contributes none.
- *   5 descriptors  ssrlcv_hip_fill_descriptors (lambda = descriptorContribWidth); parent = -1, as the sparse path writes it
+ *   5 descriptors  ssrlcv_hip_fill_descriptors (lambda = descriptorContribWidth); parent = -1, as the sparse path writes it.
+ *                  A descriptor whose window holds no gradient is outside the contract like the constant image: its votes
+ *                  are all zero and its bytes 0 / 0, unspecified.  (Reachable with wo > wd beside a flat region: the
+ *                  orientation window finds a gradient the descriptor window does not reach.)
  *   6 count        *numFeatures (device) = the full count; only the first min(count, capacity) records are written, in
  *                  order, and nothing behind features[capacity) is touched.
  * Decided on the host before any launch, the parameters before the buffers: SSRLCV_ERR_INVALID_ARG for params NULL, stride 0,

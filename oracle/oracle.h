@@ -187,6 +187,24 @@ int oracle_gauss_kernel(float sigma, float pixelWidth, float* weights);
 void oracle_set_descriptor_sum_mode(int mode);
 void oracle_fill_descriptor(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda,
                             const o_sskeypoint* kp, o_feature* feat);
+/* computeThetas(SSKeyPoint) (src/FeatureFactory.cu:1004-1112) for one key point on a caller's level: maxOrientations (<= 8)
+ * entries of thetas / valid, strongest first; an empty slot is {-FLT_MAX, 0} */
+void oracle_compute_thetas(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda, const o_sskeypoint* kp,
+                           uint32_t maxOrientations, float orientationThreshold, float* thetas, int* valid);
+/* dense SIFT as include/ssrlcv_hip.h ("dense SIFT", items 1-6) defines it, restated from the pieces above and from nothing
+ * of ssrlcv_amd/csrc.  _grid: item 3 (-1 for stride 0 or a window outside 1..32; outputs nullable).  oracle_sift_dense
+ * returns the FULL count and writes the first min(count, capacity) records (out may be NULL with capacity 0); levelOut
+ * (nullable) receives the normalised level.  -1 for parameters outside the contract.  The result does not depend on the
+ * number of OpenMP threads.  _stats: of the last oracle_sift_dense call, over the records it wrote: the largest integer
+ * vote bin (the fixed-point scale keeps it below 2^31 for gradient magnitudes <= 1.4143) and the number of descriptors
+ * without any vote, whose bytes are undefined (0 / 0). */
+int oracle_sift_dense_grid(uint32_t w, uint32_t h, uint32_t stride, float sigma, float orientationContribWidth,
+                           float descriptorContribWidth, uint32_t* margin, uint32_t* nx, uint32_t* ny, uint32_t* wo,
+                           uint32_t* wd);
+long long oracle_sift_dense(const uint8_t* pixels, uint32_t w, uint32_t h, uint32_t stride, float sigma,
+                            uint32_t maxOrientations, float orientationThreshold, float orientationContribWidth,
+                            float descriptorContribWidth, o_feature* out, uint32_t capacity, float* levelOut);
+void oracle_sift_dense_stats(uint32_t* maxVoteBin, uint32_t* emptyDescriptors);
 /* full keypoint + descriptor stage on an existing scale space; *out malloc'd (oracle_free) */
 int oracle_sift_features(oracle_sift* s, uint32_t maxOrientations, float orientationThreshold,
                          float orientationContribWidth, float descriptorContribWidth, o_feature** out);

@@ -653,8 +653,9 @@ static float tree_norm(const float* v /* [128], [nx][ny][k] order */) {
   return p[0];
 }
 
-void oracle_fill_descriptor(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda,
-                            const o_sskeypoint* kp, o_feature* feat) {
+/* *maxBin (nullable): the largest of the 128 integer bins of sum mode 0 (0 in sum mode 1) */
+static void fill_descriptor(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda,
+                            const o_sskeypoint* kp, o_feature* feat, uint32_t* maxBin) {
   const float pi = O_PI_F;
   float bins[4][4][8];
   uint32_t ibins[4][4][8];
@@ -709,6 +710,12 @@ void oracle_fill_descriptor(const float* level, uint32_t W, uint32_t H, float pi
       for (int yy = 0; yy < 4; ++yy)
         for (int z = 0; z < 8; ++z) bins[xx][yy][z] = (float)ibins[xx][yy][z];
   }
+  if (maxBin) {
+    uint32_t top = 0;
+    for (int i = 0; i < 128; ++i)
+      if ((&ibins[0][0][0])[i] > top) top = (&ibins[0][0][0])[i];
+    *maxBin = top;
+  }
   float norm = 0.0f;
   if (exact) norm = tree_norm(&bins[0][0][0]);
   else
@@ -738,6 +745,132 @@ void oracle_fill_descriptor(const float* level, uint32_t W, uint32_t H, float pi
   feat->loc.x = kp->loc.x * pixelWidth;
   feat->loc.y = kp->loc.y * pixelWidth;
   feat->parent = -1; /* Feature() default, never written by the kernel */
+}
+void oracle_fill_descriptor(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda,
+                            const o_sskeypoint* kp, o_feature* feat) {
+  fill_descriptor(level, W, H, pixelWidth, lambda, kp, feat, NULL);
+}
+
+/* computeThetas for ONE key point on a caller's level (kernel-level parity tests of the orientation exports): thetas and
+ * valid hold maxOrientations (<= 8) entries, strongest first; an empty slot is {-FLT_MAX, 0} */
+void oracle_compute_thetas(const float* level, uint32_t W, uint32_t H, float pixelWidth, float lambda, const o_sskeypoint* kp,
+                           uint32_t maxOrientations, float orientationThreshold, float* thetas, int* valid) {
+  octave_t oc;
+  memset(&oc, 0, sizeof oc);
+  oc.w = W;
+  oc.h = H;
+  oc.pixelWidth = pixelWidth;
+  if (maxOrientations > 8) maxOrientations = 8;
+  compute_thetas(&oc, level, kp, lambda, maxOrientations, orientationThreshold, thetas, valid);
+}
+
+/* ---- dense SIFT: items 1-6 of the contract in include/ssrlcv_hip.h ("dense SIFT"), from the pieces above ------------- */
+/* item 3.  The widths are the float expressions compute_thetas and fill_descriptor evaluate at pixelWidth = 1. */
+int oracle_sift_dense_grid(uint32_t w, uint32_t h, uint32_t stride, float sigma, float orientationContribWidth,
+                           float descriptorContribWidth, uint32_t* margin, uint32_t* nx, uint32_t* ny, uint32_t* wo,
+                           uint32_t* wd) {
+  const float pixelWidth = 1.0f;
+  if (stride == 0) return -1;
+  float fo = ceilf(sigma * 3.0f * orientationContribWidth / pixelWidth);
+  float fd = ceilf(sigma * descriptorContribWidth / pixelWidth);
+  if (!(fo >= 1.0f && fo <= 32.0f) || !(fd >= 1.0f && fd <= 32.0f)) return -1;
+  long long m = (long long)(fo > fd ? fo : fd);
+  long long spanX = (long long)w - 2 - 2 * m, spanY = (long long)h - 2 - 2 * m;
+  long long cx = spanX < 0 ? 0 : spanX / (long long)stride + 1, cy = spanY < 0 ? 0 : spanY / (long long)stride + 1;
+  if (cx == 0 || cy == 0) cx = cy = 0;
+  if (margin) *margin = (uint32_t)m;
+  if (nx) *nx = (uint32_t)cx;
+  if (ny) *ny = (uint32_t)cy;
+  if (wo) *wo = (uint32_t)fo;
+  if (wd) *wd = (uint32_t)fd;
+  return 0;
+}
+
+static uint32_t g_dense_max_bin = 0, g_dense_empty = 0;
+/* of the last oracle_sift_dense call, over the records it wrote: the largest integer vote bin, and how many descriptors
+ * had no vote at all (their bytes are (uint8_t)roundf(0 / 0): undefined) */
+void oracle_sift_dense_stats(uint32_t* maxVoteBin, uint32_t* emptyDescriptors) {
+  if (maxVoteBin) *maxVoteBin = g_dense_max_bin;
+  if (emptyDescriptors) *emptyDescriptors = g_dense_empty;
+}
+
+/* Returns the FULL count (item 6) and writes the first min(count, capacity) records, grid order then slot order; -1 for
+ * parameters outside the contract.  levelOut (nullable, w h floats) receives the normalised level L.  Two passes over the
+ * grid rows, count then fill, each row independent: the result does not depend on the number of threads. */
+long long oracle_sift_dense(const uint8_t* pixels, uint32_t w, uint32_t h, uint32_t stride, float sigma,
+                            uint32_t maxOrientations, float orientationThreshold, float orientationContribWidth,
+                            float descriptorContribWidth, o_feature* out, uint32_t capacity, float* levelOut) {
+  uint32_t margin, nx, ny;
+  g_dense_max_bin = g_dense_empty = 0;
+  if (maxOrientations < 1 || maxOrientations > 8) return -1;
+  if (oracle_sift_dense_grid(w, h, stride, sigma, orientationContribWidth, descriptorContribWidth, &margin, &nx, &ny, NULL, NULL))
+    return -1;
+  /* item 1: u8 -> float (src/Image.cu:1554-1559), min / max, normalise */
+  size_t px = (size_t)w * h;
+  float* level = (float*)malloc(sizeof(float) * (px ? px : 1));
+  for (size_t i = 0; i < px; ++i) level[i] = (float)pixels[i];
+  float mn, mx;
+  minmax(level, px, &mn, &mx);
+  normalize_level(level, px, mn, mx);
+  if (levelOut) memcpy(levelOut, level, sizeof(float) * px);
+  octave_t oc; /* item 2 happens inside: compute_thetas and fill_descriptor take the gradient where they sample it */
+  memset(&oc, 0, sizeof oc);
+  oc.w = w;
+  oc.h = h;
+  oc.pixelWidth = 1.0f;
+  size_t n = (size_t)nx * ny;
+  float* thetas = (float*)malloc(sizeof(float) * (n ? n : 1) * maxOrientations);
+  long long* first = (long long*)malloc(sizeof(long long) * (n + 1));
+  /* item 4, counting pass */
+#pragma omp parallel for schedule(dynamic, 1)
+  for (long long j = 0; j < (long long)ny; ++j) {
+    for (uint32_t i = 0; i < nx; ++i) {
+      size_t g = (size_t)j * nx + i;
+      o_sskeypoint kp;
+      memset(&kp, 0, sizeof kp);
+      kp.loc.x = (float)((unsigned long long)margin + (unsigned long long)i * stride);
+      kp.loc.y = (float)((unsigned long long)margin + (unsigned long long)j * stride);
+      kp.sigma = sigma;
+      kp.theta = -1.0f;
+      float th[8];
+      int valid[8];
+      compute_thetas(&oc, level, &kp, orientationContribWidth, maxOrientations, orientationThreshold, th, valid);
+      long long kept = 0;
+      for (uint32_t s = 0; s < maxOrientations; ++s)
+        if (valid[s]) thetas[g * maxOrientations + kept++] = th[s];
+      first[g + 1] = kept;
+    }
+  }
+  first[0] = 0;
+  for (size_t g = 0; g < n; ++g) first[g + 1] += first[g];
+  long long total = first[n];
+  /* item 5, filling pass */
+  uint32_t maxBin = 0, empty = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(max : maxBin) reduction(+ : empty)
+  for (long long j = 0; j < (long long)ny; ++j) {
+    for (uint32_t i = 0; i < nx; ++i) {
+      size_t g = (size_t)j * nx + i;
+      for (long long f = first[g]; f < first[g + 1] && f < (long long)capacity; ++f) {
+        o_sskeypoint kp;
+        memset(&kp, 0, sizeof kp);
+        kp.loc.x = (float)((unsigned long long)margin + (unsigned long long)i * stride);
+        kp.loc.y = (float)((unsigned long long)margin + (unsigned long long)j * stride);
+        kp.sigma = sigma;
+        kp.theta = thetas[g * maxOrientations + (size_t)(f - first[g])];
+        uint32_t top = 0;
+        memset(&out[f], 0, sizeof(o_feature));
+        fill_descriptor(level, w, h, 1.0f, descriptorContribWidth, &kp, &out[f], &top);
+        if (top > maxBin) maxBin = top;
+        if (top == 0) ++empty;
+      }
+    }
+  }
+  g_dense_max_bin = maxBin;
+  g_dense_empty = empty;
+  free(first);
+  free(thetas);
+  free(level);
+  return total;
 }
 
 /* Stages: 0 raw extrema, 1 +removeNoise(0.8*thr), 2 +refine, 3 +removeNoise(thr), 4 +removeEdges,

@@ -93,13 +93,19 @@ DenseLayout dense_layout(const DenseGeom& g, uint32_t maxO) {
   return L;
 }
 
-inline uint32_t tile_extent(uint32_t points, uint32_t stride, uint32_t halo) { return (points - 1) * stride + 2 * halo + 1; }
+// pixels a tile of `points` grid points spans.  In 64 bits: (points - 1) stride passes 2^32 for the strides near it, and a
+// wrapped extent would size a tile smaller than one window.  Capped at 2^20, far above what fits LDS, so that the products
+// of two extents below stay exact as well.
+inline size_t tile_extent(uint32_t points, uint32_t stride, uint32_t halo) {
+  const uint64_t e = (uint64_t)(points - 1) * stride + 2 * halo + 1;
+  return (size_t)(e < (1ull << 20) ? e : (1ull << 20));
+}
 inline size_t orient_lds(TileShape t, uint32_t stride, uint32_t wo) {
   const size_t tw = tile_extent(t.px, stride, wo), th = tile_extent(t.py, stride, wo), side = 2 * wo + 1;
   return tw * th * 4 + side * side * 4 + (size_t)36 * t.px * t.py * 4 + (tw * th + 3) / 4 * 4;
 }
 inline size_t desc_lds(TileShape t, uint32_t stride, uint32_t wd) {
-  return (size_t)tile_extent(t.px, stride, wd) * tile_extent(t.py, stride, wd) * 8;
+  return tile_extent(t.px, stride, wd) * tile_extent(t.py, stride, wd) * 8;
 }
 // the largest tile of grid points whose LDS fits; one point always does (halo <= 32).  A stride too long for two points
 // to share a tile leaves a block with one window: that is then all the sharing there is.

@@ -1,6 +1,8 @@
 """The dense-SIFT reference: items 1-5 of the contract in include/ssrlcv_hip.h ("dense SIFT") taken literally, as a chain of
 the per-kernel exports over a numpy-built key-point list.  The exports are independent kernels, pinned to the CPU oracle by
-tests/test_gpu_kernel_exports.py; nothing here calls ssrlcv_hip_sift_dense_u8."""
+tests/test_gpu_kernel_exports.py on the sparse path's key points; nothing here calls ssrlcv_hip_sift_dense_u8.  The chain
+shares sift_sampling.h with dense.hip, so tests/test_gpu_dense.py holds the chain itself, level L included, to the CPU
+oracle's dense SIFT (tests/dense_cases.py) at every case it runs: dense parameters leave the range the sparse path reaches."""
 import ctypes
 
 import numpy as np

@@ -53,7 +53,10 @@ def test_header_and_loader_name_the_entry_points():
 
 @pytest.mark.parametrize("w,h,stride,sigma,maxo", [
     (64, 48, 1, 1.6, 2), (160, 144, 1, 1.6, 1), (160, 144, 1, 1.6, 4), (97, 83, 3, 1.6, 2), (97, 83, 7, 1.6, 2),
-    (128, 96, 1, 1.0, 2), (128, 96, 1, 2.3, 2), (128, 96, 4, 1.6, 2), (21, 21, 1, 1.6, 2), (22, 22, 1, 1.6, 2), (22, 21, 1, 1.6, 2)])
+    (128, 96, 1, 1.0, 2), (128, 96, 1, 2.3, 2), (128, 96, 4, 1.6, 2), (21, 21, 1, 1.6, 2), (22, 22, 1, 1.6, 2), (22, 21, 1, 1.6, 2),
+    # one column, one row, one pixel short of either; strides from a few points per tile to the largest the ABI can name
+    (22, 40, 1, 1.6, 2), (40, 22, 1, 1.6, 2), (21, 40, 1, 1.6, 2), (40, 21, 1, 1.6, 2), (128, 96, 40, 1.6, 2), (128, 96, 1000, 1.6, 2),
+    (128, 96, 0x11111112, 1.6, 8), (128, 96, 0xFFFFFFFF, 1.6, 8), (100, 92, 1, 5.3, 2), (66, 66, 1, 5.3, 2), (66, 65, 0xFFFFFFFF, 5.3, 2)])
 def test_grid_follows_the_formulas(lib, w, h, stride, sigma, maxo):
     p = params(stride=stride, sigma=sigma, maxo=maxo)
     m, nx, ny, _, _ = D.grid(w, h, stride, sigma)
@@ -121,6 +124,21 @@ def test_windows_above_32_are_unsupported(lib, kw):
 def test_the_largest_supported_windows(lib):
     # sigma 5.3: wd = ceil(31.8) = 32, wo = ceil(23.85) = 24
     assert query(lib, 200, 200, params(sigma=5.3)) == (OK, 32, 200 - 2 - 64 + 1, 200 - 2 - 64 + 1)
+    # the margin is the larger of the two, whichever it is: wo = ceil(2 * 3 * 5.3) = 32, wd = ceil(2 * 3) = 6
+    assert D.grid(100, 92, sigma=2.0, ori_width=5.3, desc_width=3.0) == (32, 35, 27, 32, 6)
+    assert query(lib, 100, 92, params(sigma=2.0, ow=5.3, dw=3.0)) == (OK, 32, 35, 27)
+    assert query(lib, 100, 92, params(sigma=5.3, ow=2.0)) == (OK, 32, 35, 27)  # both 32
+    assert query(lib, 97, 83, params(ow=3.0, dw=4.0)) == (OK, 15, 66, 52)      # wo 15, wd 7
+
+
+def test_workspace_of_the_longest_strides(lib):
+    """one grid point however long the stride: the size queries do not wrap"""
+    small = lib.ssrlcv_hip_sift_dense_workspace_bytes(u32(128), u32(96), ctypes.byref(params(stride=1000)))
+    for stride in (0x11111112, 0x80000000, 0xFFFFFFFF):
+        p = params(stride=stride, maxo=8)
+        assert query(lib, 128, 96, p) == (OK, 10, 1, 1)
+        assert lib.ssrlcv_sift_dense_max_features(u32(128), u32(96), ctypes.byref(p)) == 8
+        assert 0 < lib.ssrlcv_hip_sift_dense_workspace_bytes(u32(128), u32(96), ctypes.byref(p)) <= small + 256
 
 
 def test_short_workspace(lib):
