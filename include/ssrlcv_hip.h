@@ -45,7 +45,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *   4  fundamental-matrix RANSAC: fmatrix_ransac (+ its workspace query), fmatrix_score, pose_from_fmatrix added;
  *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals;
  *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128;
- *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8 */
+ *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8;
+ *      dense stereo: stereo_workspace_bytes, stereo_sad_u8, stereo_matches_workspace_bytes, stereo_matches, stereo_points */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -569,6 +570,64 @@ size_t ssrlcv_hip_sift_dense_workspace_bytes(uint32_t w, uint32_t h, const ssrlc
 int ssrlcv_hip_sift_dense_u8(const uint8_t* pixels, uint32_t w, uint32_t h, const ssrlcv_dense_params* params, void* workspace,
                              size_t workspaceBytes, ssrlcv_sift_feature* features, uint32_t capacity, uint32_t* numFeatures,
                              ssrlcv_stream_t stream);
+
+/* ---- dense stereo: the reference's Window_NxN descriptors + MatchFactory's disparity matchers + PointCloudFactory's
+ * stereo_disparity, as SAD block matching of a rectified pair.  The reference's sources are not at hand here, so -- as for
+ * dense SIFT -- the contract below is this project's own; the kernels of csrc/stereo.hip are held to a numpy restatement of
+ * it bit for bit (tests/stereo_ref.py, tests/test_gpu_stereo.py).  Upstream materialises one window descriptor per pixel (up
+ * to 961 bytes) and runs its generic matcher over them; here the kernel works from the two images directly and no cost
+ * volume or per-pixel window exists in memory.
+ *   inputs      left, right: uint8, w x h, row-major with pitch w, rectified: the partner of left pixel (x, y) at disparity d
+ *               is right pixel (x - d, y).
+ *   1 cost      C(x, y, d) = sum over |i| <= r, |j| <= r of |L(x + i, y + j) - R(x + i - d, y + j)|: an integer, at most
+ *               961 * 255.  Defined only where both windows lie inside their image: r <= x <= w - 1 - r, r <= y <= h - 1 - r,
+ *               r <= x - d <= w - 1 - r; elsewhere d is not a candidate of (x, y).  No border is replicated anywhere.
+ *   2 winner    candidates are d = minDisparity + k, k = 0 .. numDisparities - 1.  d*(x, y) = the candidate of least cost C*,
+ *               the smallest d among equal costs.  A pixel with no candidate is invalid.
+ *   3 limit     C* > maxCost: the pixel is invalid (UINT32_MAX: no test).
+ *   4 LR check  lrTolerance >= 0: the right winner dR(x', y) = the d of least C(x' + d, y, d) over the d for which that cost is
+ *               defined, the smallest d among equal costs.  (x, y) stays valid only if |dR(x - d*, y) - d*| <= lrTolerance
+ *               (dR(x - d*, y) always has at least the candidate d*).  lrTolerance < 0: no check.
+ *   5 sub-pixel subpixel = 1: if d* - 1 and d* + 1 are both candidates of (x, y) and den = C(d* - 1) - 2 C* + C(d* + 1) != 0,
+ *               off = (float)(C(d* - 1) - C(d* + 1)) / (float)(2 den): two integers below 2^24 converted exactly, one IEEE
+ *               float division; otherwise off = 0.  disparity = (float)d* + off, one float addition.  |off| <= 0.5 since C*
+ *               is the minimum.  Items 2 and 4 always use the integer winners.
+ *   6 outputs   disparity[w h] float, an invalid pixel holds the bit pattern 0x7FC00000; cost[w h] uint32 (may be NULL) holds
+ *               C*, UINT32_MAX for an invalid pixel.  Every pixel of both maps is written, the border included.
+ * Decided on the host before any launch, the parameters before the buffers: SSRLCV_ERR_INVALID_ARG for params NULL, radius 0,
+ * numDisparities 0, minDisparity outside -32768 .. 32767, subpixel > 1, w h >= 2^31; SSRLCV_ERR_UNSUPPORTED for radius > 15 or
+ * numDisparities > 256; then SSRLCV_ERR_INVALID_ARG for a NULL buffer (cost may be NULL); SSRLCV_ERR_WORKSPACE for a short
+ * workspace.  An image smaller than one window is no error: every pixel is invalid.
+ * Workspace (ssrlcv_hip_stereo_workspace_bytes; host only; 0 for parameters the call refuses): two bytes per pixel, the
+ * winners' k of the two views.  Asynchronous on `stream`; no host synchronisation; no atomics: bit-equal run to run.
+ * Out of scope: a uniqueness ratio, unrectified pairs, colour, census or NCC costs, semi-global aggregation. */
+typedef struct {
+  uint32_t radius;          /* r in 1..15; the window is (2r + 1)^2.  Upstream's five sizes: r = 1, 4, 7, 12, 15 */
+  int32_t minDisparity;     /* -32768 .. 32767 */
+  uint32_t numDisparities;  /* D in 1..256 */
+  uint32_t maxCost;         /* a winner costlier than this is invalid; UINT32_MAX = no test */
+  int32_t lrTolerance;      /* < 0 = no left-right check */
+  uint32_t subpixel;        /* 0 or 1 */
+} ssrlcv_stereo_params;
+size_t ssrlcv_hip_stereo_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_stereo_params* params);
+int ssrlcv_hip_stereo_sad_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params* params,
+                             void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream);
+/* The valid pixels of a disparity map with x % step == 0 and y % step == 0, in raster order, as the sparse path's records:
+ * Match{invalid = 0, {leftId, (x, y)}, {rightId, ((float)x - disparity, (float)y)}}, padding bytes zero -- what
+ * ssrlcv_hip_matchset_from_matches and the triangulation take unchanged.  *count_dev (device) = the full count; only the first
+ * min(count, capacity) records are written, in order, and nothing behind out[capacity) is touched (dense SIFT's item 6); out
+ * may be NULL with capacity 0.  SSRLCV_ERR_INVALID_ARG for step 0 or w h >= 2^31, then for a NULL buffer; SSRLCV_ERR_WORKSPACE
+ * below ssrlcv_hip_stereo_matches_workspace_bytes (host only; 0 for a refused step or size).  One ordered compaction
+ * (csrc/compact.h); asynchronous on `stream`. */
+size_t ssrlcv_hip_stereo_matches_workspace_bytes(uint32_t w, uint32_t h, uint32_t step);
+int ssrlcv_hip_stereo_matches(const float* disparity, uint32_t w, uint32_t h, uint32_t step, int leftId, int rightId, ssrlcv_match* out,
+                              uint32_t capacity, uint32_t* count_dev, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+/* PointCloudFactory::stereo_disparity: per match d = kp0.x - kp1.x, Z = (foc * baseline) / (d + doffset),
+ * X = ((kp0.x - cx) * Z) / foc, Y = ((kp0.y - cy) * Z) / foc, in float32 in exactly that order, nothing contracted.  An
+ * invalid match, or one whose d + doffset is not above 0, gives (0, 0, 0): the value ssrlcv_hip_point_normals writes for a
+ * missing result.  foc not finite or 0: SSRLCV_ERR_INVALID_ARG.  Asynchronous on `stream`. */
+int ssrlcv_hip_stereo_points(const ssrlcv_match* matches, uint32_t n, float foc, float baseline, float doffset, float cx, float cy,
+                             ssrlcv_float3* points, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -65,7 +65,8 @@ def load():
                      "ssrlcv_hip_select_pair_workspace_bytes", "ssrlcv_hip_filter_workspace_bytes", "ssrlcv_hip_merge_workspace_bytes",
                      "ssrlcv_hip_fmatrix_ransac_workspace_bytes", "ssrlcv_hip_knn_workspace_bytes",
                      "ssrlcv_hip_neighbor_filter_workspace_bytes", "ssrlcv_hip_match2_workspace_bytes",
-                     "ssrlcv_hip_sift_dense_workspace_bytes"):
+                     "ssrlcv_hip_sift_dense_workspace_bytes", "ssrlcv_hip_stereo_workspace_bytes",
+                     "ssrlcv_hip_stereo_matches_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -104,4 +105,6 @@ EXPORTED = [
     "ssrlcv_hip_flag_edges", "ssrlcv_hip_check_keypoints", "ssrlcv_hip_pixel_gradients", "ssrlcv_hip_compute_thetas",
     "ssrlcv_hip_expand_keypoints", "ssrlcv_hip_fill_descriptors",
     "ssrlcv_sift_dense_grid", "ssrlcv_sift_dense_max_features", "ssrlcv_hip_sift_dense_workspace_bytes", "ssrlcv_hip_sift_dense_u8",
+    "ssrlcv_hip_stereo_workspace_bytes", "ssrlcv_hip_stereo_sad_u8", "ssrlcv_hip_stereo_matches_workspace_bytes",
+    "ssrlcv_hip_stereo_matches", "ssrlcv_hip_stereo_points",
 ]

@@ -556,6 +556,63 @@ def sift_dense(pix_d, stride=1, sigma=1.6, max_orientations=2, orientation_thres
     return feats[: min(n, cap) * 152], n
 
 
+# ------------------------------------------------------------------ dense stereo
+class StereoParams(ctypes.Structure):
+    _fields_ = [("radius", c_u32), ("minDisparity", ctypes.c_int32), ("numDisparities", c_u32), ("maxCost", c_u32),
+                ("lrTolerance", ctypes.c_int32), ("subpixel", c_u32)]
+
+
+STEREO_NO_LIMIT = 0xFFFFFFFF  # maxCost: no test
+STEREO_INVALID_BITS = 0x7FC00000  # the bit pattern of an invalid pixel of a disparity map
+
+
+def stereo_workspace(w, h, params):
+    return dev_bytes(int(LIB.ssrlcv_hip_stereo_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(params))))
+
+
+def stereo_disparity(left_d, right_d, radius=4, min_disparity=0, num_disparities=64, max_cost=STEREO_NO_LIMIT, lr_tolerance=1,
+                     subpixel=True, want_cost=True, workspace=None):
+    """SAD block matching (ssrlcv_hip_stereo_sad_u8) of two rectified u8 CUDA tensors (H, W).
+    -> (disparity float32 (H, W), invalid pixels hold STEREO_INVALID_BITS; cost int32 (H, W) holding the uint32 bits, or
+    None).  Asynchronous on the current stream."""
+    h, w = left_d.shape
+    assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
+    assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
+    p = StereoParams(radius, min_disparity, num_disparities, max_cost, lr_tolerance, 1 if subpixel else 0)
+    need = int(LIB.ssrlcv_hip_stereo_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
+    disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
+    check(LIB.ssrlcv_hip_stereo_sad_u8(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()),
+                                       ptr(disp), ptr(cost), stream_ptr()))
+    return disp, cost
+
+
+def stereo_matches(disp_d, step=1, left_id=0, right_id=1, capacity=None):
+    """The valid pixels of a disparity map on the `step` grid as Match records (ssrlcv_hip_stereo_matches), in raster order.
+    -> (Match bytes [min(count, capacity) * 40], count).  capacity defaults to the grid's size."""
+    h, w = disp_d.shape
+    assert step >= 1 and disp_d.dtype == torch.float32 and disp_d.is_cuda and disp_d.is_contiguous()  # read with pitch w
+    cap = -(-w // step) * -(-h // step) if capacity is None else int(capacity)
+    need = int(LIB.ssrlcv_hip_stereo_matches_workspace_bytes(c_u32(w), c_u32(h), c_u32(step)))
+    ws = dev_bytes(need)
+    out = dev_bytes(cap * 40)
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_stereo_matches(ptr(disp_d), c_u32(w), c_u32(h), c_u32(step), c_int(left_id), c_int(right_id), ptr(out),
+                                        c_u32(cap), ptr(count), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    n = int(count.item())
+    return out[: min(n, cap) * 40], n
+
+
+def stereo_points(matches_d, n, foc, baseline, doffset, cx, cy):
+    """upstream's stereo_disparity (ssrlcv_hip_stereo_points) -> float32 (n, 3)"""
+    assert matches_d.dtype == torch.uint8 and matches_d.numel() >= 40 * n
+    pts = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    check(LIB.ssrlcv_hip_stereo_points(ptr(matches_d), c_u32(n), c_f32(foc), c_f32(baseline), c_f32(doffset), c_f32(cx), c_f32(cy),
+                                       ptr(pts), stream_ptr()))
+    return pts
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

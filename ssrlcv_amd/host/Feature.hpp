@@ -36,4 +36,30 @@ struct SIFT_Descriptor {
 
 static_assert(sizeof(Feature<SIFT_Descriptor>) == sizeof(ssrlcv_sift_feature), "Feature<SIFT_Descriptor> must be 152 B");
 
+// Window_3x3 ... Window_31x31: a square of pixels around a location, compared by the sum of absolute differences.  Host-side
+// types with a host helper, like SIFT_Descriptor's: the dense-stereo kernels (DisparityFactory.hpp, csrc/stereo.hip) never
+// materialise a window -- they work from the two images directly -- so no device array of these exists.
+template <int N>
+struct Window_NxN {
+  unsigned char values[N][N];
+  Window_NxN() {
+    for (int y = 0; y < N; ++y)
+      for (int x = 0; x < N; ++x) values[y][x] = 0;
+  }
+  // sum of absolute differences with early exit; exact in float (at most 961 * 255 < 2^24)
+  float distProtocol(const Window_NxN<N>& b, const float& bestMatch = FLT_MAX) const {
+    float dist = 0.0f;
+    for (int y = 0; y < N && dist < bestMatch; ++y)
+      for (int x = 0; x < N; ++x) dist += values[y][x] > b.values[y][x] ? (float)(values[y][x] - b.values[y][x]) : (float)(b.values[y][x] - values[y][x]);
+    return dist;
+  }
+};
+typedef Window_NxN<3> Window_3x3;
+typedef Window_NxN<9> Window_9x9;
+typedef Window_NxN<15> Window_15x15;
+typedef Window_NxN<25> Window_25x25;
+typedef Window_NxN<31> Window_31x31;
+static_assert(sizeof(Window_3x3) == 9 && sizeof(Window_9x9) == 81 && sizeof(Window_15x15) == 225 && sizeof(Window_25x25) == 625 &&
+              sizeof(Window_31x31) == 961, "Window_NxN holds N x N bytes");
+
 }  // namespace ssrlcv

@@ -1,7 +1,8 @@
 // ssrlcv_amd/host/MatchFactory.hpp -- MatchFactory<T> with the reference's signatures (include/MatchFactory.cuh:23-309),
 // bound to the fp16-MFMA matcher of the HIP C ABI.  Provided for T = SIFT_Descriptor (the pipeline's only
-// instantiation, src/Pipeline.cu:175); Window_* descriptors, FeatureMatch outputs, disparity matchers and match-file
-// IO are out of scope.
+// instantiation, src/Pipeline.cu:175).  The Window_* descriptors' disparity matchers are DisparityFactory.hpp (dense stereo
+// from the two images, no per-pixel windows); FeatureMatch outputs and match-file IO are out of scope (SURVEY.md section 2
+// row 6).
 //
 // Every method keeps upstream's memory-state contract: inputs are moved to the gpu for the call and restored to their
 // origin state before returning; results are fresh Unity objects on the gpu holding only the valid matches

@@ -2,8 +2,9 @@
 // (include/PointCloudFactory.cuh:25-48,93-255), bound to the HIP C ABI: generateBundles, the two-view / N-view
 // triangulators and BundleAdjustTwoView.  Memory-state side effects follow upstream: generateBundles leaves the match
 // set on the cpu (src/PointCloudFactory.cu:909-914), triangulators return the cloud on the cpu and drop the gpu copies
-// of lines/bundles (:286-290).  linearCutoffFilter / deterministicStatisticalFilter (section 8f item 1) are provided;
-// stereo disparity, plane fitting, debug dumps and cloud scale/rotate helpers are out of scope.
+// of lines/bundles (:286-290).  linearCutoffFilter / deterministicStatisticalFilter (section 8f item 1) and stereo_disparity
+// (the cloud of DisparityFactory.hpp's matches) are provided; plane fitting, debug dumps and cloud scale/rotate helpers are
+// out of scope.
 //
 // BundleAdjustTwoView keeps upstream's control flow (:1832-2262) but evaluates all 24 + 588 finite-difference points
 // of calculateImageGradient / calculateImageHessian (:1059-1504) in ONE fused launch (ssrlcv_hip_ba_sweep2) instead of
@@ -139,6 +140,26 @@ class PointCloudFactory {
       images[i]->setFloatVector(tmp);
     }
     return generateBundles(matchSet, images);
+  }
+
+  // stereo_disparity: the cloud of a rectified pair's matches, Z = foc baseline / (d + doffset) with d = kp0.x - kp1.x,
+  // X = (kp0.x - center.x) Z / foc, Y likewise (ssrlcv_hip_stereo_points); the four-argument form measures from the pixel
+  // origin.  Like the triangulators the cloud comes back on the cpu; the matches are restored to their origin state.
+  ptr::value<Unity<float3>> stereo_disparity(ptr::value<Unity<Match>> matches, float foc, float baseline, float doffset, float2 center) {
+    MemoryState origin = matches->getMemoryState();
+    if (origin != gpu) matches->setMemoryState(gpu);
+    const uint32_t n = (uint32_t)matches->size();
+    ptr::value<Unity<float3>> pointcloud(nullptr, (unsigned long)n, gpu);
+    HipSafeCall(ssrlcv_hip_stereo_points(reinterpret_cast<const ssrlcv_match*>(matches->device.get()), n, foc, baseline, doffset, center.x,
+                                         center.y, reinterpret_cast<ssrlcv_float3*>(pointcloud->device.get()), nullptr));
+    HipCheckError();
+    pointcloud->transferMemoryTo(cpu);
+    pointcloud->clear(gpu);
+    if (origin != gpu) matches->setMemoryState(origin);
+    return pointcloud;
+  }
+  ptr::value<Unity<float3>> stereo_disparity(ptr::value<Unity<Match>> matches, float foc, float baseline, float doffset) {
+    return stereo_disparity(matches, foc, baseline, doffset, float2{0.0f, 0.0f});
   }
 
   // src/PointCloudFactory.cu:228-556

@@ -5,6 +5,7 @@
 #include "Image.hpp"
 #include "SIFT_FeatureFactory.hpp"
 #include "MatchFactory.hpp"
+#include "DisparityFactory.hpp"
 #include "PointCloudFactory.hpp"
 #include "io_util.hpp"
 #include "MeshFactory.hpp"

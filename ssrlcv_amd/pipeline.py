@@ -137,6 +137,31 @@ def extract_features_dense(pixel_tensors, stride=1, sigma=1.6, max_orientations=
     return out
 
 
+def stereo_disparity(left, right, radius=4, min_disparity=0, num_disparities=64, max_cost=capi.STEREO_NO_LIMIT, lr_tolerance=1,
+                     subpixel=True, want_cost=True):
+    """Dense stereo on a rectified pair (u8 CUDA tensors (H, W)): SAD block matching over (2 radius + 1)^2 windows, the
+    disparities min_disparity .. min_disparity + num_disparities - 1, with the cost limit, left-right check and sub-pixel
+    step of include/ssrlcv_hip.h "dense stereo".  -> (disparity float32 (H, W), cost or None): invalid pixels hold the bit
+    pattern capi.STEREO_INVALID_BITS (a NaN) and cost 0xFFFFFFFF."""
+    return capi.stereo_disparity(left, right, radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel, want_cost)
+
+
+def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, **disparity_args):
+    """Rectified pair -> dense cloud: stereo_disparity, then capi.stereo_matches (the valid pixels of the `step` grid as Match
+    records), then capi.stereo_points (upstream's stereo_disparity: Z = foc baseline / (d + doffset)).  cx, cy default to the
+    image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel
+    (the cost map is not computed: want_cost is not taken).  -> (points float32 (n, 3), Match bytes, n, disparity).
+    The Match records are the sparse path's: with real cameras they also go through capi.matchset_from_matches and
+    triangulate() unchanged (tests/test_gpu_stereo.py does)."""
+    h, w = left.shape
+    if "want_cost" in disparity_args:
+        raise TypeError("stereo_cloud computes no cost map: call stereo_disparity for one")
+    disp, _ = stereo_disparity(left, right, want_cost=False, **disparity_args)
+    matches, n = capi.stereo_matches(disp, step, left_id, right_id)
+    pts = capi.stereo_points(matches, n, foc, baseline, doffset, w / 2.0 if cx is None else cx, h / 2.0 if cy is None else cy)
+    return pts, matches, n, disp
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:

@@ -3,6 +3,7 @@
 // wave-instruction per SIMD.  Each kernel runs 8 independent chains of one instruction, 16x unrolled.
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define CHAIN8(OP)            \
@@ -70,6 +71,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define OP_SMOV(x) asm volatile("v_fma_f32 %0, %0, %1, %2\n s_mov_b64 s[20:21], exec" : "+v"(x) : "v"(a), "v"(b) : "s20", "s21");
 #define OP_MADI24(x) asm volatile("v_mad_i32_i24 %0, %0, -2, %1" : "+v"(x) : "v"(iters));
 #define OP_MIN3I(x) asm volatile("v_min3_i32 %0, %0, %1, %1" : "+v"(x) : "v"(iters));
+// the byte-SAD and byte-align instructions of the dense-stereo cost pass (csrc/stereo.hip)
+#define OP_SADU8(x) asm volatile("v_sad_u8 %0, %1, %2, %0" : "+v"(x) : "v"(iters), "v"(a));
+#define OP_ALIGNBYTE(x) asm volatile("v_alignbyte_b32 %0, %0, %1, 1" : "+v"(x) : "v"(iters));
 #define OP_DSADD(x) asm volatile("ds_add_u64 %0, %1" : : "v"(ldsaddr), "v"(x64) : "memory");
 
 DEF_KERNEL(k_fma, float, INITF, OP_FMA)
@@ -114,6 +118,8 @@ DEF_KERNEL(k_muls, float, INITF, OP_MUL_S)
 DEF_KERNEL(k_cmpx, float, INITF, OP_CMPX)
 DEF_KERNEL(k_salu2, float, INITF, OP_SALU2)
 DEF_KERNEL(k_smov, float, INITF, OP_SMOV)
+DEF_KERNEL(k_sadu8, unsigned, INITU, OP_SADU8)
+DEF_KERNEL(k_alignbyte, unsigned, INITU, OP_ALIGNBYTE)
 __global__ void k_dsadd(float* out, int iters, float a, float b) {
   __shared__ unsigned long long sh[4096];
   for (int i = threadIdx.x; i < 4096; i += 256) sh[i] = 0;
@@ -163,7 +169,7 @@ __global__ void k_pkadd(float* out, int iters, float a, float b) {
 typedef void (*kern_t)(float*, int, float, float);
 struct Entry { const char* name; kern_t fn; };
 
-int main() {
+int main(int argc, char** argv) {  // optional argument: only the entries whose name contains it
   float* d;
   hipMalloc(&d, 256 * 4096 * 4);
   hipEvent_t e0, e1;
@@ -183,8 +189,10 @@ int main() {
                  {"v_readlane_b32", k_readlane}, {"v_readfirstlane_b32", k_readfirst}, {"v_mov_b32", k_mov},
                  {"v_mov_b32 v, s", k_movs}, {"v_fma_f32 v,s,v", k_fmas}, {"v_mul_f32 s,v", k_muls},
                  {"s_mov exec; v_cmpx; v_fma; s_mov exec", k_cmpx}, {"v_fma + 2 SALU", k_salu2},
-                 {"v_fma + s_mov_b64", k_smov}, {"v_mad_i32_i24", k_madi24}, {"v_min3_i32", k_min3i}, {"ds_add_u64 (conflict-free)", k_dsadd}};
+                 {"v_fma + s_mov_b64", k_smov}, {"v_mad_i32_i24", k_madi24}, {"v_min3_i32", k_min3i}, {"v_sad_u8", k_sadu8},
+                 {"v_alignbyte_b32", k_alignbyte}, {"ds_add_u64 (conflict-free)", k_dsadd}};
   for (const Entry& e : tab) {
+    if (argc > 1 && !strstr(e.name, argv[1])) continue;
     printf("%-46s", e.name);
     for (int wavesPerSimd = 1; wavesPerSimd <= 8; wavesPerSimd *= 2) {
       int blocks = 256 * wavesPerSimd;  // 256 threads = 4 waves = 1 per SIMD per block
