@@ -185,7 +185,12 @@ int ssrlcv_hip_pose_from_fmatrix(const ssrlcv_match* matches, uint32_t numMatche
  *   k-NN        the neighbours of i are the k points j != i smallest by the key (d2(i, j), j), in ascending key order, with
  *               dx = p[j].x - p[i].x (likewise y, z) and d2 = (dx*dx + dy*dy) + dz*dz in float32, every product and sum
  *               rounded in that order.  Duplicates (d2 = 0) are ordinary neighbours; ties go to the lower index.  The
- *               result is unique: it does not depend on the cell size, the launch shape or scheduling.
+ *               result is unique: it does not depend on the cell size, the launch shape or scheduling.  This holds for
+ *               every finite input, tiny and huge scales included: where the products are subnormal or underflow to 0 the
+ *               float32 key, not the distance, still decides (all d2 = 0: the k lowest indices), and where they overflow
+ *               d2 = +inf with a valid index, ties by index.  The grid search relies on d2 following the true distance
+ *               (to 5 2^-24 relative: difference, product, two sums) only for squared distances of 2^-100 and more, where
+ *               no significant product underflows; below, every query is answered by the exact scan over all points.
  *   mean        m_i = (sqrtf(d2_1) + ... + sqrtf(d2_k)) / k: a sequential float32 sum in neighbour order, one division.
  *   filter      over the points with finite m_i: mu = sum(m_i) / n_f, std = sqrt(sum((m_i - mu)^2) / n_f) (population),
  *               both float64 through a fixed partition and a fixed tree (no float atomics: bit-identical run to run);

@@ -12,7 +12,7 @@
 //   exclusive scan      slot starts (scan_lookback.h); k_scatter puts the points in cell-contiguous order
 //   k_knn_grid<K>       THE HOT PATH: one lane per point in cell order, top-K (d2, j) keys in registers, rings of cells
 //                       until the k-th key is below the guaranteed distance of every unsearched cell; queries still open
-//                       after kRingCap rings go to the far list
+//                       after kRingCap rings, or at a scale where float32 products underflow, go to the far list
 //   k_knn_far<K>        the far list, exactly: every finite point through LDS tiles, 8 waves per 64 queries
 // Everything is keyed by (d2, j), so the result does not depend on h, on the order inside a cell or on scheduling.
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kRingCap = 3;            // rings 0..kRingCap on the grid, then the far path
+constexpr double kGridBoundMin = 0x1p-100;  // the grid's ring stop holds for squared distances from here up (k_knn_grid)
 constexpr int kFarWaves = 8;          // waves sharing the 64 queries of a far block
 constexpr int kFarTile = 256;          // points staged in LDS per wave and step of the far scan
 constexpr uint32_t kAxisBits = 21;     // cell coordinate bits per axis of the packed key
@@ -323,8 +324,15 @@ __global__ __launch_bounds__(kThreads) void k_knn_grid(const float4* __restrict_
       }
     }
     // every unsearched cell lies beyond the faces of the searched (2r+1)^3 block: the query's distance to the nearest
-    // face, less a margin for the float64 cell coordinates, is a lower bound of their true distance; the float32 d2 of
-    // the contract is at least (1 - 2^-22) of the true one (five correctly rounded steps)
+    // face, less a margin for the float64 cell coordinates, is a lower bound D of the true squared distance of every
+    // point in them.  The float32 d2 of the contract is at least (1 - 5 2^-24) of the true one (the difference, the
+    // product and two sums, each within 2^-24 relative) ONLY WHILE NOTHING UNDERFLOWS: a product below 2^-126 is rounded
+    // to a multiple of 2^-149, and below 2^-150 to 0, so at tiny scales the float32 key stops following the distance
+    // (at 2^-80 every d2 is 0 and the contract's answer is the k lowest indices).  With D >= 2^-100 the largest of the
+    // three products is at least 2^-102, normal like every sum it enters, and the two others lose at most 2^-150 each:
+    // d2 >= D (1 - 5 2^-24) - 2^-149 >= D (1 - 5 2^-24 - 2^-49) > D (1 - 1e-6).  So the ring stop is taken only with
+    // bound >= kGridBoundMin; below it the query goes to the far scan, which evaluates the key itself and is exact at
+    // every scale.  (Overflow needs no guard: d2 = +inf is above every bound.)
     double gap = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -335,7 +343,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_grid(const float4* __restrict_
     }
     gap = fmax(gap - 1e-6, 0.0) * cell;
     const double bound = gap * gap * (1.0 - 1e-6);
-    done = (double)__uint_as_float((uint32_t)(top.kth >> 32)) < bound;
+    done = bound >= kGridBoundMin && (double)__uint_as_float((uint32_t)(top.kth >> 32)) < bound;
   }
   if (!done) {
     far[atomicAdd(&h->farCount, 1u)] = qi;
@@ -344,7 +352,8 @@ __global__ __launch_bounds__(kThreads) void k_knn_grid(const float4* __restrict_
   top.write(qi, k, nbr, d2out);
 }
 
-// the far list: every finite point, exactly.  A block takes 64 queries (one per lane) and kFarWaves waves: wave w scans
+// the far list: every finite point, exactly: the key of the contract is evaluated for every pair, so underflow (d2
+// subnormal or 0) and overflow (d2 = +inf) order as the contract says, with no distance argument.  A block takes 64 queries (one per lane) and kFarWaves waves: wave w scans
 // tiles w, w + kFarWaves, ... of the cell-ordered points through its own LDS tile (every lane reads the same point: an
 // LDS broadcast), then the waves' lists are merged into wave 0's through LDS.  The split keeps the GPU busy when only
 // a few thousand queries are far.

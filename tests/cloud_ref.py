@@ -3,8 +3,10 @@ _point_normals), the reference the GPU tests hold csrc/cloud.hip to.
 
 k-NN: the k points j != i smallest by (d2, j), d2 = (dx*dx + dy*dy) + dz*dz in float32 with dx = p[j] - p[i].  Candidates
 come from scipy's cKDTree (float64) with a margin and are re-ranked by the exact float32 key; a row whose margin does not
-prove the answer (ties at the edge of the candidate list) is redone by brute force.  Without scipy every row is brute
-force.  Non-finite points get (UINT32_MAX, +inf) rows and are nobody's neighbour."""
+prove the answer (ties at the edge of the candidate list, or a k-th d2 so small that float32 products underflow and the
+float64 distances no longer bound the float32 ones) is redone by brute force.  Without scipy every row is brute force.
+Non-finite points get (UINT32_MAX, +inf) rows and are nobody's neighbour.  knn_brute is the contract itself at every
+scale: the edge-case tests (tests/cloud_cases.py) use it alone."""
 import os
 import sys
 
@@ -18,6 +20,7 @@ except ImportError:  # pragma: no cover - scipy is optional: the chunked brute f
     cKDTree = None
 
 NONE = np.uint32(0xFFFFFFFF)
+UNDERFLOW_GUARD = np.float32(2.0 ** -100)   # a d2 at or above it has a relative float32 error below 1e-6 (see knn)
 
 
 def finite_mask(p):
@@ -28,8 +31,9 @@ def d2_f32(q, c):
     """the contract's float32 d2 of queries q [..., 3] to candidates c [..., 3] (broadcast), dx = c - q"""
     q = q.astype(np.float32, copy=False)
     c = c.astype(np.float32, copy=False)
-    dx, dy, dz = c[..., 0] - q[..., 0], c[..., 1] - q[..., 1], c[..., 2] - q[..., 2]
-    return (dx * dx + dy * dy) + dz * dz
+    with np.errstate(over="ignore", under="ignore"):  # +inf and subnormal / zero d2 are inside the contract
+        dx, dy, dz = c[..., 0] - q[..., 0], c[..., 1] - q[..., 1], c[..., 2] - q[..., 2]
+        return (dx * dx + dy * dy) + dz * dz
 
 
 def _keys(d2, j):
@@ -97,10 +101,13 @@ def knn(p, k, margin=None):
     out_d2 = np.full((n, k), np.inf, np.float32)
     nbr[fin], out_d2[fin] = nb, d2
     # proof of the margin: every point outside the candidates is at least as far (float64) as the last candidate; its
-    # float32 d2 is within 1e-6 relative of the float64 one.  A row whose k-th key is not clearly below that is redone.
+    # float32 d2 is within 1e-6 relative of the float64 one WHERE THAT IS AT LEAST 2^-100 (the largest of the three
+    # products is then normal, and the two that may be subnormal add at most 2 * 2^-150).  Below, products underflow and
+    # the float32 order is no longer the spatial one.  A row whose k-th key is not clearly below the last candidate's
+    # distance, or is below 2^-100, is redone.
     if kq < len(fin):
         last = dist[:, -1] ** 2
-        unsure = ~(d2[:, -1].astype(np.float64) * (1 + 1e-5) < last * (1 - 1e-5))
+        unsure = ~(d2[:, -1].astype(np.float64) * (1 + 1e-5) < last * (1 - 1e-5)) | ~(d2[:, -1] >= UNDERFLOW_GUARD)
         if unsure.any():
             bn, bd = knn_brute(p, k, rows=fin[unsure])
             nbr[fin[unsure]], out_d2[fin[unsure]] = bn, bd
@@ -129,21 +136,29 @@ def filter_mask(m, t):
     return np.isfinite(m) & (m.astype(np.float64) <= t)
 
 
+def covariances(p, nbr):
+    """the float64 covariance (times k + 1) of every row with a finite centre and k neighbours below n -> (row indices,
+    cov [m, 3, 3]); shifted by p_i first, so k + 1 coincident points give exactly zero"""
+    p = np.asarray(p, np.float32)
+    ok = finite_mask(p) & (nbr < len(p)).all(1)
+    idx = np.nonzero(ok)[0]
+    P = p.astype(np.float64)
+    grp = np.concatenate([P[idx][:, None, :], P[nbr[idx].astype(np.int64)]], 1)   # [m, k + 1, 3]
+    grp = grp - P[idx][:, None, :]
+    c = grp - grp.mean(1, keepdims=True)
+    return idx, np.einsum("mia,mib->mab", c, c)
+
+
 def normals(p, nbr, k, viewpoint):
     """-> (normals float64 [n, 3] (oriented, (0,0,0) where the contract says so), relative eigengap (l2 - l1) / l3)"""
     p = np.asarray(p, np.float32)
     n = len(p)
     out = np.zeros((n, 3))
     gap = np.zeros(n)
-    ok = finite_mask(p) & (nbr != NONE).all(1)
-    idx = np.nonzero(ok)[0]
+    idx, cov = covariances(p, nbr)
     if len(idx) == 0:
         return out, gap
     P = p.astype(np.float64)
-    grp = np.concatenate([P[idx][:, None, :], P[nbr[idx].astype(np.int64)]], 1)   # [m, k + 1, 3]
-    grp = grp - P[idx][:, None, :]
-    c = grp - grp.mean(1, keepdims=True)
-    cov = np.einsum("mia,mib->mab", c, c)
     w, v = np.linalg.eigh(cov)
     e = v[:, :, 0]
     vp = np.asarray(viewpoint, np.float64)
@@ -191,6 +206,7 @@ def self_test(seed=1):
     bad[::37] = np.nan
     bad[5, 1] = np.inf
     clouds.append(bad)
+    clouds.append(rng.random((600, 3)).astype(np.float32) * np.float32(2.0 ** -70))  # products underflow: index order
     for p in clouds:
         for k in (1, 8, 16):
             a = knn(p, k)
