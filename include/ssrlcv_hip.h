@@ -109,11 +109,25 @@ int ssrlcv_hip_ba_sweep2(const ssrlcv_multimatch* matches, const ssrlcv_keypoint
  * The device part of PoseEstimator::LM_iteration (src/PoseEstimator.cu:349-393): computeResidualsAndJacobian
  * (:647-729, central differences with delta 1e-5 on roll/pitch/yaw, position columns 0), computeJTJ / computeJTf
  * (:814-844) and computeCost (:731-740) fused; the per-match residual is getResidual (:742-812).
- * out43 (device): JTJ[36] with JTJ[i + 6 j], then JTf[6], then the cost sum(|f|^2). */
+ * out43 (device): JTJ[36] with JTJ[i + 6 j], then JTf[6], then the cost sum(|f|^2).
+ * Contract (tests/test_gpu_pose_edges.py):
+ *   - all 43 floats are written whatever they held; numMatches == 0 gives all +0.  Stream-ordered, no host
+ *     synchronisation.  A NULL matches, pose, query, target or out43: SSRLCV_ERR_INVALID_ARG, nothing written.
+ *   - JTJ is exactly symmetric (one triangle is summed, the other copied).
+ *   - the position rows and columns (3..5) of JTJ and JTf[3..5] are +0 ALWAYS.  This is this library's deliberate
+ *     difference: upstream (and the CPU oracle) multiply the zero position columns into the sums, so a residual that is
+ *     not finite gives NaN * 0 = NaN there; the kernel never forms those products.
+ *   - the per-match residual f and Jacobian J are the float32 values of the reference's expressions; the ORDER of the
+ *     sums over rows and matches is unspecified.  Every returned sum lies within gamma_d * sum |terms| of the exact sum
+ *     of its float32 terms (J[r][a] * J[r][b], J[r][a] * f[r], one |f|^2 per match), gamma_d = d u / (1 - d u),
+ *     u = 2^-24, d the longest chain of additions of the launch (terms per thread + 6 butterfly levels + one atomic per
+ *     wave: 4108 for 262 145 to 524 288 matches); with one match no order enters and the result is bit-exact.  A sum
+ *     over a NaN term is NaN. */
 int ssrlcv_hip_pose_lm_terms(const ssrlcv_match* matches, uint32_t numMatches, const ssrlcv_pose* pose,
                              const ssrlcv_camera* query, const ssrlcv_camera* target, float* out43,
                              ssrlcv_stream_t stream);
-/* computeCost alone (:731-740), for the trial poses of the inner LM loop; cost: one device float. */
+/* computeCost alone (:731-740), for the trial poses of the inner LM loop; cost: one device float, under the same
+ * contract as out43[42] (always written, +0 for numMatches == 0, summation order unspecified within the same bound). */
 int ssrlcv_hip_pose_cost(const ssrlcv_match* matches, uint32_t numMatches, const ssrlcv_pose* pose,
                          const ssrlcv_camera* query, const ssrlcv_camera* target, float* cost, ssrlcv_stream_t stream);
 

@@ -164,6 +164,10 @@ void oracle_pose_residual(const o_pose* pose, const o_camera* query, const o_cam
                           const o_float2* t_loc, float out[4]);
 float oracle_pose_cost(const o_match* matches, uint32_t n, const o_pose* pose, const o_camera* query,
                        const o_camera* target);
+/* one match's residual f[m][0..2] and Jacobian J[m][row][col] (rotation columns, central differences, delta 1e-5):
+ * the terms oracle_pose_lm_terms sums; f: n x 3, J: n x 3 x 3 */
+void oracle_pose_match_terms(const o_match* matches, uint32_t n, const o_pose* pose, const o_camera* query,
+                             const o_camera* target, float* f, float* J);
 void oracle_pose_lm_terms(const o_match* matches, uint32_t n, const o_pose* pose, const o_camera* query,
                           const o_camera* target, float JTJ[36], float JTf[6], float* cost);
 

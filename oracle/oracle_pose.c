@@ -4,7 +4,7 @@
  * reference's formulas only.
  *
  *   getResidual                      src/PoseEstimator.cu:742-812   oracle_pose_residual
- *   computeResidualsAndJacobian      src/PoseEstimator.cu:647-729   (inside oracle_pose_lm_terms)
+ *   computeResidualsAndJacobian      src/PoseEstimator.cu:647-729   oracle_pose_match_terms (rows 0-2, columns 0-2)
  *   computeJTJ / computeJTf          src/PoseEstimator.cu:814-844   (inside oracle_pose_lm_terms)
  *   computeCost                      src/PoseEstimator.cu:731-740   oracle_pose_cost
  *
@@ -58,17 +58,15 @@ float oracle_pose_cost(const o_match* matches, uint32_t n, const o_pose* pose, c
   return cost;
 }
 
-void oracle_pose_lm_terms(const o_match* matches, uint32_t n, const o_pose* pose0, const o_camera* query,
-                          const o_camera* target, float JTJ[36], float JTf[6], float* cost) {
-  for (int i = 0; i < 36; ++i) JTJ[i] = 0;
-  for (int i = 0; i < 6; ++i) JTf[i] = 0;
-  float csum = 0;
+void oracle_pose_match_terms(const o_match* matches, uint32_t n, const o_pose* pose0, const o_camera* query,
+                             const o_camera* target, float* f_out, float* J_out) {
   for (uint32_t m = 0; m < n; ++m) {
     o_float2 q_loc = matches[m].keyPoints[0].loc, t_loc = matches[m].keyPoints[1].loc;
     o_pose pose = *pose0;
-    float f[4], J[4][6];
+    float f[4];
     const float delta = 1e-5;
     residual(&pose, query, target, q_loc, t_loc, f);
+    for (int r = 0; r < 3; ++r) f_out[3 * m + r] = f[r];
     float* ang[3] = {&pose.roll, &pose.pitch, &pose.yaw};
     for (int c = 0; c < 3; ++c) {
       float right[4], left[4];
@@ -78,10 +76,25 @@ void oracle_pose_lm_terms(const o_match* matches, uint32_t n, const o_pose* pose
       *ang[c] -= 2 * delta;
       residual(&pose, query, target, q_loc, t_loc, left);
       *ang[c] = saved;
-      for (int r = 0; r < 4; ++r) J[r][c] = (right[r] - left[r]) / (2 * delta);
+      for (int r = 0; r < 3; ++r) J_out[9 * m + 3 * r + c] = (right[r] - left[r]) / (2 * delta);
     }
-    for (int c = 3; c < 6; ++c)
-      for (int r = 0; r < 4; ++r) J[r][c] = 0;
+  }
+}
+
+void oracle_pose_lm_terms(const o_match* matches, uint32_t n, const o_pose* pose0, const o_camera* query,
+                          const o_camera* target, float JTJ[36], float JTf[6], float* cost) {
+  for (int i = 0; i < 36; ++i) JTJ[i] = 0;
+  for (int i = 0; i < 6; ++i) JTf[i] = 0;
+  float csum = 0;
+  for (uint32_t m = 0; m < n; ++m) {
+    /* the residual's 4th component is 0 and so is the 4th row of J ((0 - 0) / (2 delta)); the position columns are
+     * written as 0.  They stay in the sums as upstream has them: 0 * NaN = NaN reaches the position entries. */
+    float fm[3], Jm[3][3], f[4], J[4][6];
+    oracle_pose_match_terms(matches + m, 1, pose0, query, target, fm, &Jm[0][0]);
+    for (int r = 0; r < 4; ++r) {
+      f[r] = r < 3 ? fm[r] : 0;
+      for (int c = 0; c < 6; ++c) J[r][c] = r < 3 && c < 3 ? Jm[r][c] : 0;
+    }
     for (int r = 0; r < 4; ++r) {
       for (int i = 0; i < 6; ++i) {
         for (int j = 0; j < 6; ++j) JTJ[i + 6 * j] += J[r][i] * J[r][j];

@@ -288,6 +288,15 @@ def oracle_pose_terms(lib, matches, pose6, qcam, tcam):
     return jtj.reshape(6, 6), jtf, float(cost.value)
 
 
+def oracle_pose_match_terms(lib, matches, pose6, qcam, tcam):
+    """-> (f[n, 3], J[n, 3, 3] as J[m, row, col]): the float32 per-match terms oracle_pose_lm_terms sums"""
+    pose = np.asarray(pose6, np.float32).copy()
+    n = len(matches)
+    f, J = np.zeros((n, 3), np.float32), np.zeros((n, 3, 3), np.float32)
+    lib.oracle_pose_match_terms(P(matches), ctypes.c_uint32(n), P(pose), P(qcam), P(tcam), P(f), P(J))
+    return f, J
+
+
 def oracle_pose_cost(lib, matches, pose6, qcam, tcam):
     pose = np.asarray(pose6, np.float32).copy()
     lib.oracle_pose_cost.restype = ctypes.c_float

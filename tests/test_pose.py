@@ -61,11 +61,13 @@ def test_oracle_terms_are_symmetric_on_the_fixture(oracle_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [0, 1, 63, 257, 13534])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 256, 257, 13534])
 def test_pose_terms_match_oracle(oracle_lib, n):
-    """HIP (wave-reduced float sums) vs oracle (sequential float sums): the Jacobian is a central difference of float
-    residuals (delta 1e-5), so single entries carry ~1e-3 relative noise from libm differences; the sums over the
-    matches must agree to 2e-3 of the largest entry, the cost to 1e-4."""
+    """HIP (wave-reduced float sums) vs oracle (sequential float sums) on the fixture.  The per-match residual and Jacobian
+    are the same float32 values on both sides (device_math.h and oracle_math.h spell out one rounding sequence); what
+    differs is the order of the sums.  The sums over the matches must agree to 2e-3 of the largest entry, the cost to
+    1e-4: a coarse check of the fixture path.  tests/test_gpu_pose_edges.py holds every entry to its own derived
+    summation bound and one match bit for bit."""
     from ssrlcv_amd import capi
     cams, m = _fixture_matches()
     m = m[:n]
