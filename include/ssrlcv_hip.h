@@ -46,7 +46,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      later, as pure additions: knn, neighbor_distance_filter (+ their workspace queries), point_normals;
  *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128;
  *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8;
- *      dense stereo: stereo_workspace_bytes, stereo_sad_u8, stereo_matches_workspace_bytes, stereo_matches, stereo_points */
+ *      dense stereo: stereo_workspace_bytes, stereo_sad_u8, stereo_matches_workspace_bytes, stereo_matches, stereo_points;
+ *      rectification: rectify_cameras_host, warp_homography_u8, stereo_mask_rectified, matches_apply_homography */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -619,7 +620,8 @@ int ssrlcv_hip_sift_dense_u8(const uint8_t* pixels, uint32_t w, uint32_t h, cons
  * workspace.  An image smaller than one window is no error: every pixel is invalid.
  * Workspace (ssrlcv_hip_stereo_workspace_bytes; host only; 0 for parameters the call refuses): two bytes per pixel, the
  * winners' k of the two views.  Asynchronous on `stream`; no host synchronisation; no atomics: bit-equal run to run.
- * Out of scope: a uniqueness ratio, unrectified pairs, colour, census or NCC costs, semi-global aggregation. */
+ * Out of scope: a uniqueness ratio, colour, census or NCC costs, semi-global aggregation.  (An unrectified pair of pinhole
+ * cameras is rectified first: "rectification" below.) */
 typedef struct {
   uint32_t radius;          /* r in 1..15; the window is (2r + 1)^2.  Upstream's five sizes: r = 1, 4, 7, 12, 15 */
   int32_t minDisparity;     /* -32768 .. 32767 */
@@ -647,6 +649,87 @@ int ssrlcv_hip_stereo_matches(const float* disparity, uint32_t w, uint32_t h, ui
  * missing result.  foc not finite or 0: SSRLCV_ERR_INVALID_ARG.  Asynchronous on `stream`. */
 int ssrlcv_hip_stereo_points(const ssrlcv_match* matches, uint32_t n, float foc, float baseline, float doffset, float cx, float cy,
                              ssrlcv_float3* points, ssrlcv_stream_t stream);
+
+/* ---- rectification: a converging pair of Image::Camera records -> two homographies -> a rectified pair for the dense stereo
+ * above, and its matches back in source pixels, where they triangulate with the original cameras into the sparse path's world
+ * frame.  Like dense stereo the contract is this project's own; the kernels of csrc/rectify.hip are held to a numpy restatement
+ * of it bit for bit (tests/rectify_ref.py, tests/test_gpu_rectify.py).
+ *
+ * Evaluating a homography.  H is 9 floats, row-major.  At a float point (x, y), in float32, every product and sum rounded on
+ * its own, nothing contracted:
+ *     X = (H0 x + H1 y) + H2      Y = (H3 x + H4 y) + H5      W = (H6 x + H7 y) + H8
+ *     sx = X / W, sy = Y / W      two IEEE divisions
+ * The point is MAPPED if W > 0 and sx, sy are finite.  It is INSIDE a sw x sh source if it is mapped and 0 <= sx <= sw - 1 and
+ * 0 <= sy <= sh - 1.
+ *
+ * ssrlcv_hip_warp_homography_u8: dst(x, y) = src sampled bilinearly at H (x, y).  H is a HOST pointer; its 9 values travel as
+ * kernel arguments.  Both images are uint8 with pitch = width.  For every output pixel (x, y), converted exactly to float:
+ *   not mapped  the byte is 0.
+ *   otherwise   sx is clamped to [0, srcW - 1] and sy to [0, srcH - 1];
+ *               x0 = min((int)floor(sx), max(srcW - 2, 0)), x1 = min(x0 + 1, srcW - 1), fx = sx - (float)x0 (exact); y0, y1, fy
+ *               the same from sy and srcH;
+ *               a, b, c, d = S(x0, y0), S(x1, y0), S(x0, y1), S(x1, y1) as floats;
+ *               top = a + fx (b - a), bot = c + fx (d - c), v = top + fy (bot - top): every operation rounded, no fma;
+ *               the byte is (uint8)floor(v + 0.5f).  v stays in [0, 255] (each step lies between its two end values).
+ * Every output pixel is written and nothing behind dst[dstW dstH); the border is replicated, never read outside; the source is
+ * never written.  Decided on the host before any launch, the parameters before the buffers: SSRLCV_ERR_INVALID_ARG for H NULL,
+ * a source side 0, any side above 2^24, or w h >= 2^31 of either image; a dst of 0 pixels is then SSRLCV_OK (nothing to do);
+ * then SSRLCV_ERR_INVALID_ARG for a NULL buffer.  Asynchronous on `stream`, no workspace, no atomics, bit-equal run to run.
+ *
+ * ssrlcv_hip_stereo_mask_rectified: in place on the maps ssrlcv_hip_stereo_sad_u8 wrote for a pair warped by Hl, Hr (host
+ * pointers) from srcW x srcH sources.  A pixel (x, y) whose disparity delta is not the invalid pattern stays valid only if
+ *   the four points (x +- r, y +- r) are inside the left source under Hl, and
+ *   the four points (xr +- (r + 0.5), y +- r), xr = (float)x - delta (one float subtraction, then one float addition or
+ *   subtraction of the exact r + 0.5), are inside the right source under Hr
+ * (the box is half a pixel wider than the integer winner's window because |delta - d*| <= 0.5).  Otherwise disparity <-
+ * 0x7FC00000, and cost <- UINT32_MAX if a cost map is given.  The corners suffice: a homography maps lines to lines, so the
+ * pre-image of the source rectangle (in the half plane W > 0) is convex, and a box whose four corners lie in a convex set lies
+ * in it.  What the call does not do: the left-right check ran before it, over costs that include replicated border, so the mask
+ * only removes pixels; it never rescues one.  SSRLCV_ERR_INVALID_ARG for Hl or Hr NULL, a source side 0, any side above 2^24,
+ * w h >= 2^31 of the map or the source, radius outside 1..15; a map of 0 pixels is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG
+ * for disparity NULL (cost may be NULL).  Asynchronous on `stream`.
+ *
+ * ssrlcv_hip_matches_apply_homography: in place.  For each record with invalid == 0, keyPoints[k].loc <- (sx, sy) under Hk (host
+ * pointers; a NULL Hk leaves that side alone).  If either side is not mapped the record keeps both locations as they were and
+ * gets invalid = 1.  Parent ids and padding bytes are untouched.  n == 0 is SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for matches
+ * NULL.  With Hl, Hr of a rectification it turns ssrlcv_hip_stereo_matches' records into matches in source pixels.
+ *
+ * ssrlcv_rectify_cameras_host: host only, double precision, no device touched -- the one definition both binders call.
+ *   1  per camera, the focal length in pixels f = foc / dpix with dpix = foc tan(fov.x / 2) / (size.x / 2), the value
+ *      generateBundle recomputes (the stored dpix is ignored);
+ *   2  R_i = Rz Ry Rx of cam_rot (rotatePoint's convention), double sin / cos of the float angles;
+ *   3  b = pos_r - pos_l, xh = b / |b|; yh = normalise((z_l + z_r) x xh), z_i the third column of R_i; zh = xh x yh;
+ *   4  the Euler angles of [xh yh zh]: y = -asin(clamp(M20)), x = atan2(M21, M22), z = atan2(M10, M00), rounded to float32 and
+ *      stored as cam_rot; R_n is rebuilt from the ROUNDED angles and everything below uses that R_n;
+ *   5  with a_i = R_n^T z_i: tl = rint(f_l a_l.x / a_l.z), tr = rint(f_l a_r.x / a_r.z),
+ *      ty = rint(f_l (a_l.y / a_l.z + a_r.y / a_r.z) / 2)   (rint: to nearest, ties to even);
+ *   6  with K(f) = [[f, 0, w/2], [0, f, h/2], [0, 0, 1]] and T(t) = [[1, 0, t], [0, 1, ty], [0, 0, 1]]:
+ *      H_i = K(f_i) R_i^T R_n K(f_l)^-1 T(t_i), divided by its last entry; G_i its inverse, normalised the same way; all four
+ *      rounded to float32.  H_i takes a rectified pixel to its source pixel (what the warp and the mask evaluate), G_i back;
+ *   7  w, h = the left camera's size; foc = f_l, baseline = |b|, doffset = tl - tr, cx = w/2 - tl, cy = h/2 - ty: exactly
+ *      ssrlcv_hip_stereo_points' parameters, so Z = foc baseline / (d + doffset) holds for the rectified pair, and both old
+ *      image centres land on the rectified centre: the content overlaps at disparities near 0, whatever the convergence.
+ * Refusals, in this order: SSRLCV_ERR_INVALID_ARG for a NULL; for sizes that differ or have a zero side; for foc or fov.x not
+ * finite and positive; for |b| = 0; for xh . (first column of R_l) <= 0 (the caller has the cameras the wrong way round);
+ * SSRLCV_ERR_UNSUPPORTED when (z_l + z_r) x xh vanishes (norm below 1e-6: float32 angles resolve no less); when a_l.z or a_r.z is below cos 45 deg; when a last
+ * entry to divide by is not positive.  `out` is untouched on any error.
+ *
+ * Out of scope: rectifying from a fundamental matrix alone (Hartley) -- the device entry points take any homography, so it can
+ * come later without touching a kernel; pushbroom cameras; lens distortion; interpolation other than bilinear; colour. */
+typedef struct {
+  float Hl[9], Hr[9];       /* rectified pixel -> source pixel, left and right */
+  float Gl[9], Gr[9];       /* source pixel -> rectified pixel */
+  uint32_t w, h;            /* size of the rectified images */
+  float foc, baseline, doffset, cx, cy;  /* ssrlcv_hip_stereo_points' parameters of the rectified pair */
+  float cam_rot[3];         /* Euler angles of the rectified frame R_n */
+} ssrlcv_rectification;
+int ssrlcv_rectify_cameras_host(const ssrlcv_camera* left, const ssrlcv_camera* right, ssrlcv_rectification* out);
+int ssrlcv_hip_warp_homography_u8(const uint8_t* src, uint32_t srcW, uint32_t srcH, const float* H_host, uint8_t* dst, uint32_t dstW,
+                                  uint32_t dstH, ssrlcv_stream_t stream);
+int ssrlcv_hip_stereo_mask_rectified(float* disparity, uint32_t* cost, uint32_t w, uint32_t h, uint32_t radius, const float* Hl_host,
+                                     const float* Hr_host, uint32_t srcW, uint32_t srcH, ssrlcv_stream_t stream);
+int ssrlcv_hip_matches_apply_homography(ssrlcv_match* matches, uint32_t n, const float* H0_host, const float* H1_host,
+                                        ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -107,4 +107,6 @@ EXPORTED = [
     "ssrlcv_sift_dense_grid", "ssrlcv_sift_dense_max_features", "ssrlcv_hip_sift_dense_workspace_bytes", "ssrlcv_hip_sift_dense_u8",
     "ssrlcv_hip_stereo_workspace_bytes", "ssrlcv_hip_stereo_sad_u8", "ssrlcv_hip_stereo_matches_workspace_bytes",
     "ssrlcv_hip_stereo_matches", "ssrlcv_hip_stereo_points",
+    "ssrlcv_rectify_cameras_host", "ssrlcv_hip_warp_homography_u8", "ssrlcv_hip_stereo_mask_rectified",
+    "ssrlcv_hip_matches_apply_homography",
 ]

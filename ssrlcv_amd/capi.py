@@ -613,6 +613,65 @@ def stereo_points(matches_d, n, foc, baseline, doffset, cx, cy):
     return pts
 
 
+# ------------------------------------------------------------------ rectification
+RECTIFICATION = np.dtype([("Hl", "<f4", (9,)), ("Hr", "<f4", (9,)), ("Gl", "<f4", (9,)), ("Gr", "<f4", (9,)), ("w", "<u4"), ("h", "<u4"),
+                          ("foc", "<f4"), ("baseline", "<f4"), ("doffset", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("cam_rot", "<f4", (3,))])
+assert RECTIFICATION.itemsize == 184
+
+
+def camera_bytes(cam):
+    raw = np.ascontiguousarray(cam).view(np.uint8).reshape(-1)
+    assert raw.size == 80, "one Image::Camera record (80 bytes)"
+    return raw.copy()
+
+
+def homography9(Hm):
+    """9 floats, row-major -> a host float[9] (None passes NULL)"""
+    if Hm is None:
+        return None
+    a = np.ascontiguousarray(Hm, np.float32).reshape(-1)
+    assert a.size == 9, "a homography is 9 floats, row-major"
+    return (c_f32 * 9)(*[float(v) for v in a])
+
+
+def rectify_cameras(cam_l, cam_r):
+    """ssrlcv_rectify_cameras_host of two Image::Camera records (host arithmetic: needs no GPU) -> a RECTIFICATION record."""
+    a, b = camera_bytes(cam_l), camera_bytes(cam_r)
+    out = np.zeros(1, RECTIFICATION)
+    check(LIB.ssrlcv_rectify_cameras_host(a.ctypes.data_as(c_vp), b.ctypes.data_as(c_vp), out.ctypes.data_as(c_vp)))
+    return out[0]
+
+
+def warp_homography(src_d, Hm, out_shape=None):
+    """dst(x, y) = src sampled bilinearly at H (x, y) (ssrlcv_hip_warp_homography_u8); src_d a u8 CUDA tensor (H, W), out_shape
+    (rows, columns) defaults to the source's.  -> u8 CUDA tensor.  Asynchronous on the current stream."""
+    assert src_d.dim() == 2 and src_d.dtype == torch.uint8 and src_d.is_cuda and src_d.is_contiguous()  # read with pitch w
+    sh, sw = src_d.shape
+    dh, dw = (sh, sw) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+    dst = torch.empty((dh, dw), dtype=torch.uint8, device="cuda")
+    check(LIB.ssrlcv_hip_warp_homography_u8(ptr(src_d), c_u32(sw), c_u32(sh), homography9(Hm), ptr(dst), c_u32(dw), c_u32(dh), stream_ptr()))
+    return dst
+
+
+def stereo_mask_rectified(disp_d, cost_d, radius, rect):
+    """Invalidates, in place, the pixels of stereo_disparity's maps whose windows left the source images of the rectification
+    `rect` (ssrlcv_hip_stereo_mask_rectified); cost_d may be None.  Asynchronous on the current stream."""
+    h, w = disp_d.shape
+    assert disp_d.dtype == torch.float32 and disp_d.is_cuda and disp_d.is_contiguous()  # read with pitch w
+    assert cost_d is None or (cost_d.shape == disp_d.shape and cost_d.dtype == torch.int32 and cost_d.is_cuda and cost_d.is_contiguous())
+    check(LIB.ssrlcv_hip_stereo_mask_rectified(ptr(disp_d), ptr(cost_d), c_u32(w), c_u32(h), c_u32(radius), homography9(rect["Hl"]), homography9(rect["Hr"]),
+                                               c_u32(int(rect["w"])), c_u32(int(rect["h"])), stream_ptr()))
+    return disp_d, cost_d
+
+
+def matches_apply_homography(matches_d, n, H0, H1):
+    """keyPoints[k].loc <- Hk loc of the first n Match records, in place (ssrlcv_hip_matches_apply_homography); a None side is
+    left alone; a record that does not map gets invalid = 1.  Asynchronous on the current stream."""
+    assert matches_d.dtype == torch.uint8 and matches_d.is_cuda and matches_d.is_contiguous() and matches_d.numel() >= 40 * n
+    check(LIB.ssrlcv_hip_matches_apply_homography(ptr(matches_d), c_u32(n), homography9(H0), homography9(H1), stream_ptr()))
+    return matches_d
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

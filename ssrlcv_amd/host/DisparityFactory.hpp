@@ -9,12 +9,23 @@
 //   auto matches = factory.generateMatches(disparity, left, right);   // Unity<Match>, gpu: the sparse path's records
 //   auto cloud = PointCloudFactory().stereo_disparity(matches, foc, baseline, doffset);
 //
+// An unrectified pair of pinhole Images goes through rectify() first (include/ssrlcv_hip.h "rectification"):
+//
+//   ptr::value<Image> leftR, rightR;
+//   Rectification rect = factory.rectify(left, right, leftR, rightR);  // from left->camera, right->camera
+//   auto disparity = factory.generateDisparities(leftR, rightR);
+//   factory.maskRectified(disparity, nullptr, rect);                   // the windows that left a source image
+//   auto matches = factory.generateMatches(disparity, left, right);
+//   factory.unrectifyMatches(matches, rect);                           // source pixels: triangulate with the original cameras
+//
 // Pixels keep upstream's memory-state contract: forced onto the gpu for the call, restored to their origin state after it.
 #pragma once
 #include "Image.hpp"
 #include "MatchFactory.hpp"
 
 namespace ssrlcv {
+
+typedef ssrlcv_rectification Rectification;
 
 class DisparityFactory {
   ssrlcv_stereo_params params;
@@ -115,6 +126,77 @@ class DisparityFactory {
     ptr::device<Match> exact((long)count);
     HipSafeCall(ssrlcv_hip_memcpy(exact.get(), staging.get(), (size_t)count * sizeof(Match), 2));
     return ptr::value<Unity<Match>>(exact, (unsigned long)count, gpu);
+  }
+
+  // the pair warped by the homographies of ssrlcv_rectify_cameras_host(left->camera, right->camera): two new single-channel
+  // Images in state gpu with the sources' ids; the returned record holds the homographies and the rectified pair's foc,
+  // baseline, doffset and principal point (PointCloudFactory::stereo_disparity's parameters)
+  Rectification rectify(ptr::value<Image> left, ptr::value<Image> right, ptr::value<Image>& leftOut, ptr::value<Image>& rightOut) {
+    Rectification rect;
+    const int rc = ssrlcv_rectify_cameras_host(reinterpret_cast<const ssrlcv_camera*>(&left->camera),
+                                               reinterpret_cast<const ssrlcv_camera*>(&right->camera), &rect);
+    if (rc != 0) {
+      logger.err << "ERROR: this camera pair cannot be rectified: " + std::string(ssrlcv_hip_status_string(rc));
+      std::exit(-1);
+    }
+    if (left->size.x != rect.w || left->size.y != rect.h || right->size.x != rect.w || right->size.y != rect.h) {
+      logger.err << "ERROR: the images of a pair to rectify have their cameras' size";
+      std::exit(-1);
+    }
+    MemoryState originL, originR;
+    bool keepL, keepR;
+    toGpu(left, originL, keepL);
+    toGpu(right, originR, keepR);
+    const unsigned long n = (unsigned long)rect.w * rect.h;
+    ptr::value<Unity<unsigned char>> pixelsL(nullptr, n, gpu), pixelsR(nullptr, n, gpu);
+    HipSafeCall(ssrlcv_hip_warp_homography_u8(left->pixels->device.get(), rect.w, rect.h, rect.Hl, pixelsL->device.get(), rect.w, rect.h, nullptr));
+    HipSafeCall(ssrlcv_hip_warp_homography_u8(right->pixels->device.get(), rect.w, rect.h, rect.Hr, pixelsR->device.get(), rect.w, rect.h, nullptr));
+    HipCheckError();
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the sources may leave the gpu
+    restore(left, originL, keepL);
+    restore(right, originR, keepR);
+    leftOut = ptr::value<Image>(uint2{rect.w, rect.h}, 1u, pixelsL);
+    rightOut = ptr::value<Image>(uint2{rect.w, rect.h}, 1u, pixelsR);
+    leftOut->id = left->id;
+    rightOut->id = right->id;
+    return rect;
+  }
+
+  // in place on generateDisparities' maps of a pair rectify() made: the pixels whose windows left a source image become
+  // invalid (it only removes pixels); cost may be nullptr
+  void maskRectified(ptr::value<Unity<float>> disparity, ptr::value<Unity<unsigned int>> cost, const Rectification& rect) {
+    MemoryState origin = disparity->getMemoryState(), originC = cost != nullptr ? cost->getMemoryState() : gpu;
+    if (origin != gpu) disparity->setMemoryState(gpu);
+    if (cost != nullptr && originC != gpu) cost->setMemoryState(gpu);
+    HipSafeCall(ssrlcv_hip_stereo_mask_rectified(disparity->device.get(), cost != nullptr ? cost->device.get() : nullptr, rect.w, rect.h,
+                                                 params.radius, rect.Hl, rect.Hr, rect.w, rect.h, nullptr));
+    HipCheckError();
+    if (origin != gpu) disparity->setMemoryState(origin);
+    if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);
+  }
+
+  // in place: generateMatches' records of a rectified pair, through Hl and Hr into source pixels; a record that does not
+  // map back is removed (validateMatches' stable compaction)
+  void unrectifyMatches(ptr::value<Unity<Match>> matches, const Rectification& rect) {
+    MemoryState origin = matches->getMemoryState();
+    if (origin != gpu) matches->setMemoryState(gpu);
+    const uint32_t n = (uint32_t)matches->size();
+    HipSafeCall(ssrlcv_hip_matches_apply_homography(reinterpret_cast<ssrlcv_match*>(matches->device.get()), n, rect.Hl, rect.Hr, nullptr));
+    HipCheckError();
+    const size_t wsBytes = ssrlcv_hip_match_workspace_bytes(n, 1);
+    ptr::device<unsigned char> workspace((long)wsBytes);
+    uint32_t left = 0;
+    HipSafeCall(ssrlcv_hip_compact_matches(SSRLCV_OUT_MATCH, matches->device.get(), n, &left, workspace.get(), wsBytes, nullptr));
+    if (left == 0) {
+      logger.err << "ERROR: no match of the rectified pair maps back into the sources";
+      std::exit(0);
+    }
+    if (left != n) {
+      ptr::device<Match> kept((long)left);
+      HipSafeCall(ssrlcv_hip_memcpy(kept.get(), matches->device.get(), (size_t)left * sizeof(Match), 2));
+      matches->setData(kept, left, gpu);
+    }
+    if (origin != gpu) matches->setMemoryState(origin);
   }
 };
 

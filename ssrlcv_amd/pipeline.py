@@ -162,6 +162,43 @@ def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step
     return pts, matches, n, disp
 
 
+def rectify_pair(left, right, cam_l, cam_r):
+    """Two views (u8 CUDA tensors (H, W)) of a converging pinhole pair and their Image::Camera records -> (left_r, right_r, rect):
+    the pair warped by the homographies of capi.rectify_cameras (include/ssrlcv_hip.h "rectification"), row-aligned, with
+    rect's foc, baseline, doffset, cx, cy as capi.stereo_points' parameters."""
+    rect = capi.rectify_cameras(cam_l, cam_r)
+    shape = (int(rect["h"]), int(rect["w"]))
+    assert tuple(left.shape) == shape and tuple(right.shape) == shape, "the images have the cameras' size"
+    return capi.warp_homography(left, rect["Hl"], shape), capi.warp_homography(right, rect["Hr"], shape), rect
+
+
+def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, **disparity_args):
+    """Unrectified pair -> dense cloud in the world frame of triangulate()'s clouds: rectify_pair, stereo_disparity, the mask
+    of the windows that left a source image (capi.stereo_mask_rectified), capi.stereo_matches, the records mapped back into
+    source pixels (capi.matches_apply_homography), compacted, then capi.matchset_from_matches and the two-view triangulation
+    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args as for stereo_cloud.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
+    matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
+    if "want_cost" in disparity_args:
+        raise TypeError("stereo_cloud_cameras computes no cost map: call stereo_disparity for one")
+    left_r, right_r, rect = rectify_pair(left, right, cam_l, cam_r)
+    disp, _ = stereo_disparity(left_r, right_r, want_cost=False, **disparity_args)
+    capi.stereo_mask_rectified(disp, None, disparity_args.get("radius", 4), rect)
+    matches, n = capi.stereo_matches(disp, step, 0, 1)
+    capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
+    if n:
+        n = capi.compact_matches(capi.OUT_MATCH, matches, n, capi.match_workspace(n, 1))   # a record that did not map back
+        matches = matches[: 40 * n]
+    pts = torch.zeros((0, 3), dtype=torch.float32, device="cuda")
+    if n:
+        kp_d, mm_d, _ = capi.matchset_from_matches(capi.OUT_MATCH, matches, n)
+        # the two 80-byte records as bytes (numpy would repack a padded record dtype when concatenating)
+        cameras = np.concatenate([capi.camera_bytes(cam_l), capi.camera_bytes(cam_r)])
+        # triangulate()'s two-view path on the device copies (the dense match set never travels to the host)
+        b_d, l_d = capi.generate_bundles(mm_d, kp_d, n, capi.to_dev(cameras), 2, 2 * n)
+        pts = capi.triangulate(l_d, b_d, n, nview=False)[0].view(-1, 3)
+    return pts, matches, n, disp, rect
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:
