@@ -1,7 +1,12 @@
 """generateMatchesExhaustive's merge on the device (csrc/merge.hip, ssrlcv_hip_merge_matches; src/MatchFactory.cu:943-1020):
 the round-wise resolution of the seeds must return exactly what upstream's single-threaded walk returns (mode 1 of the
 host test hook) -- on consistent scenes, on scenes where many seeds of an image share targets (the conflicts the rounds
-exist for), and on chains of conflicts longer than the round limit (the in-order tail)."""
+exist for), and on chains of conflicts longer than the round limit (the in-order tail).
+
+The reference here shares the walk's text: walk(), for_each_cleared() and commit() of csrc/host_merge.cpp are those of
+csrc/merge.hip, so a mistake made once in transcribing upstream is in both, and `random_pairs` hardly ever makes a walk take a
+second hop.  tests/test_gpu_merge_edges.py holds the device to a plain Python restatement (tests/merge_ref.py) on cases built
+to reach the multi-hop walk, every grid shape and the tail (tests/merge_cases.py)."""
 import numpy as np
 import pytest
 import torch
