@@ -332,7 +332,13 @@ int ssrlcv_hip_match_ratio_u8x128(const ssrlcv_sift_feature* query, uint32_t num
                                   void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* validateMatches (src/MatchFactory.cu:32-108): stable removal of invalid entries (thrust::remove_if).  In place;
- * *count_host receives the survivors.  Synchronous (returns after the count is on the host, like the reference). */
+ * *count_host receives the survivors.  Synchronous (returns after the count is on the host, like the reference).
+ * A DMatch or Match is invalid when its `invalid` byte is not 0 (any value, not only 1); a uint2_pair when a.x == b.x and
+ * a.y == b.y (a pair that shares one of the two is kept).  The survivors are moved whole, in input order, to the front of
+ * the list; the records behind them, [count, numMatches), are left as they were, and nothing outside the list is written.
+ * workspace: numMatches * sizeof(record) + 256 + 4 * (4 * ceil(numMatches / 2048) + 3) bytes are enough (a workspace of
+ * ssrlcv_hip_match_workspace_bytes / _match2_workspace_bytes for the call that made the list is too); nothing is written
+ * past that many bytes, one byte less is SSRLCV_ERR_WORKSPACE, and a workspace may hold anything on entry. */
 int ssrlcv_hip_compact_matches(int outKind, void* matches, uint32_t numMatches, uint32_t* count_host, void* workspace,
                                size_t workspaceBytes, ssrlcv_stream_t stream);
 
@@ -340,7 +346,10 @@ int ssrlcv_hip_compact_matches(int outKind, void* matches, uint32_t numMatches, 
  * number of survivors, which are left at the front of `matches`.  For callers that queue many pairs and read all the
  * counts after one synchronisation (the per-pair D2H count of the call above was a stall per image pair).
  * outKind SSRLCV_OUT_DMATCH or SSRLCV_OUT_UINT2_PAIR; the 40-byte Match is not a multiple of the 16-byte words the
- * counted copy moves: SSRLCV_ERR_UNSUPPORTED (use ssrlcv_hip_compact_matches). */
+ * counted copy moves, and neither is a list that does not begin on a 16-byte boundary: with numMatches > 0 either is
+ * SSRLCV_ERR_UNSUPPORTED, nothing touched (use ssrlcv_hip_compact_matches).  numMatches == 0 is answered first by both
+ * calls: SSRLCV_OK, a count of 0, list and workspace untouched, whatever the kind, the alignment and workspaceBytes.
+ * Rules, order, the records behind the survivors and the workspace as above. */
 int ssrlcv_hip_compact_matches_async(int outKind, void* matches, uint32_t numMatches, uint32_t* count_dev, void* workspace,
                                      size_t workspaceBytes, ssrlcv_stream_t stream);
 
@@ -396,7 +405,11 @@ int ssrlcv_hip_sort_keys_u32(const uint32_t* keys, uint32_t n, uint32_t* perm, v
  * location} for every member {image, feature index} of the merged MatchSet, gathered on the device.  members: device
  * array of numMembers {x = image, y = feature}; features_host: HOST array of numImages device pointers.  keyPoints must
  * be 16-byte aligned (any device allocation is; a sub-array must start at an even byte offset / 16): each 16-byte element,
- * padding included, is written with one store -- SSRLCV_ERR_INVALID_ARG otherwise. */
+ * padding included (the 4 bytes behind parentId are zero), is written with one store -- SSRLCV_ERR_INVALID_ARG otherwise.
+ * A member that names no image (x >= numImages), no feature of its image (y >= numFeatures_host[x]) or an image whose
+ * array pointer is NULL (its count is then not read) gets parentId = x and the location (0, 0): upstream indexes its
+ * arrays with such a member unchecked, so there is nothing to reproduce, and no array is read out of bounds here.
+ * numMembers == 0: SSRLCV_OK, nothing touched.  One launch per 64 images over the same member list. */
 int ssrlcv_hip_keypoints_from_members(const ssrlcv_uint2* members, uint32_t numMembers,
                                       const ssrlcv_sift_feature* const* features_host, const uint32_t* numFeatures_host,
                                       uint32_t numImages, ssrlcv_keypoint* keyPoints, ssrlcv_stream_t stream);
@@ -474,8 +487,9 @@ int ssrlcv_hip_minmax(const float* in, size_t n, float* minmax, ssrlcv_stream_t 
 int ssrlcv_hip_normalize(float* data, size_t n, const float* minmax, ssrlcv_stream_t stream);
 /* Octave::normalize + convertToDOG/subtractImages (src/FeatureFactory.cu:327-331,404-440,842-845) fused:
  * dog[b] = N(level[b+1]) - N(level[b]), b = 0..4, with N(x) = (x-min_b)/(max_b-min_b); levelMinMax = 6 x {min,max};
- * dogMinMax (nullable, 5 x {min,max}, caller-initialised) accumulates the min/max that findKeyPoints' second
- * normalisation (src/FeatureFactory.cu:472) needs. */
+ * dogMinMax (nullable, 5 x {min,max}, caller-initialised to {FLT_MAX,-FLT_MAX}) accumulates the min/max that findKeyPoints'
+ * second normalisation (src/FeatureFactory.cu:472) needs.  Pixels are moved four at a time: w * h % 4 != 0 returns
+ * SSRLCV_ERR_INVALID_ARG (every level of a plan is a multiple of 4 pixels), and the levels must be 16-byte aligned. */
 int ssrlcv_hip_dog_normalised_sub(const float* const levels_host[6], const float* levelMinMax, uint32_t w, uint32_t h,
                                   float* const dog_host[5], float* dogMinMax, ssrlcv_stream_t stream);
 

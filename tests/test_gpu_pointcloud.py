@@ -4,6 +4,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import glue_cases as G
 import helpers as H
 import pointcloud_cases as C
 
@@ -136,12 +137,53 @@ def test_pushbroom_bundles_match_oracle(capi, oracle_lib):
     assert np.array_equal(capi.to_host(b_d, H.BUNDLE, nb)["index"], mm["index"])
 
 
+def test_pushbroom_bundles_match_oracle_with_a_camera_of_its_own_each(capi, oracle_lib):
+    """every camera with its own altitude, foc, gsd, dpix and an odd size (the centre is a half pixel); rolls of 0, below 0 and
+    above; key points at pixel 0, at size - 1 and at the exact centre of every camera among random ones"""
+    rng = np.random.default_rng(10)
+    ncam, nb = 7, 3001
+    pb = np.zeros(ncam, H.PUSHBROOM)
+    pb["axis_radius"] = 6371.0
+    pb["roll"] = [0.0, -7.5, 3.25, -0.001, 8.0, -12.0, 0.0]
+    pb["altitude"] = [400.0, 412.5, 389.0, 705.0, 400.25, 550.0, 617.0]
+    pb["foc"] = [0.859311, 0.9, 0.75, 1.2, 0.859311, 0.5, 2.0]
+    pb["fov"] = 0.0418879
+    pb["gsd"] = [0.006, 0.0055, 0.0071, 0.01, 0.003, 0.0065, 0.0049]
+    pb["dpix"] = np.array([3.5e-5, 3.4e-5, 4.0e-5, 5.5e-5, 3.5e-5, 2.0e-5, 6.5e-5], np.float32)[:, None] * np.array([1.0, 1.25], np.float32)
+    pb["size"] = [[8191, 8191], [4097, 8193], [8193, 4095], [1001, 999], [8191, 2049], [3, 5], [6001, 7001]]
+    assert (pb["size"] % 2 == 1).all() and (pb["roll"] == 0).any() and (pb["roll"] < 0).any()
+    mm = np.zeros(nb, H.MULTIMATCH)
+    mm["numKeyPoints"] = rng.integers(2, 5, nb)
+    mm["index"] = np.concatenate([[0], np.cumsum(mm["numKeyPoints"])[:-1]])
+    nk = int(mm["numKeyPoints"].sum())
+    kp = np.zeros(nk, H.KEYPOINT)
+    kp["parentId"] = rng.integers(0, ncam, nk)
+    size = pb["size"][kp["parentId"]].astype(np.float32)
+    kp["loc"] = (rng.random((nk, 2)) * size).astype(np.float32)
+    for c in range(ncam):                      # pixel 0, size - 1 and the centre, in both coordinates and mixed
+        mine = np.flatnonzero(kp["parentId"] == c)[:6]
+        s = pb["size"][c].astype(np.float32)
+        kp["loc"][mine] = [[0, 0], s - 1, s / np.float32(2.0), [0, s[1] - 1], [s[0] / np.float32(2.0), 0], [s[0] - 1, s[1] / np.float32(2.0)]]
+    b_d, l_d = capi.generate_pushbroom_bundles(capi.to_dev(mm), capi.to_dev(kp), nb, capi.to_dev(pb), ncam, nk)
+    ob = np.zeros(nb, H.BUNDLE)
+    ol = np.zeros(nk, H.LINE)
+    oracle_lib.oracle_generate_pushbroom_bundles(ctypes.c_uint32(nb), H.P(mm), H.P(kp), H.P(pb), H.P(ob), H.P(ol))
+    gl = capi.to_host(l_d, H.LINE, nk)
+    for name in ("vec", "pnt"):
+        ne = (H.bits(gl[name]) != H.bits(ol[name])).any(1)
+        assert not ne.any(), (name, int(ne.sum()), kp[ne][:4], gl[name][ne][:4], ol[name][ne][:4])
+    gb = capi.to_host(b_d, H.BUNDLE, nb)
+    assert np.array_equal(gb["index"], mm["index"]) and np.array_equal(gb["numLines"], mm["numKeyPoints"]) and (gb["invalid"] == 0).all()
+
+
 # ---- filters between triangulation and BA on the device (csrc/filter.hip) ------------------------------------------------
 @pytest.mark.parametrize("n,jump", [(1, 10), (9, 10), (10, 10), (1023, 10), (13534, 10), (21177, 10), (100000, 3), (1 << 20, 10),
-                                    (3100000, 10), (5000, 1)])
+                                    (3100000, 10), (5000, 1)] + G.cutoff_params())
 def test_sample_cutoff_is_the_hosts_sequential_sum(capi, oracle_lib, n, jump):
     """sigma x std of every jump-th error: the device chain must be the host loop's float sums bit for bit
-    (src/PointCloudFactory.cu:3121-3156)."""
+    (src/PointCloudFactory.cu:3121-3156).  glue_cases.cutoff_params: sample counts either side of the float4 body / scalar
+    tail and of the 1024-sample chunks of the double buffer (1 .. 5, 1023 .. 1025, 2047 .. 2049, 3075), each with every error
+    a sample and with every seventh, numErrors no multiple of 7."""
     import torch
     rng = np.random.default_rng(n + jump)
     errs = (rng.random(n).astype(np.float32) ** 4 * np.float32(50.0)).astype(np.float32)   # skewed, like squared line gaps
