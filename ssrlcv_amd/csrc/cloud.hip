@@ -17,6 +17,7 @@
 // Everything is keyed by (d2, j), so the result does not depend on h, on the order inside a cell or on scheduling.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include "align256.h"
 #include "device_math.h"
 #include "scan_lookback.h"
 #include "ssrlcv_hip.h"
@@ -47,13 +48,11 @@ struct CloudHdr {
 constexpr size_t kHdrBytes = 256;
 static_assert(sizeof(CloudHdr) <= kHdrBytes, "CloudHdr");
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline uint32_t table_log2(uint32_t n) {
   uint32_t l = 1;
   while ((1ull << l) < 2ull * n) ++l;
   return l;
 }
-inline uint32_t scan_tiles_for(uint32_t n) { return svs::scan_tiles<8>(n); }
 
 struct KnnLayout {
   size_t keys, start, slot, rank, sorted, far, scan, total;
@@ -70,7 +69,7 @@ inline KnnLayout knn_layout(uint32_t n) {
   L.sorted = L.rank + align256((size_t)n * 4);
   L.far = L.sorted + align256((size_t)n * 16);
   L.scan = L.far + align256((size_t)n * 4);
-  L.total = L.scan + svs::workspace_bytes<1>(scan_tiles_for(L.T + 1));
+  L.total = L.scan + svs::workspace_bytes<1>(svs::scan_tiles<8>(L.T + 1));
   return L;
 }
 
@@ -418,7 +417,7 @@ inline FilterLayout filter_layout(uint32_t n) {
   L.partial = kHdrBytes;
   L.mean = L.partial + align256((size_t)kStatBlocks * 3 * sizeof(double));
   L.scan = L.mean + align256((size_t)n * sizeof(float));
-  L.total = L.scan + svs::workspace_bytes<1>(scan_tiles_for(n));
+  L.total = L.scan + svs::workspace_bytes<1>(svs::scan_tiles<8>(n));
   return L;
 }
 
@@ -497,11 +496,10 @@ __global__ __launch_bounds__(kThreads) void k_filter_compact(const ssrlcv_float3
                                                              ssrlcv_float3* __restrict__ pOut, uint32_t* __restrict__ idxOut,
                                                              float* __restrict__ nOut, uint32_t* __restrict__ count,
                                                              svs::TileScan<1> ts) {
-  constexpr uint32_t kTile = kThreads * kItems;
   const double t = stats[2];
-  for (uint32_t tile = svs::next_tile(ts.counter); tile < ts.numTiles; tile = svs::next_tile(ts.counter)) {
-    const uint32_t base = tile * kTile + threadIdx.x * kItems;
-    uint32_t keep = 0, mine[1] = {0};
+  uint32_t keep;
+  auto read = [&](uint32_t base, uint32_t (&mine)[1]) {
+    keep = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kItems; ++j) {
       if (base + j < n) {
@@ -510,10 +508,9 @@ __global__ __launch_bounds__(kThreads) void k_filter_compact(const ssrlcv_float3
       }
     }
     mine[0] = __popc(keep);
-    uint32_t excl[1], total[1], prefix[1];
-    svs::block_exclusive<1>(mine, excl, total);
-    svs::tile_prefix<1>(ts, tile, total, prefix);
-    uint32_t o = prefix[0] + excl[0];
+  };
+  auto write = [&](uint32_t base, const uint32_t (&at)[1]) {
+    uint32_t o = at[0];
 #pragma unroll
     for (uint32_t j = 0; j < kItems; ++j) {
       if (keep & (1u << j)) {
@@ -528,8 +525,9 @@ __global__ __launch_bounds__(kThreads) void k_filter_compact(const ssrlcv_float3
         ++o;
       }
     }
-    if (tile + 1 == ts.numTiles && threadIdx.x == kThreads - 1) *count = prefix[0] + total[0];
-  }
+  };
+  auto finish = [&](const uint32_t (&totals)[1]) { *count = totals[0]; };
+  svs::for_each_tile<1, kItems>(ts, read, write, finish);
 }
 
 // ---- normals: covariance of the k + 1 points about their mean (float64), cyclic Jacobi, smallest eigenvector -------
@@ -706,12 +704,8 @@ int ssrlcv_hip_neighbor_distance_filter(const ssrlcv_float3* points, uint32_t nu
   hipLaunchKernelGGL(k_mean_stats, dim3(kStatBlocks), dim3(kThreads), 0, st, dist2, numPoints, k, mean, partial, stats, 1);
   hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(kThreads), 0, st, partial, stats, sigma, 1);
   SSRLCV_LAUNCH_CHECK();
-  const uint32_t tiles = scan_tiles_for(numPoints);
-  SSRLCV_HIP_TRY(hipMemsetAsync(ws + L.scan, 0, svs::workspace_bytes<1>(tiles), st));
-  const svs::TileScan<1> ts = svs::make_tile_scan<1>(ws + L.scan, tiles);
-  hipLaunchKernelGGL(k_filter_compact, dim3(tiles < 2048u ? tiles : 2048u), dim3(kThreads), 0, st, points, numPoints, mean,
-                     (const double*)stats, normalsIn, pointsOut, indexOut, normalsOut, count, ts);
-  SSRLCV_LAUNCH_CHECK();
+  SSRLCV_HIP_TRY(svs::launch_tiles<1>(k_filter_compact, svs::scan_tiles<kItems>(numPoints), ws + L.scan, st, points, numPoints, mean,
+                                       (const double*)stats, normalsIn, pointsOut, indexOut, normalsOut, count));
   return SSRLCV_OK;
 }
 

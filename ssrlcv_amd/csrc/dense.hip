@@ -26,6 +26,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "ssrlcv_hip.h"
+#include "align256.h"
 #include "device_math.h"
 #include "scan_lookback.h"
 #include "sift_sampling.h"
@@ -72,7 +73,6 @@ int dense_geom(uint32_t w, uint32_t h, const ssrlcv_dense_params* p, DenseGeom* 
   return SSRLCV_OK;
 }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // workspace: {min, max} | L float[w h] | polar float2[w h] | bin u8[w h] | weights float[(2 wo + 1)^2] |
 //            thetas float[n maxO] | counts u32[n + 1] | offsets u32[n + 1] | scan descriptors        (n = nx ny)
@@ -81,13 +81,13 @@ DenseLayout dense_layout(const DenseGeom& g, uint32_t maxO) {
   const size_t px = (size_t)g.w * g.h, n = (size_t)g.nx * g.ny, side = 2 * g.wo + 1;
   size_t at = 0;
   L.mm = at;      at += 256;
-  L.level = at;   at += up256(px * 4);
-  L.polar = at;   at += up256(px * 8);
-  L.bin = at;     at += up256(px);
-  L.wtab = at;    at += up256(side * side * 4);
-  L.thetas = at;  at += up256(n * maxO * 4);
-  L.cnt = at;     at += up256((n + 1) * 4);
-  L.off = at;     at += up256((n + 1) * 4);
+  L.level = at;   at += align256(px * 4);
+  L.polar = at;   at += align256(px * 8);
+  L.bin = at;     at += align256(px);
+  L.wtab = at;    at += align256(side * side * 4);
+  L.thetas = at;  at += align256(n * maxO * 4);
+  L.cnt = at;     at += align256((n + 1) * 4);
+  L.off = at;     at += align256((n + 1) * 4);
   L.scan = at;    at += svs::workspace_bytes<1>(svs::scan_tiles<8>((uint32_t)(n + 1)));
   L.total = at;
   return L;

@@ -86,12 +86,9 @@ __global__ __launch_bounds__(svs::kThreads) void k_filter_matchset(const ssrlcv_
                                                                    uint32_t n, ssrlcv_multimatch* __restrict__ mmOut,
                                                                    ssrlcv_keypoint* __restrict__ kpOut, uint32_t* __restrict__ counts,
                                                                    svs::TileScan<3> ts) {
-  constexpr uint32_t kTile = svs::kThreads * kItems;
-  for (uint32_t tile = svs::next_tile(ts.counter); tile < ts.numTiles; tile = svs::next_tile(ts.counter)) {
-    const uint32_t base = tile * kTile + threadIdx.x * kItems;
-    uint32_t lines[kItems];
-    bool keep[kItems];
-    uint32_t mine[3] = {0, 0, 0};
+  uint32_t lines[kItems];
+  bool keep[kItems];
+  auto read = [&](uint32_t base, uint32_t (&mine)[3]) {
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
       lines[j] = 0;
@@ -105,10 +102,9 @@ __global__ __launch_bounds__(svs::kThreads) void k_filter_matchset(const ssrlcv_
       mine[1] += keep[j] ? lines[j] : 0u;
       mine[2] += lines[j];
     }
-    uint32_t excl[3], total[3], prefix[3];
-    svs::block_exclusive<3>(mine, excl, total);
-    svs::tile_prefix<3>(ts, tile, total, prefix);
-    uint32_t k_bundle = prefix[0] + excl[0], k_adjust = prefix[1] + excl[1], k_keypnt = prefix[2] + excl[2];
+  };
+  auto write = [&](uint32_t, const uint32_t (&at)[3]) {
+    uint32_t k_bundle = at[0], k_adjust = at[1], k_keypnt = at[2];
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
       if (keep[j]) {
@@ -122,31 +118,30 @@ __global__ __launch_bounds__(svs::kThreads) void k_filter_matchset(const ssrlcv_
       }
       k_keypnt += lines[j];
     }
-    if (tile == ts.numTiles - 1 && threadIdx.x == 0) {
-      counts[0] = prefix[0] + total[0];  // bundles kept
-      counts[1] = prefix[1] + total[1];  // key points kept
-      counts[2] = prefix[2] + total[2];  // key points of the input (all lines)
-    }
-  }
+  };
+  auto finish = [&](const uint32_t (&totals)[3]) {
+    counts[0] = totals[0];  // bundles kept
+    counts[1] = totals[1];  // key points kept
+    counts[2] = totals[2];  // key points of the input (all lines)
+  };
+  svs::for_each_tile<3, kItems>(ts, read, write, finish);
 }
-
-inline uint32_t filter_tiles(uint32_t n) { return (n + svs::kThreads * kItems - 1) / (svs::kThreads * kItems); }
 
 // ---- the two-view bundles of one image pair out of an N-view MatchSet, as a two-camera MatchSet (round 5) -----------------------
 // BundleAdjustTwoView works on a 2-view MatchSet; in the N-view flows (config[3]) the sweep is run on the bundles of the
 // first image pair.  One look-back pass: a multi-match is taken when it has exactly two key points and they belong to
 // images a and b (in that order, which is the order generateMatchesExhaustive writes them); output j = {2, 2 j} with the
 // two key points re-labelled 0 / 1, order kept.
+// a ssrlcv_keypoint moved as one 16-byte value, its padding included (parentId is word 0)
+typedef uint32_t KeyPointWord __attribute__((ext_vector_type(4), aligned(8), may_alias));
+static_assert(sizeof(KeyPointWord) == sizeof(ssrlcv_keypoint) && alignof(KeyPointWord) <= alignof(ssrlcv_keypoint), "KeyPointWord");
 __global__ __launch_bounds__(svs::kThreads) void k_select_pair(const ssrlcv_multimatch* __restrict__ mm, const ssrlcv_keypoint* __restrict__ kp,
                                                                uint32_t n, uint32_t numKeyPoints, int imageA, int imageB,
                                                                ssrlcv_multimatch* __restrict__ mmOut, ssrlcv_keypoint* __restrict__ kpOut,
                                                                uint32_t* __restrict__ count, svs::TileScan<1> ts) {
-  constexpr uint32_t kTile = svs::kThreads * kItems;
-  for (uint32_t tile = svs::next_tile(ts.counter); tile < ts.numTiles; tile = svs::next_tile(ts.counter)) {
-    const uint32_t base = tile * kTile + threadIdx.x * kItems;
-    bool keep[kItems];
-    uint32_t first[kItems];
-    uint32_t mine[1] = {0};
+  bool keep[kItems];
+  uint32_t first[kItems];
+  auto read = [&](uint32_t base, uint32_t (&mine)[1]) {
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
       keep[j] = false;
@@ -159,26 +154,26 @@ __global__ __launch_bounds__(svs::kThreads) void k_select_pair(const ssrlcv_mult
       }
       mine[0] += keep[j] ? 1u : 0u;
     }
-    uint32_t excl[1], total[1], prefix[1];
-    svs::block_exclusive<1>(mine, excl, total);
-    svs::tile_prefix<1>(ts, tile, total, prefix);
-    uint32_t at = prefix[0] + excl[0];
+  };
+  auto write = [&](uint32_t, const uint32_t (&start)[1]) {
+    uint32_t at = start[0];
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
       if (!keep[j]) continue;
-      ssrlcv_keypoint k0 = kp[first[j]], k1 = kp[first[j] + 1u];
-      k0.parentId = 0;
-      k1.parentId = 1;
-      kpOut[2u * at] = k0;
-      kpOut[2u * at + 1u] = k1;
+      KeyPointWord k0 = *(const KeyPointWord*)(kp + first[j]), k1 = *(const KeyPointWord*)(kp + first[j] + 1u);
+      k0.x = 0u;  // parentId
+      k1.x = 1u;
+      *(KeyPointWord*)(kpOut + 2u * at) = k0;
+      *(KeyPointWord*)(kpOut + 2u * at + 1u) = k1;
       ssrlcv_multimatch m;
       m.numKeyPoints = 2u;
       m.index = (int)(2u * at);
       mmOut[at] = m;
       ++at;
     }
-    if (tile == ts.numTiles - 1 && threadIdx.x == 0) *count = prefix[0] + total[0];
-  }
+  };
+  auto finish = [&](const uint32_t (&totals)[1]) { *count = totals[0]; };
+  svs::for_each_tile<1, kItems>(ts, read, write, finish);
 }
 
 }  // namespace
@@ -193,9 +188,9 @@ int ssrlcv_hip_error_sample_cutoff(const float* errors, uint32_t numErrors, uint
   return SSRLCV_OK;
 }
 
-size_t ssrlcv_hip_filter_workspace_bytes(uint32_t numBundles) { return svs::workspace_bytes<3>(filter_tiles(numBundles ? numBundles : 1)); }
+size_t ssrlcv_hip_filter_workspace_bytes(uint32_t numBundles) { return svs::workspace_bytes<3>(svs::scan_tiles<kItems>(numBundles ? numBundles : 1)); }
 
-size_t ssrlcv_hip_select_pair_workspace_bytes(uint32_t numMatches) { return svs::workspace_bytes<1>(filter_tiles(numMatches ? numMatches : 1)); }
+size_t ssrlcv_hip_select_pair_workspace_bytes(uint32_t numMatches) { return svs::workspace_bytes<1>(svs::scan_tiles<kItems>(numMatches ? numMatches : 1)); }
 
 int ssrlcv_hip_select_pair_bundles(const ssrlcv_multimatch* matches, const ssrlcv_keypoint* keyPoints, uint32_t numMatches,
                                    uint32_t numKeyPoints, int imageA, int imageB, ssrlcv_multimatch* matchesOut,
@@ -205,14 +200,10 @@ int ssrlcv_hip_select_pair_bundles(const ssrlcv_multimatch* matches, const ssrlc
   const hipStream_t st = (hipStream_t)stream;
   if (numMatches == 0) return (int)hipMemsetAsync(count, 0, 4, st);
   if (!matches || !keyPoints || !matchesOut || !keyPointsOut || !workspace) return SSRLCV_ERR_INVALID_ARG;
-  const uint32_t tiles = filter_tiles(numMatches);
+  const uint32_t tiles = svs::scan_tiles<kItems>(numMatches);
   if (workspaceBytes < svs::workspace_bytes<1>(tiles)) return SSRLCV_ERR_WORKSPACE;
-  SSRLCV_HIP_TRY(hipMemsetAsync(workspace, 0, svs::workspace_bytes<1>(tiles), st));
-  const svs::TileScan<1> ts = svs::make_tile_scan<1>(workspace, tiles);
-  const unsigned blocks = tiles < 2048u ? tiles : 2048u;
-  hipLaunchKernelGGL(k_select_pair, dim3(blocks), dim3(svs::kThreads), 0, st, matches, keyPoints, numMatches, numKeyPoints, imageA, imageB,
-                     matchesOut, keyPointsOut, count, ts);
-  SSRLCV_LAUNCH_CHECK();
+  SSRLCV_HIP_TRY(svs::launch_tiles<1>(k_select_pair, tiles, workspace, st, matches, keyPoints, numMatches, numKeyPoints, imageA, imageB,
+                                       matchesOut, keyPointsOut, count));
   return SSRLCV_OK;
 }
 
@@ -223,14 +214,9 @@ int ssrlcv_hip_filter_matchset(const ssrlcv_bundle* bundles, const ssrlcv_keypoi
   const hipStream_t st = (hipStream_t)stream;
   if (numBundles == 0) return (int)hipMemsetAsync(counts, 0, 12, st);
   if (!bundles || !keyPoints || !matchesOut || !keyPointsOut || !workspace) return SSRLCV_ERR_INVALID_ARG;
-  const uint32_t tiles = filter_tiles(numBundles);
+  const uint32_t tiles = svs::scan_tiles<kItems>(numBundles);
   if (workspaceBytes < svs::workspace_bytes<3>(tiles)) return SSRLCV_ERR_WORKSPACE;
-  SSRLCV_HIP_TRY(hipMemsetAsync(workspace, 0, svs::workspace_bytes<3>(tiles), st));
-  const svs::TileScan<3> ts = svs::make_tile_scan<3>(workspace, tiles);
-  const unsigned blocks = tiles < 2048u ? tiles : 2048u;
-  hipLaunchKernelGGL(k_filter_matchset, dim3(blocks), dim3(svs::kThreads), 0, st, bundles, keyPoints, numBundles, matchesOut, keyPointsOut,
-                     counts, ts);
-  SSRLCV_LAUNCH_CHECK();
+  SSRLCV_HIP_TRY(svs::launch_tiles<3>(k_filter_matchset, tiles, workspace, st, bundles, keyPoints, numBundles, matchesOut, keyPointsOut, counts));
   return SSRLCV_OK;
 }
 

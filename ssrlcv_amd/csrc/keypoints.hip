@@ -2354,17 +2354,14 @@ __global__ __launch_bounds__(64) void k_x_descriptors(uint32_t n, uint32_t start
 }
 // thrust::remove / remove_if in place, order kept, one pass: a tile's kept elements land at or below where they were read,
 // inside the regions of tiles that loaded their elements before they published the aggregate this tile waited for
+constexpr int kRemoveItems = 4;
 template <typename T, typename Drop>
 __global__ __launch_bounds__(svs::kThreads) void k_x_remove_if(T* data, uint32_t n, Drop drop, uint32_t* __restrict__ count, svs::TileScan<1> ts) {
-  constexpr int ITEMS = 4;
-  constexpr uint32_t kTile = svs::kThreads * ITEMS;
-  for (uint32_t tile = svs::next_tile(ts.counter); tile < ts.numTiles; tile = svs::next_tile(ts.counter)) {
-    const uint32_t base = tile * kTile + threadIdx.x * ITEMS;
-    T v[ITEMS];
-    bool keep[ITEMS];
-    uint32_t mine[1] = {0};
+  T v[kRemoveItems];
+  bool keep[kRemoveItems];
+  auto read = [&](uint32_t base, uint32_t (&mine)[1]) {
 #pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
+    for (int j = 0; j < kRemoveItems; ++j) {
       keep[j] = false;
       if (base + j < n) {
         v[j] = data[base + j];
@@ -2372,15 +2369,15 @@ __global__ __launch_bounds__(svs::kThreads) void k_x_remove_if(T* data, uint32_t
       }
       mine[0] += keep[j] ? 1u : 0u;
     }
-    uint32_t excl[1], total[1], prefix[1];
-    svs::block_exclusive<1>(mine, excl, total);  // (its barriers: every element of the tile is in registers before a store)
-    svs::tile_prefix<1>(ts, tile, total, prefix);
-    uint32_t at = prefix[0] + excl[0];
+  };
+  auto write = [&](uint32_t, const uint32_t (&start)[1]) {  // (the walk's barriers: every element of the tile is in registers before a store)
+    uint32_t at = start[0];
 #pragma unroll
-    for (int j = 0; j < ITEMS; ++j)
+    for (int j = 0; j < kRemoveItems; ++j)
       if (keep[j]) data[at++] = v[j];
-    if (tile == ts.numTiles - 1 && threadIdx.x == 0) *count = prefix[0] + total[0];
-  }
+  };
+  auto finish = [&](const uint32_t (&totals)[1]) { *count = totals[0]; };
+  svs::for_each_tile<1, kRemoveItems>(ts, read, write, finish);
 }
 struct DropMinusOne { __device__ bool operator()(int v) const { return v == -1; } };
 struct DropFlagged { __device__ bool operator()(const ssrlcv_sskeypoint& k) const { return k.discard != 0; } };
@@ -2390,12 +2387,9 @@ int x_remove_if(T* data, uint32_t n, uint32_t* count_dev, void* workspace, size_
   if (!count_dev) return SSRLCV_ERR_INVALID_ARG;
   if (n == 0) return (int)hipMemsetAsync(count_dev, 0, 4, st);
   if (!data || !workspace) return SSRLCV_ERR_INVALID_ARG;
-  const uint32_t tiles = (n + svs::kThreads * 4 - 1) / (svs::kThreads * 4);
+  const uint32_t tiles = svs::scan_tiles<kRemoveItems>(n);
   if (workspaceBytes < svs::workspace_bytes<1>(tiles)) return SSRLCV_ERR_WORKSPACE;
-  SSRLCV_HIP_TRY(hipMemsetAsync(workspace, 0, svs::workspace_bytes<1>(tiles), st));
-  hipLaunchKernelGGL((k_x_remove_if<T, Drop>), dim3(tiles < 2048u ? tiles : 2048u), dim3(svs::kThreads), 0, st, data, n, Drop(), count_dev,
-                     svs::make_tile_scan<1>(workspace, tiles));
-  SSRLCV_LAUNCH_CHECK();
+  SSRLCV_HIP_TRY(svs::launch_tiles<1>(k_x_remove_if<T, Drop>, tiles, workspace, st, data, n, Drop(), count_dev));
   return SSRLCV_OK;
 }
 inline unsigned xb(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -2410,7 +2404,7 @@ int ssrlcv_hip_find_extrema(uint32_t w, uint32_t h, const float* pixelsUpper, co
   SSRLCV_LAUNCH_CHECK();
   return SSRLCV_OK;
 }
-size_t ssrlcv_hip_compact_workspace_bytes(uint32_t n) { return svs::workspace_bytes<1>((n + svs::kThreads * 4 - 1) / (svs::kThreads * 4) + 1); }
+size_t ssrlcv_hip_compact_workspace_bytes(uint32_t n) { return svs::workspace_bytes<1>(svs::scan_tiles<kRemoveItems>(n) + 1); }
 int ssrlcv_hip_compact_addresses(int* addresses, uint32_t n, uint32_t* count_dev, void* workspace, size_t workspaceBytes,
                                  ssrlcv_stream_t stream) {
   return x_remove_if<int, DropMinusOne>(addresses, n, count_dev, workspace, workspaceBytes, (hipStream_t)stream);

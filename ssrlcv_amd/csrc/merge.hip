@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <map>
 #include <mutex>
+#include "align256.h"
 #include "device_math.h"
 #include "scan_lookback.h"
 #include "ssrlcv_hip.h"
@@ -293,10 +294,8 @@ __global__ __launch_bounds__(svs::kThreads) void k_merge_emit(Lists L, uint32_t 
     }
     return;
   }
-  constexpr uint32_t kTile = svs::kThreads * kEmitItems;
-  for (uint32_t tile = svs::next_tile(ts.counter); tile < ts.numTiles; tile = svs::next_tile(ts.counter)) {
-    const uint32_t base = tile * kTile + threadIdx.x * kEmitItems;
-    uint32_t g[kEmitItems], c[kEmitItems], mine[2] = {0, 0};
+  uint32_t g[kEmitItems], c[kEmitItems];
+  auto read = [&](uint32_t base, uint32_t (&mine)[2]) {
 #pragma unroll
     for (int j = 0; j < kEmitItems; ++j) {
       const bool in = base + j < numSeeds;
@@ -305,10 +304,9 @@ __global__ __launch_bounds__(svs::kThreads) void k_merge_emit(Lists L, uint32_t 
       mine[0] += g[j];
       mine[1] += c[j];
     }
-    uint32_t excl[2], total[2], prefix[2];
-    svs::block_exclusive<2>(mine, excl, total);
-    svs::tile_prefix<2>(ts, tile, total, prefix);
-    uint32_t mmAt = prefix[0] + excl[0], memAt = prefix[1] + excl[1];
+  };
+  auto write = [&](uint32_t base, const uint32_t (&at)[2]) {
+    uint32_t mmAt = at[0], memAt = at[1];
 #pragma unroll
     for (int j = 0; j < kEmitItems; ++j) {
       if (g[j]) {
@@ -330,20 +328,19 @@ __global__ __launch_bounds__(svs::kThreads) void k_merge_emit(Lists L, uint32_t 
         memAt += c[j];
       }
     }
-    if (tile == ts.numTiles - 1 && threadIdx.x == 0) {
-      counts[0] = prefix[0] + total[0];
-      counts[1] = prefix[1] + total[1];
-      counts[2] = 0u;  // counts[3] (rounds) was written by k_merge_walk
-    }
-  }
+  };
+  auto finish = [&](const uint32_t (&totals)[2]) {
+    counts[0] = totals[0];
+    counts[1] = totals[1];
+    counts[2] = 0u;  // counts[3] (rounds) was written by k_merge_walk
+  };
+  svs::for_each_tile<2, kEmitItems>(ts, read, write, finish);
 }
 __global__ void k_merge_no_seeds(const int* __restrict__ bad, uint32_t* __restrict__ counts) {  // two images: nothing seeds a multi-match
   counts[0] = counts[1] = counts[3] = 0u;
   counts[2] = (uint32_t)*bad;
 }
-inline uint32_t emit_tiles(uint32_t numSeeds) { return (numSeeds + svs::kThreads * kEmitItems - 1) / (svs::kThreads * kEmitItems); }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 struct Layout {
   size_t mask, len, start, entries, minReader, minWriter, state, outcome, good, members, scalars, ctl, scanTmp, total;
   size_t ctlBytes;
@@ -352,7 +349,7 @@ struct Layout {
 Layout make_layout(uint32_t numImages, uint32_t numLists, uint32_t total, uint32_t maxSeeds, uint32_t numSeeds) {
   Layout y;
   size_t p = 0;
-  auto take = [&](size_t bytes) { const size_t at = p; p += up256(bytes); return at; };
+  auto take = [&](size_t bytes) { const size_t at = p; p += align256(bytes); return at; };
   y.mask = take((size_t)numLists * 4);
   y.len = take(((size_t)numLists + 1) * 4);  // + the element the scan over numLists + 1 inputs reads (zeroed)
   y.start = take(((size_t)numLists + 1) * 4);
@@ -369,7 +366,7 @@ Layout make_layout(uint32_t numImages, uint32_t numLists, uint32_t total, uint32
   y.ctl = take(y.ctlBytes);
   // descriptors of the two single-pass scans (used one after the other): list starts over numLists + 1 lengths, emit over the seeds
   const size_t s1 = svs::workspace_bytes<1>(svs::scan_tiles<8>(numLists + 1));
-  const size_t s2 = svs::workspace_bytes<2>(emit_tiles(numSeeds ? numSeeds : 1));
+  const size_t s2 = svs::workspace_bytes<2>(svs::scan_tiles<kEmitItems>(numSeeds ? numSeeds : 1));
   y.scanTmpBytes = s1 > s2 ? s1 : s2;
   y.scanTmp = take(y.scanTmpBytes ? y.scanTmpBytes : 256);
   y.total = p;
@@ -481,11 +478,8 @@ int ssrlcv_hip_merge_matches(uint32_t numImages, const uint32_t* numFeatures_hos
   }
   // ---- output in (image, feature) order
   if (numSeeds) {
-    const uint32_t tiles = emit_tiles(numSeeds);
-    SSRLCV_HIP_TRY(hipMemsetAsync(ws + y.scanTmp, 0, svs::workspace_bytes<2>(tiles), st));
-    const svs::TileScan<2> ts = svs::make_tile_scan<2>(ws + y.scanTmp, tiles);
-    hipLaunchKernelGGL(k_merge_emit, dim3(tiles < 2048u ? tiles : 2048u), dim3(svs::kThreads), 0, st, L, numSeeds, (const uint32_t*)good,
-                       (const uint32_t*)memberCnt, matches, members, counts, (const int*)bad, ts);
+    SSRLCV_HIP_TRY(svs::launch_tiles<2>(k_merge_emit, svs::scan_tiles<kEmitItems>(numSeeds), ws + y.scanTmp, st, L, numSeeds, (const uint32_t*)good,
+                                         (const uint32_t*)memberCnt, matches, members, counts, (const int*)bad));
   } else {
     hipLaunchKernelGGL(k_merge_no_seeds, dim3(1), dim3(1), 0, st, (const int*)bad, counts);
   }

@@ -20,6 +20,7 @@
 #include <new>
 #include <stdlib.h>
 #include <string.h>
+#include "align256.h"
 #include "dev_switch.h"
 #include "device_math.h"
 #include "sift_plan.h"
@@ -1836,7 +1837,6 @@ int launch_conv(const float* in, float* out, float* tmp, uint32_t w, uint32_t h,
   return SSRLCV_OK;
 }
 
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 

@@ -12,6 +12,7 @@
 //   k_fmatrix_score      the refit, then k_finalize keeps it when it has at least as many inliers
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include "align256.h"
 #include "device_math.h"
 #include "ssrlcv_hip.h"
 
@@ -40,7 +41,6 @@ constexpr int kScoreMatchTile = kScoreThreads * kScoreP;  // matches per block
 constexpr int kScoreChunk = 256;                          // candidates staged in LDS at a time
 constexpr int kRefitBlocksMax = 256;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline uint32_t refit_blocks(uint32_t n) {
   uint32_t b = (n + 255) / 256;
   return b < 1 ? 1 : b > kRefitBlocksMax ? kRefitBlocksMax : b;

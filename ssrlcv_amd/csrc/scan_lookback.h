@@ -12,14 +12,18 @@
 // and read with relaxed device-scope atomics, so no fence orders them.  NSUM sums are carried side by side (a stream
 // compaction of variable-length records needs two: records kept, elements kept).
 //
-// The caller zeroes the workspace (workspace_bytes: descriptors + the tile counter) on the stream before the launch.
+// A kernel states what is its own -- what a thread reads and sums, what it writes from its offsets, where the totals go --
+// as the three steps of for_each_tile, which is the walk.  The host side: scan_tiles (the tiles of an input) and
+// launch_tiles (zeroes the workspace -- descriptors + the tile counter, workspace_bytes -- on the stream and launches).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "align256.h"
 
 namespace svs {
 
 constexpr int kThreads = 256;
+constexpr uint32_t kMaxBlocks = 2048;  // of a launch: past it a block goes on to claim further tiles
 constexpr unsigned long long kAggregate = 1ull << 62, kPrefix = 2ull << 62, kStateMask = 3ull << 62;
 
 template <int NSUM>
@@ -30,13 +34,13 @@ struct TileScan {
 };
 template <int NSUM>
 inline size_t workspace_bytes(uint32_t numTiles) {
-  return ((size_t)NSUM * numTiles * 8 + 255) / 256 * 256 + 256;
+  return align256((size_t)NSUM * numTiles * 8) + 256;
 }
 template <int NSUM>
 inline TileScan<NSUM> make_tile_scan(void* workspace, uint32_t numTiles) {
   TileScan<NSUM> t;
   t.desc = (unsigned long long*)workspace;
-  t.counter = (uint32_t*)((char*)workspace + ((size_t)NSUM * numTiles * 8 + 255) / 256 * 256);
+  t.counter = (uint32_t*)((char*)workspace + align256((size_t)NSUM * numTiles * 8));
   t.numTiles = numTiles;
   return t;
 }
@@ -148,42 +152,81 @@ __device__ __forceinline__ void tile_prefix(const TileScan<NSUM>& ts, uint32_t t
   for (int s = 0; s < NSUM; ++s) exclusive[s] = s_excl[s];
 }
 
-// ---- plain exclusive scan of a uint32 array (out[i] = sum of in[0..i)), ITEMS per thread; in == out is fine
-template <int ITEMS>
-__global__ __launch_bounds__(kThreads) void k_exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, TileScan<1> ts) {
+// ---- the walk of a single-pass compaction / expansion / scan: each thread owns ITEMS consecutive elements of a tile
+//   count(base, mine)  read the thread's ITEMS elements from `base` on (mind the end of the input), add to its NSUM sums
+//   place(base, at)    at[] = the sums over every element before `base`: write the outputs from there
+//   done(totals)       one thread of the last tile: the sums over the whole input
+// What a thread carries from count to place (keep flags, the elements of a removal in place) lives in the caller's
+// locals, captured by reference.  Tiles are claimed through the counter, so a block that starts late never waits for a tile
+// nobody runs; every element of a tile is read before the barriers of block_exclusive and written after them, which with
+// the look-back's order is what lets a removal work in place.
+template <int NSUM, int ITEMS, class Count, class Place, class Done>
+__device__ __forceinline__ void for_each_tile(const TileScan<NSUM>& ts, Count count, Place place, Done done) {
   constexpr uint32_t kTile = kThreads * ITEMS;
   for (uint32_t tile = next_tile(ts.counter); tile < ts.numTiles; tile = next_tile(ts.counter)) {
     const uint32_t base = tile * kTile + threadIdx.x * ITEMS;
-    uint32_t v[ITEMS], mine[1] = {0};
+    uint32_t sums[NSUM] = {}, mine[NSUM], excl[NSUM], total[NSUM], prefix[NSUM], at[NSUM];
+    count(base, sums);
+    // block_exclusive gets a copy of the sums.  count is a call the optimiser has not yet inlined when it settles how
+    // block_exclusive takes its input, and an array that was handed to such a call makes it leave that input behind a
+    // pointer for every caller in the file: the kernels that call block_exclusive themselves (k_expand_orient) would
+    // compile to other code than they do without this walk beside them.
+#pragma unroll
+    for (int s = 0; s < NSUM; ++s) mine[s] = sums[s];
+    block_exclusive<NSUM>(mine, excl, total);
+    tile_prefix<NSUM>(ts, tile, total, prefix);
+#pragma unroll
+    for (int s = 0; s < NSUM; ++s) at[s] = prefix[s] + excl[s];
+    place(base, at);
+    if (tile == ts.numTiles - 1 && threadIdx.x == 0) {
+      uint32_t totals[NSUM];
+#pragma unroll
+      for (int s = 0; s < NSUM; ++s) totals[s] = prefix[s] + total[s];
+      done(totals);
+    }
+  }
+}
+
+// tiles of n elements at ITEMS per thread
+template <int ITEMS>
+inline uint32_t scan_tiles(uint32_t n) { return (n + kThreads * ITEMS - 1) / (kThreads * ITEMS); }
+
+// queues the memset of workspace_bytes<NSUM>(tiles) bytes and kernel(args..., TileScan<NSUM>) over the tiles
+template <int NSUM, class Kernel, class... Args>
+inline hipError_t launch_tiles(Kernel kernel, uint32_t tiles, void* workspace, hipStream_t st, Args... args) {
+  const hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes<NSUM>(tiles), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(tiles < kMaxBlocks ? tiles : kMaxBlocks), dim3(kThreads), 0, st, args..., make_tile_scan<NSUM>(workspace, tiles));
+  return hipGetLastError();
+}
+
+// ---- plain exclusive scan of a uint32 array (out[i] = sum of in[0..i)), ITEMS per thread; in == out is fine
+template <int ITEMS>
+__global__ __launch_bounds__(kThreads) void k_exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, TileScan<1> ts) {
+  uint32_t v[ITEMS];
+  auto read = [&](uint32_t base, uint32_t (&mine)[1]) {
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
       v[j] = base + j < n ? in[base + j] : 0u;
       mine[0] += v[j];
     }
-    uint32_t excl[1], total[1], prefix[1];
-    block_exclusive<1>(mine, excl, total);
-    tile_prefix<1>(ts, tile, total, prefix);
-    uint32_t run = prefix[0] + excl[0];
+  };
+  auto write = [&](uint32_t base, const uint32_t (&at)[1]) {
+    uint32_t run = at[0];
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
       if (base + j < n) out[base + j] = run;
       run += v[j];
     }
-  }
+  };
+  auto finish = [](const uint32_t (&)[1]) {};
+  for_each_tile<1, ITEMS>(ts, read, write, finish);
 }
-// queues memset + the scan; workspace of workspace_bytes<1>(tiles(n)) bytes
-template <int ITEMS = 8>
-inline uint32_t scan_tiles(uint32_t n) { return (n + kThreads * ITEMS - 1) / (kThreads * ITEMS); }
+// workspace of workspace_bytes<1>(scan_tiles<ITEMS>(n)) bytes
 template <int ITEMS = 8>
 inline hipError_t exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, void* workspace, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  const uint32_t tiles = scan_tiles<ITEMS>(n);
-  hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes<1>(tiles), st);
-  if (e != hipSuccess) return e;
-  const TileScan<1> ts = make_tile_scan<1>(workspace, tiles);
-  const unsigned blocks = tiles < 2048u ? tiles : 2048u;
-  hipLaunchKernelGGL((k_exclusive_scan<ITEMS>), dim3(blocks), dim3(kThreads), 0, st, in, out, n, ts);
-  return hipGetLastError();
+  return launch_tiles<1>(k_exclusive_scan<ITEMS>, scan_tiles<ITEMS>(n), workspace, st, in, out, n);
 }
 
 }  // namespace svs

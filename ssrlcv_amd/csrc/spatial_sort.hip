@@ -17,6 +17,7 @@
 //                  unique: equal keys come in index order, run to run.
 #include <hip/hip_runtime.h>
 #include "ssrlcv_hip.h"
+#include "align256.h"
 #include "spatial_sort.h"
 
 namespace {
@@ -139,11 +140,10 @@ __global__ __launch_bounds__(kSortThreads) void k_bin_sort(const uint32_t* __res
 
 namespace svm {
 
-static size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
 size_t sort_scratch_bytes(uint32_t n) {
   const size_t nn = n ? n : 1;
-  return round256(nn * 4) + round256(nn * 8) + 3 * round256((size_t)(kBins + 1) * 4);  // keys, words, counts / bases / cursors
+  return align256(nn * 4) + align256(nn * 8) + 3 * align256((size_t)(kBins + 1) * 4);  // keys, words, counts / bases / cursors
 }
 
 SortBuffers sort_buffers(void* scratch, uint32_t n) {
@@ -156,10 +156,10 @@ int sort_filled_keys(uint32_t n, uint32_t* perm, void* scratch, size_t scratchBy
   if (scratchBytes < sort_scratch_bytes(n)) return SSRLCV_ERR_WORKSPACE;
   char* base = (char*)scratch;
   const uint32_t* keys = (const uint32_t*)base;
-  unsigned long long* words = (unsigned long long*)(base + round256((size_t)n * 4));
-  uint32_t* binCount = (uint32_t*)((char*)words + round256((size_t)n * 8));
-  uint32_t* binBase = (uint32_t*)((char*)binCount + round256((size_t)(kBins + 1) * 4));
-  uint32_t* cursor = (uint32_t*)((char*)binBase + round256((size_t)(kBins + 1) * 4));
+  unsigned long long* words = (unsigned long long*)(base + align256((size_t)n * 4));
+  uint32_t* binCount = (uint32_t*)((char*)words + align256((size_t)n * 8));
+  uint32_t* binBase = (uint32_t*)((char*)binCount + align256((size_t)(kBins + 1) * 4));
+  uint32_t* cursor = (uint32_t*)((char*)binBase + align256((size_t)(kBins + 1) * 4));
   hipError_t e = hipMemsetAsync(binCount, 0, (size_t)kBins * 4, stream);
   if (e != hipSuccess) return (int)e;
   const uint32_t chunk = (n + kChunkBlocks - 1) / kChunkBlocks;

@@ -26,6 +26,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "ssrlcv_hip.h"
+#include "align256.h"
 #include "compact.h"
 #include "device_math.h"
 
@@ -320,7 +321,7 @@ int stereo_params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) 
 // samples 0, step, 2 step, ... below n: ceil(n / step) without the sum n + step - 1, which wraps for a step near 2^32
 uint32_t stereo_grid(uint32_t n, uint32_t step) { return n ? (n - 1) / step + 1 : 0; }
 
-size_t stereo_map_bytes(uint32_t w, uint32_t h) { return ((size_t)w * h + 255) / 256 * 256; }
+size_t stereo_map_bytes(uint32_t w, uint32_t h) { return align256((size_t)w * h); }
 
 StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) {
   StereoArgs a;
@@ -397,7 +398,7 @@ int ssrlcv_hip_stereo_sad_u8(const uint8_t* left, const uint8_t* right, uint32_t
 size_t ssrlcv_hip_stereo_matches_workspace_bytes(uint32_t w, uint32_t h, uint32_t step) {
   if (step == 0 || (unsigned long long)w * h >= (1ull << 31)) return 0;
   const uint32_t nxs = stereo_grid(w, step), nys = stereo_grid(h, step);
-  return (svc::workspace_words<1, kMatchPerThread>(nxs * nys) * 4 + 255) / 256 * 256;
+  return align256(svc::workspace_words<1, kMatchPerThread>(nxs * nys) * 4);
 }
 
 int ssrlcv_hip_stereo_matches(const float* disparity, uint32_t w, uint32_t h, uint32_t step, int leftId, int rightId, ssrlcv_match* out,

@@ -25,8 +25,8 @@ COPY_SWEEP = COPY_BLOCKS * COPY_THREADS
 # ---- csrc/scan_lookback.h, csrc/filter.hip
 SVS_THREADS = 256                      # svs::kThreads
 K_ITEMS = 4                            # filter.hip kItems
-TILE = SVS_THREADS * K_ITEMS           # 1024 bundles / multi-matches per tile
-GRID_CAP = 2048                        # blocks of k_filter_matchset / k_select_pair at most
+TILE = SVS_THREADS * K_ITEMS           # 1024 bundles / multi-matches per tile (scan_lookback.h for_each_tile<NSUM, kItems>)
+GRID_CAP = 2048                        # scan_lookback.h kMaxBlocks: blocks of k_filter_matchset / k_select_pair at most
 LOOKBACK_WINDOW = 64                   # aggregates one look-back step reads (tile_prefix: at -= 64); not forced, see DESIGN.md
 K_CHUNK = 1024                         # filter.hip kChunk: samples per half of k_sample_cutoff's double buffer
 

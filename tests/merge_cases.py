@@ -72,8 +72,11 @@ TRACKS = {
     "tracks_v32_full": dict(seed=3202, nf=[80] * 32, vis=1.0, points=64),
 }
 # tracks_v4_drop again with the largest seed image at N features: 1, 1, 1, 2, 16, 17, 34 and (CU count) blocks of the
-# persistent kernel -- barrier groups uneven, full and wrapped; 70 000 takes the grid-stride loops
-GRID_SIZES = (1, 255, 256, 257, 3841, 4097, 8449, 70000)
+# persistent kernel -- barrier groups uneven, full and wrapped; 70 000 takes the grid-stride loops.  682, 683 and 684 give
+# 1023, 1024 and 1026 seeds (N + N // 2: the first two images seed): either side of k_merge_emit's tile of 256 x 4 seeds
+GRID_SIZES = (1, 255, 256, 257, 682, 683, 684, 3841, 4097, 8449, 70000)
+EMIT_TILE = 1024
+assert [n + n // 2 for n in GRID_SIZES[4:7]] == [EMIT_TILE - 1, EMIT_TILE, EMIT_TILE + 2]
 
 
 def grid(n):

@@ -32,7 +32,8 @@ def source(name):
     ("scan_lookback.h", r"at -= (\d+);", C.LOOKBACK_WINDOW),
     ("filter.hip", r"constexpr int kItems = (\d+);", C.K_ITEMS),
     ("filter.hip", r"constexpr int kChunk = (\d+);", C.K_CHUNK),
-    ("filter.hip", r"constexpr uint32_t kTile = svs::kThreads \* kItems;", None),
+    ("scan_lookback.h", r"constexpr uint32_t kTile = kThreads \* ITEMS;", None),
+    ("scan_lookback.h", r"constexpr uint32_t kMaxBlocks = (\d+);", C.GRID_CAP),
     ("matcher.hip", r"constexpr int kMaxGatherImages = (\d+);", C.MAX_GATHER_IMAGES),
     ("matcher.hip", r"blocks = blocks > (\d+)u \? 2048u : blocks;\s+hipLaunchKernelGGL\(k_copy_counted, dim3\(blocks\), dim3\(256\)", C.COPY_BLOCKS),
     ("matcher.hip", r"i \+= \(size_t\)gridDim\.x \* (\d+)\) dst\[i\] = src\[i\];", C.COPY_THREADS),
@@ -48,16 +49,25 @@ def test_the_constants_are_the_sources(name, pattern, value):
 
 
 def test_the_instantiations_are_the_sources():
-    """partition<1, 8> at all five call sites of the two compactions, the grid cap of both look-back kernels, and the
-    workspace formula the exact-size tests restate"""
+    """partition<1, 8> at all five call sites of the two compactions, the one walk of the look-back kernels (its tile, its grid
+    cap, its last-tile condition) with both filter kernels instantiating it at kItems, and the workspace formula the exact-size
+    tests restate"""
     m = source("matcher.hip")
     body = m[m.index("int ssrlcv_hip_compact_matches("): m.index("int ssrlcv_hip_keypoints_from_members(")]
     assert len(re.findall(r"svc::partition<1, %d>\(numMatches" % C.PER_THREAD, body)) == 5 == len(re.findall(r"svc::partition<", body))
     assert len(re.findall(r"\(size_t\)numMatches \* elem \+ 256 \+ svc::workspace_words<1, %d>\(numMatches\) \* 4;" % C.PER_THREAD, body)) == 2
     assert "return (size_t)NKEYS * kWavesPerBlock * num_chunks(n, PER_THREAD) + NKEYS + 2;" in source("compact.h")
-    f = source("filter.hip")
-    assert len(re.findall(r"const unsigned blocks = tiles < %du \? tiles : %du;" % (C.GRID_CAP, C.GRID_CAP), f)) == 2
-    assert len(re.findall(r"if \(tile == ts\.numTiles - 1 && threadIdx\.x == 0\)", f)) == 2
+    h, f = source("scan_lookback.h"), source("filter.hip")
+    # one walk: a tile of kThreads * ITEMS from `base` on, tiles handed out up to ts.numTiles, the last one's thread 0 reports
+    assert len(re.findall(r"const uint32_t base = tile \* kTile \+ threadIdx\.x \* ITEMS;", h)) == 1
+    assert len(re.findall(r"if \(tile == ts\.numTiles - 1 && threadIdx\.x == 0\)", h)) == 1
+    assert len(re.findall(r"for \(uint32_t tile = next_tile\(ts\.counter\); tile < ts\.numTiles; tile = next_tile\(ts\.counter\)\)", h)) == 1
+    # one launch: the grid cap, and the tile count the filters ask for is that of their kItems
+    assert len(re.findall(r"dim3\(tiles < kMaxBlocks \? tiles : kMaxBlocks\), dim3\(kThreads\)", h)) == 1
+    assert "inline uint32_t scan_tiles(uint32_t n) { return (n + kThreads * ITEMS - 1) / (kThreads * ITEMS); }" in h
+    assert len(re.findall(r"svs::for_each_tile<3, kItems>\(", f)) == 1 == len(re.findall(r"svs::for_each_tile<1, kItems>\(", f))
+    assert len(re.findall(r"svs::launch_tiles<3>\(k_filter_matchset, tiles,", f)) == 1 == len(re.findall(r"svs::launch_tiles<1>\(k_select_pair, tiles,", f))
+    assert len(re.findall(r"const uint32_t tiles = svs::scan_tiles<kItems>\(", f)) == 2 and "next_tile" not in f and "hipLaunchKernelGGL(k_filter" not in f
     assert "for (uint32_t base = 0; base < numImages; base += (uint32_t)kMaxGatherImages)" in m
 
 
