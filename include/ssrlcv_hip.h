@@ -47,7 +47,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      match2_workspace_bytes, match_knn2_u8x128, match_ratio_u8x128;
  *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8;
  *      dense stereo: stereo_workspace_bytes, stereo_sad_u8, stereo_matches_workspace_bytes, stereo_matches, stereo_points;
- *      rectification: rectify_cameras_host, warp_homography_u8, stereo_mask_rectified, matches_apply_homography */
+ *      rectification: rectify_cameras_host, warp_homography_u8, stereo_mask_rectified, matches_apply_homography;
+ *      semi-global matching: stereo_sgm_workspace_bytes, stereo_sgm_u8, stereo_sgm_set_pass_events */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -634,8 +635,8 @@ int ssrlcv_hip_sift_dense_u8(const uint8_t* pixels, uint32_t w, uint32_t h, cons
  * workspace.  An image smaller than one window is no error: every pixel is invalid.
  * Workspace (ssrlcv_hip_stereo_workspace_bytes; host only; 0 for parameters the call refuses): two bytes per pixel, the
  * winners' k of the two views.  Asynchronous on `stream`; no host synchronisation; no atomics: bit-equal run to run.
- * Out of scope: a uniqueness ratio, colour, census or NCC costs, semi-global aggregation.  (An unrectified pair of pinhole
- * cameras is rectified first: "rectification" below.) */
+ * Out of scope here: a uniqueness ratio, colour, census or NCC costs.  Aggregating these costs along paths is the next
+ * section, "semi-global matching".  (An unrectified pair of pinhole cameras is rectified first: "rectification" below.) */
 typedef struct {
   uint32_t radius;          /* r in 1..15; the window is (2r + 1)^2.  Upstream's five sizes: r = 1, 4, 7, 12, 15 */
   int32_t minDisparity;     /* -32768 .. 32767 */
@@ -663,6 +664,64 @@ int ssrlcv_hip_stereo_matches(const float* disparity, uint32_t w, uint32_t h, ui
  * missing result.  foc not finite or 0: SSRLCV_ERR_INVALID_ARG.  Asynchronous on `stream`. */
 int ssrlcv_hip_stereo_points(const ssrlcv_match* matches, uint32_t n, float foc, float baseline, float doffset, float cx, float cy,
                              ssrlcv_float3* points, ssrlcv_stream_t stream);
+
+/* ---- semi-global matching (Hirschmueller) over the SAD costs of dense stereo: instead of every pixel choosing its disparity
+ * on its own, the clamped matching costs are aggregated along up to eight paths through the image with a small penalty for a
+ * disparity step of one and a larger one for any other jump, and the winner is taken from the sum.  Integer arithmetic
+ * throughout: the kernels of csrc/stereo.hip are held to a numpy restatement bit for bit (tests/sgm_ref.py,
+ * tests/test_gpu_sgm.py).  The outputs are dense stereo's two maps, so ssrlcv_hip_stereo_mask_rectified, _stereo_matches,
+ * _matches_apply_homography and _stereo_points take them unchanged.
+ *   inputs      those of dense stereo.  C(x, y, d), "candidate" and the interior I = [r, w - 1 - r] x [r, h - 1 - r] are items
+ *               1-2 of dense stereo, unchanged.  The disparity index is k = 0 .. D - 1 (D = numDisparities), d = minDisparity + k.
+ *   1 cost      for p in I: M(p, k) = min(C(p, d), costClamp) if d is a candidate of p, else costClamp.  A non-candidate takes
+ *               part in the recursion like any other entry; it can never be a winner.
+ *   2 paths     bit i of `paths` selects direction i, (dx, dy) = 0: (+1, 0)  1: (-1, 0)  2: (0, +1)  3: (0, -1)  4: (+1, +1)
+ *               5: (-1, +1)  6: (+1, -1)  7: (-1, -1).  The predecessor of p is q = p - (dx, dy).  0x0F is the usual 4-path
+ *               form, 0xFF the 8-path form.
+ *   3 path cost q not in I: L_i(p, k) = M(p, k).  Otherwise, with m = min over all k of L_i(q, k):
+ *               L_i(p, k) = M(p, k) + min(L_i(q, k), L_i(q, k - 1) + P1 [k >= 1], L_i(q, k + 1) + P1 [k <= D - 2], m + P2) - m.
+ *               Integers, 0 <= L_i <= costClamp + P2.
+ *   4 sum       S(p, k) = sum over the selected i of L_i(p, k) <= popcount(paths) (costClamp + P2).
+ *   5 winner    d*(p) = the candidate of least S, the smallest d among equal S.  A pixel with no candidate is invalid.  There
+ *               is no cost limit.
+ *   6 LR check  lrTolerance >= 0: item 4 of dense stereo with S in place of C: dR(x', y) = the d of least S(x' + d, y, d) over
+ *               the d that are candidates of (x' + d, y), the smallest d on ties; (x, y) stays valid only if
+ *               |dR(x - d*, y) - d*| <= lrTolerance.  The right view gets no aggregation of its own.
+ *   7 sub-pixel subpixel = 1: item 5 of dense stereo with S in place of C: both neighbours candidates, den = S(d* - 1) - 2 S* +
+ *               S(d* + 1) != 0, off = (float)(S(d* - 1) - S(d* + 1)) / (float)(2 den), disparity = (float)d* + off; every
+ *               integer is below 2^24.
+ *   8 outputs   item 6 of dense stereo: disparity[w h] float, 0x7FC00000 for an invalid pixel; cost[w h] uint32 (may be NULL)
+ *               holds S*, UINT32_MAX for an invalid pixel.  Every pixel of both maps is written.
+ * Decided on the host before any launch, the parameters before the buffers, in this order: SSRLCV_ERR_INVALID_ARG for params
+ * NULL, radius 0, numDisparities 0, minDisparity outside -32768 .. 32767, subpixel > 1, P1 > P2, paths 0 or above 0xFF, w h >=
+ * 2^31; SSRLCV_ERR_UNSUPPORTED for radius > 15, numDisparities > 256 or popcount(paths) (costClamp + P2) > 65535 (evaluated in
+ * 64 bits; the bound that lets M, L and S live in 16 bits); then SSRLCV_ERR_INVALID_ARG for a NULL buffer (cost may be NULL);
+ * SSRLCV_ERR_WORKSPACE for a short workspace.  An image smaller than one window is no error: every pixel is invalid.
+ * Workspace (ssrlcv_hip_stereo_sgm_workspace_bytes; host only; 0 for parameters the call refuses; computed in size_t): with
+ * K = numDisparities rounded up to 8, 16, 32, 64, 128 or 256 and a256(n) = n rounded up to 256,
+ *     2 a256(w h) + 2 a256(2 w h K) + 256 bytes
+ * -- the winners' k of the two views and the two uint16 volumes M and S, [y][x][k] (at 4096 x 4096, D = 64: 2 x 2.1 GB).
+ * Asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.
+ * Out of scope: a uniqueness ratio, colour, census or NCC costs, more than 8 paths, penalties adapted to the image gradient. */
+typedef struct {
+  uint32_t radius;          /* 1..15 */
+  int32_t minDisparity;     /* -32768 .. 32767 */
+  uint32_t numDisparities;  /* 1..256 */
+  uint32_t costClamp;       /* 0 is legal: everything ties */
+  uint32_t P1, P2;          /* P1 <= P2 */
+  uint32_t paths;           /* bit mask, 1..0xFF */
+  int32_t lrTolerance;      /* < 0: no check */
+  uint32_t subpixel;        /* 0 or 1 */
+} ssrlcv_sgm_params;        /* 36 bytes */
+size_t ssrlcv_hip_stereo_sgm_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params);
+int ssrlcv_hip_stereo_sgm_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
+                             void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream);
+/* The hook tools/bench_sgm.py times the passes of one call with (process-wide, not thread-safe; not for production callers):
+ * every later ssrlcv_hip_stereo_sgm_u8 records events[j] (hipEvent_t; a NULL entry is skipped) on its stream -- [0] before the
+ * first launch, [1] behind the fill and the cost pass, then one behind each selected direction's pass in the order of the bits,
+ * one behind the winner pass and one behind the left-right check (at most 12).  count 0 removes the hook; count > 12 or events
+ * NULL with count > 0: SSRLCV_ERR_INVALID_ARG.  The caller keeps the events alive until it removes the hook. */
+int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count);
 
 /* ---- rectification: a converging pair of Image::Camera records -> two homographies -> a rectified pair for the dense stereo
  * above, and its matches back in source pixels, where they triangulate with the original cameras into the sparse path's world

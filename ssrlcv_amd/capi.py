@@ -588,6 +588,43 @@ def stereo_disparity(left_d, right_d, radius=4, min_disparity=0, num_disparities
     return disp, cost
 
 
+class SgmParams(ctypes.Structure):
+    _fields_ = [("radius", c_u32), ("minDisparity", ctypes.c_int32), ("numDisparities", c_u32), ("costClamp", c_u32), ("P1", c_u32),
+                ("P2", c_u32), ("paths", c_u32), ("lrTolerance", ctypes.c_int32), ("subpixel", c_u32)]
+
+
+def stereo_sgm(left_d, right_d, radius=2, min_disparity=0, num_disparities=64, cost_clamp=1000, p1=40, p2=400, paths=0xFF,
+               lr_tolerance=1, subpixel=True, want_cost=False, workspace=None):
+    """Semi-global matching over the clamped SAD costs (ssrlcv_hip_stereo_sgm_u8; include/ssrlcv_hip.h "semi-global
+    matching") of two rectified u8 CUDA tensors (H, W).  -> (disparity, cost or None) as stereo_disparity gives them; the cost
+    is the winner's summed path cost.  The workspace holds two uint16 volumes of H W num_disparities entries each.
+    Asynchronous on the current stream."""
+    h, w = left_d.shape
+    assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
+    assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
+    p = SgmParams(radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, 1 if subpixel else 0)
+    need = int(LIB.ssrlcv_hip_stereo_sgm_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
+    disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
+    check(LIB.ssrlcv_hip_stereo_sgm_u8(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()),
+                                       ptr(disp), ptr(cost), stream_ptr()))
+    return disp, cost
+
+
+def stereo_sgm_set_pass_events(events):
+    """torch.cuda.Events (or None to remove the hook) that every later stereo_sgm records between its passes
+    (ssrlcv_hip_stereo_sgm_set_pass_events): before the first launch, behind the cost pass, behind each selected direction,
+    behind the winner pass and behind the left-right check.  The caller keeps the events alive until it removes the hook."""
+    if not events:
+        check(LIB.ssrlcv_hip_stereo_sgm_set_pass_events(None, c_u32(0)))
+        return
+    for e in events:
+        e.record()                   # torch creates the underlying hipEvent_t lazily, on the first record
+    arr = (c_vp * len(events))(*[e.cuda_event for e in events])
+    check(LIB.ssrlcv_hip_stereo_sgm_set_pass_events(arr, c_u32(len(events))))
+
+
 def stereo_matches(disp_d, step=1, left_id=0, right_id=1, capacity=None):
     """The valid pixels of a disparity map on the `step` grid as Match records (ssrlcv_hip_stereo_matches), in raster order.
     -> (Match bytes [min(count, capacity) * 40], count).  capacity defaults to the grid's size."""

@@ -19,7 +19,26 @@
 //                    the next group) and writes the pixel: cost limit, sub-pixel offset, disparity, cost, k.
 //                    RIGHT = true is the same pass seen from the right image (partner at x + d): the right winners of the
 //                    left-right check, as a second pass (it runs only when the check is asked for).
+//                    VOLUME = true is the cost pass of semi-global matching: the same march and the same 32 running sums,
+//                    but instead of choosing a winner a lane stores its eight costs of a column, clamped (costClamp, also
+//                    for a non-candidate), as eight uint16 in one 16-byte store into the volume M[y][x][k].
 //   k_stereo_lr      the left-right check over the two k maps
+//   k_sgm_path       semi-global matching (include/ssrlcv_hip.h "semi-global matching"; tests/sgm_ref.py restates it): one
+//                    direction's pass.  A group of nD lanes -- 8 disparities a lane, the SAD kernel's ownership -- owns ONE
+//                    path from its first pixel of the interior to its last: 64 / nD paths a wave, one wave a block, no block
+//                    waits for another.  The state L(q, .) lives in 32-bit registers; a step takes L(q, k -/+ 1) of the group's
+//                    edge disparities from the neighbouring lanes (one lane up, one down, the group's ends and k >= D
+//                    holding a sentinel no minimum picks and no penalty wraps) and min over k of L(q, k) through the xor
+//                    butterfly, both as DPP moves inside a row of 16 lanes (shuffles only for 32-lane groups).  The addresses of M and S along a path do not depend on the chain: the 16-byte loads of
+//                    the next kSgmAhead steps are in flight in a register ring while a step is computed, and S, read
+//                    ahead with M, is updated beside the chain (the first selected direction stores S, the others add).
+//                    Every pixel of the interior lies on exactly one path of a pass; the passes are ordered on the stream.
+//                    Diagonals are enumerated in coordinates flipped so that the direction is (+1, +1): wi paths start on
+//                    the first row, hi - 1 on the first column below it.
+//   k_sgm_winners    the left winner of every interior pixel from S over its candidates (the SAD kernel's key and
+//                    butterfly), the sub-pixel offset, both maps and kL; and, when the check is asked for, the right
+//                    winners into kR for k_stereo_lr: S(x' + d, y, d) reaches right pixel x' through an LDS tile of the
+//                    block's row strip, so S is read in whole 16-byte entries only
 //   StereoKeep / StereoEmit + compact.h   the valid pixels of the sampling grid as Match records, in raster order
 //   k_stereo_points  upstream's stereo_disparity
 #include <hip/hip_runtime.h>
@@ -90,7 +109,9 @@ __global__ __launch_bounds__(256) void k_stereo_fill(float* __restrict__ dispari
 
 // RIGHT = false: base = left image, other = right, partner of (x, d) at x - d; writes disparity, cost and kwin.
 // RIGHT = true:  base = right image, other = left, partner at x + d; writes kwin alone.
-template <bool RIGHT>
+// VOLUME = true: stores the clamped costs instead of choosing winners.  The arguments keep their places, so that the winner
+// form's code does not move: `disparity` carries the volume M (uint16 [y][x][nD * 8]), a.maxCost the clamp; cost, kwin unused.
+template <bool RIGHT, bool VOLUME = false>
 __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ base, const uint8_t* __restrict__ other, StereoArgs a,
                                                     float* __restrict__ disparity, uint32_t* __restrict__ cost, uint8_t* __restrict__ kwin) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -194,6 +215,26 @@ __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ 
     const int y = t - a.r;
     if (y < Y0) continue;  // block-uniform: the window is not full yet
 
+    if constexpr (VOLUME) {
+      uint16_t* volume = reinterpret_cast<uint16_t*>(disparity);
+#pragma unroll
+      for (int xi = 0; xi < kXs; ++xi) {
+        const int x = X0 + offB + xi;
+        if (x <= a.w - 1 - a.r) {
+          uint32_t c[kDc];
+#pragma unroll
+          for (int dk = 0; dk < kDc; ++dk) c[dk] = (valid[xi] >> dk) & 1u ? min(V[xi][dk], a.maxCost) : a.maxCost;
+          uint4 o;
+          o.x = c[0] | (c[1] << 16);
+          o.y = c[2] | (c[3] << 16);
+          o.z = c[4] | (c[5] << 16);
+          o.w = c[6] | (c[7] << 16);
+          *reinterpret_cast<uint4*>(volume + ((size_t)y * a.w + x) * Dtile + dl * kDc) = o;
+        }
+      }
+      continue;
+    }
+
 #pragma unroll
     for (int xi = 0; xi < kXs; ++xi) {
       uint32_t best = kNoKey;
@@ -253,6 +294,220 @@ __global__ __launch_bounds__(256) void k_stereo_lr(float* __restrict__ disparity
       disparity[p] = __uint_as_float(kNaN);
       if (cost) cost[p] = 0xFFFFFFFFu;
     }
+  }
+}
+
+// ---- semi-global matching over the clamped SAD costs
+constexpr uint32_t kSgmBig = 0x0FFFFFFFu;  // a padded entry (k >= D) or a missing neighbour: above every L, and + P2 does not wrap
+constexpr int kSgmAhead = 8;               // steps whose M and S loads are in flight ahead of the chain
+
+struct SgmArgs {
+  int w, h, r, wi, hi;     // wi x hi: the interior
+  int D, dmin, nD, nDlog, K8;  // K8 = nD * 8 entries per pixel of either volume
+  uint32_t P1, P2;
+  int nPaths;
+  int subpixel, wantRight;
+  const uint16_t* M;
+  uint16_t* S;
+};
+
+__device__ __forceinline__ void sgm_unpack(const uint4& v, uint32_t (&o)[kDc]) {
+  o[0] = v.x & 0xFFFFu; o[1] = v.x >> 16;
+  o[2] = v.y & 0xFFFFu; o[3] = v.y >> 16;
+  o[4] = v.z & 0xFFFFu; o[5] = v.z >> 16;
+  o[6] = v.w & 0xFFFFu; o[7] = v.w >> 16;
+}
+
+// One DPP move: lane i takes `v` of the lane CTRL names, or `old` where that lane does not exist (bound_ctrl off).
+template <int CTRL>
+__device__ __forceinline__ uint32_t sgm_dpp(uint32_t old, uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, 0xF, 0xF, false);
+}
+
+// min over the nD lanes of a group (every lane of the wave active).  Quads swap by quad_perm; once a quad agrees, the mirror of
+// a half row pairs it with the other quad of its eight, and the mirror of a row pairs the eights; 32 lanes take one shuffle.
+__device__ __forceinline__ uint32_t sgm_group_min(uint32_t m, int nD) {
+  if (nD >= 2) m = min(m, sgm_dpp<0xB1>(m, m));    // quad_perm [1, 0, 3, 2]
+  if (nD >= 4) m = min(m, sgm_dpp<0x4E>(m, m));    // quad_perm [2, 3, 0, 1]
+  if (nD >= 8) m = min(m, sgm_dpp<0x141>(m, m));   // row_half_mirror
+  if (nD >= 16) m = min(m, sgm_dpp<0x140>(m, m));  // row_mirror
+  if (nD >= 32) m = min(m, (uint32_t)__shfl_xor((int)m, 16, 64));
+  return m;
+}
+
+template <int DX, int DY, bool FIRST>
+__global__ __launch_bounds__(64) void k_sgm_path(SgmArgs a) {
+  const int tid = (int)(blockIdx.x * 64u + threadIdx.x);
+  const int dl = tid & (a.nD - 1);
+  const int path = tid >> a.nDlog;
+  // the path's first pixel (u, v) in interior coordinates flipped so that the direction is (+1 or 0, +1 or 0), and its length
+  int u, v, len;
+  if (DY == 0) { u = 0; v = path; len = a.wi; }
+  else if (DX == 0) { u = path; v = 0; len = a.hi; }
+  else if (path < a.wi) { u = path; v = 0; len = min(a.wi - path, a.hi); }
+  else { u = 0; v = path - a.wi + 1; len = min(a.hi - v, a.wi); }
+  if (path >= a.nPaths) { u = 0; v = 0; len = 0; }
+  const int x = a.r + (DX >= 0 ? u : a.wi - 1 - u);
+  const int y = a.r + (DY >= 0 ? v : a.hi - 1 - v);
+  const long long stride = ((long long)DY * a.w + DX) * a.K8;  // elements from a pixel to the next one of the path
+  const long long at0 = ((long long)y * a.w + x) * a.K8 + dl * kDc;
+  int wlen = len;  // the longest path of this wave: the loop is wave-uniform, a finished group idles
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) wlen = max(wlen, __shfl_xor(wlen, s, 64));
+
+  uint32_t inD = 0;  // which of this lane's eight k are below D
+#pragma unroll
+  for (int dk = 0; dk < kDc; ++dk)
+    if (dl * kDc + dk < a.D) inD |= 1u << dk;
+
+  uint4 mq[kSgmAhead], sq[kSgmAhead];
+#pragma unroll
+  for (int j = 0; j < kSgmAhead; ++j) {
+    mq[j] = make_uint4(0, 0, 0, 0);
+    sq[j] = make_uint4(0, 0, 0, 0);
+    if (j < len) {
+      mq[j] = *reinterpret_cast<const uint4*>(a.M + at0 + j * stride);
+      if (!FIRST) sq[j] = *reinterpret_cast<const uint4*>(a.S + at0 + j * stride);
+    }
+  }
+
+  uint32_t L[kDc];
+#pragma unroll
+  for (int dk = 0; dk < kDc; ++dk) L[dk] = kSgmBig;
+
+  for (int s0 = 0; s0 < wlen; s0 += kSgmAhead) {
+#pragma unroll
+    for (int j = 0; j < kSgmAhead; ++j) {
+      const int s = s0 + j;
+      uint32_t Mk[kDc], Sk[kDc];
+      sgm_unpack(mq[j], Mk);
+      sgm_unpack(sq[j], Sk);
+      if (s + kSgmAhead < len) {
+        mq[j] = *reinterpret_cast<const uint4*>(a.M + at0 + (s + kSgmAhead) * stride);
+        if (!FIRST) sq[j] = *reinterpret_cast<const uint4*>(a.S + at0 + (s + kSgmAhead) * stride);
+      }
+      if (s == 0) {  // wave-uniform: the predecessor is outside the interior
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) L[dk] = (inD >> dk) & 1u ? Mk[dk] : kSgmBig;
+      } else {
+        uint32_t m = L[0];
+#pragma unroll
+        for (int dk = 1; dk < kDc; ++dk) m = min(m, L[dk]);
+        m = sgm_group_min(m, a.nD);
+        uint32_t below, above;  // L(q, k - 1) of this lane's first k, L(q, k + 1) of its last
+        if (a.nD <= 16) {       // wave-uniform: a group lies inside a row of 16 lanes
+          below = sgm_dpp<0x111>(kSgmBig, L[kDc - 1]);  // row_shr:1
+          above = sgm_dpp<0x101>(kSgmBig, L[0]);        // row_shl:1
+        } else {
+          below = (uint32_t)__shfl_up((int)L[kDc - 1], 1, 64);
+          above = (uint32_t)__shfl_down((int)L[0], 1, 64);
+        }
+        if (dl == 0) below = kSgmBig;
+        if (dl == a.nD - 1) above = kSgmBig;
+        const uint32_t jump = m + a.P2;
+        uint32_t N[kDc];
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) {
+          const uint32_t lo = dk == 0 ? below : L[dk - 1];
+          const uint32_t hi = dk == kDc - 1 ? above : L[dk + 1];
+          N[dk] = Mk[dk] + min(min(L[dk], jump), min(lo, hi) + a.P1) - m;
+        }
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) L[dk] = (inD >> dk) & 1u ? N[dk] : kSgmBig;
+      }
+      if (s < len) {
+        uint32_t o[kDc];
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) o[dk] = (inD >> dk) & 1u ? (FIRST ? L[dk] : Sk[dk] + L[dk]) : 0u;  // <= 65535 (the host's bound)
+        uint4 ov;
+        ov.x = o[0] | (o[1] << 16);
+        ov.y = o[2] | (o[3] << 16);
+        ov.z = o[4] | (o[5] << 16);
+        ov.w = o[6] | (o[7] << 16);
+        *reinterpret_cast<uint4*>(a.S + at0 + s * stride) = ov;
+      }
+    }
+  }
+}
+
+// A block owns one interior row and T neighbouring pixels of it, as left pixels and as right pixels.  It walks the left pixels
+// whose entries either view needs, 256 / nD at a time, every lane with the eight S of its pixel from one 16-byte load: a pixel
+// of the block's own gets its left winner (the SAD kernel's key, butterfly and edge shuffles), and every entry S(x, k) whose
+// right pixel x - d lies in the block goes to that pixel's row of an LDS tile [T][8 nD]; behind one barrier the right winners
+// are read off the tile the same way.  The tile is 32 KB at most (T = 16384 / (8 nD), at most 1024).
+__global__ __launch_bounds__(256) void k_sgm_winners(SgmArgs a, int T, int strips, float* __restrict__ disparity, uint32_t* __restrict__ cost,
+                                                     uint8_t* __restrict__ kL, uint8_t* __restrict__ kR) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint16_t* tile = reinterpret_cast<uint16_t*>(smem);  // [T][K8]: S(x' + d, y, d) of right pixel x0 + t
+  const int tid = threadIdx.x;
+  const int dl = tid & (a.nD - 1), pl = tid >> a.nDlog;
+  const int P = 256 >> a.nDlog;
+  const int strip = (int)(blockIdx.x % (unsigned)strips), v = (int)(blockIdx.x / (unsigned)strips);
+  const int y = a.r + v, lo = a.r, hi = a.w - 1 - a.r;
+  const int x0 = a.r + strip * T, x1 = min(x0 + T - 1, hi);  // the block's own pixels
+  int first = x0, last = x1;                                  // the left pixels it walks
+  if (a.wantRight) {
+    first = max(lo, min(x0, x0 + a.dmin));
+    last = min(hi, max(x1, x1 + a.dmin + a.D - 1));
+  }
+  const size_t rowAt = (size_t)y * a.w;
+  for (int xb = first; xb <= last; xb += P) {  // block-uniform
+    const int x = xb + pl;
+    const bool there = x <= last;
+    const size_t p = rowAt + (there ? x : first);
+    uint32_t S[kDc];
+    sgm_unpack(*reinterpret_cast<const uint4*>(a.S + p * a.K8 + dl * kDc), S);
+    uint32_t best = kNoKey;
+#pragma unroll
+    for (int dk = 0; dk < kDc; ++dk) {
+      const int k = dl * kDc + dk, partner = x - (a.dmin + k);
+      const bool cand = k < a.D && partner >= lo && partner <= hi;
+      best = min(best, cand ? (S[dk] << 8) | (uint32_t)k : kNoKey);
+      if (a.wantRight && there && cand && partner >= x0 && partner <= x1) tile[(partner - x0) * a.K8 + k] = (uint16_t)S[dk];
+    }
+    for (int s = 1; s < a.nD; s <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, s, 64));
+    const uint32_t fromBelow = (uint32_t)__shfl_up((int)S[kDc - 1], 1, 64);
+    const uint32_t fromAbove = (uint32_t)__shfl_down((int)S[0], 1, 64);
+    const int k = (int)(best & 0xFFu);
+    if (there && x >= x0 && x <= x1 && best != kNoKey && (k >> 3) == dl) {
+      kL[p] = (uint8_t)k;
+      const uint32_t c = best >> 8;
+      const int d = a.dmin + k;
+      float disp = (float)d;
+      if (a.subpixel) {
+        const int partner = x - d;
+        const bool hasM = k >= 1 && partner + 1 >= lo && partner + 1 <= hi;
+        const bool hasP = k + 1 < a.D && partner - 1 >= lo && partner - 1 <= hi;
+        if (hasM && hasP) {
+          const int idx = k & 7;
+          uint32_t cm = fromBelow, cp = fromAbove;
+#pragma unroll
+          for (int dk = 0; dk < kDc; ++dk) {
+            if (idx == dk + 1) cm = S[dk];
+            if (idx + 1 == dk) cp = S[dk];
+          }
+          const int den = (int)cm - 2 * (int)c + (int)cp;
+          if (den != 0) disp = (float)d + __fdiv_rn((float)((int)cm - (int)cp), (float)(2 * den));
+        }
+      }
+      disparity[p] = disp;
+      if (cost) cost[p] = c;
+    }
+  }
+  if (!a.wantRight) return;  // block-uniform
+  __syncthreads();
+  for (int t = pl; t < T; t += P) {  // T is a multiple of P: wave-uniform trip count
+    const int xr = x0 + t;
+    uint32_t S[kDc];
+    sgm_unpack(*reinterpret_cast<const uint4*>(tile + t * a.K8 + dl * kDc), S);
+    uint32_t bestR = kNoKey;
+#pragma unroll
+    for (int dk = 0; dk < kDc; ++dk) {  // an entry nobody wrote belongs to no candidate: never looked at
+      const int k = dl * kDc + dk, xl = xr + a.dmin + k;
+      bestR = min(bestR, k < a.D && xl >= lo && xl <= hi ? (S[dk] << 8) | (uint32_t)k : kNoKey);
+    }
+    for (int s = 1; s < a.nD; s <<= 1) bestR = min(bestR, (uint32_t)__shfl_xor((int)bestR, s, 64));
+    if (dl == 0 && xr <= x1 && bestR != kNoKey) kR[rowAt + xr] = (uint8_t)(bestR & 0xFFu);
   }
 }
 
@@ -356,6 +611,55 @@ StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) {
   return a;
 }
 
+int sgm_params_status(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
+  if (!p) return SSRLCV_ERR_INVALID_ARG;
+  if (p->radius == 0 || p->numDisparities == 0 || p->minDisparity < -32768 || p->minDisparity > 32767 || p->subpixel > 1 || p->P1 > p->P2 ||
+      p->paths == 0 || p->paths > 0xFFu)
+    return SSRLCV_ERR_INVALID_ARG;
+  if ((unsigned long long)w * h >= (1ull << 31)) return SSRLCV_ERR_INVALID_ARG;
+  if (p->radius > 15 || p->numDisparities > 256) return SSRLCV_ERR_UNSUPPORTED;
+  // M, L and S live in 16 bits: S <= popcount(paths) (costClamp + P2)
+  if ((unsigned long long)__builtin_popcount(p->paths) * ((unsigned long long)p->costClamp + p->P2) > 65535ull) return SSRLCV_ERR_UNSUPPORTED;
+  return SSRLCV_OK;
+}
+
+ssrlcv_stereo_params sgm_as_stereo(const ssrlcv_sgm_params* p) {
+  ssrlcv_stereo_params s;
+  s.radius = p->radius;
+  s.minDisparity = p->minDisparity;
+  s.numDisparities = p->numDisparities;
+  s.maxCost = 0xFFFFFFFFu;
+  s.lrTolerance = p->lrTolerance;
+  s.subpixel = p->subpixel;
+  return s;
+}
+
+// one volume: uint16 [h][w][8 nD], 8 nD = numDisparities rounded up to 8, 16, 32, .. 256
+size_t sgm_volume_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
+  size_t k8 = 8;
+  while (k8 < p->numDisparities) k8 <<= 1;
+  return align256((size_t)w * h * k8 * 2);
+}
+
+// ssrlcv_hip_stereo_sgm_set_pass_events: the events later calls record between their passes (tools/bench_sgm.py)
+constexpr uint32_t kSgmMaxEvents = 12;
+void* g_sgm_events[kSgmMaxEvents];
+uint32_t g_sgm_event_count = 0;
+
+template <bool FIRST>
+void sgm_launch_path(int dir, unsigned blocks, hipStream_t st, const SgmArgs& a) {
+  switch (dir) {
+    case 0: hipLaunchKernelGGL((k_sgm_path<1, 0, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_sgm_path<-1, 0, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_sgm_path<0, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_sgm_path<0, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_sgm_path<1, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 5: hipLaunchKernelGGL((k_sgm_path<-1, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    case 6: hipLaunchKernelGGL((k_sgm_path<1, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((k_sgm_path<-1, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,6 +694,82 @@ int ssrlcv_hip_stereo_sad_u8(const uint8_t* left, const uint8_t* right, uint32_t
       hipLaunchKernelGGL(k_stereo_sad<true>, grid, dim3(a.threads), lds, st, right, left, a, (float*)nullptr, (uint32_t*)nullptr, kR);
       hipLaunchKernelGGL(k_stereo_lr, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, kL, kR, (int)w, n, a.dmin, params->lrTolerance);
     }
+  }
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+size_t ssrlcv_hip_stereo_sgm_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params) {
+  if (sgm_params_status(w, h, params)) return 0;
+  return 2 * stereo_map_bytes(w, h) + 2 * sgm_volume_bytes(w, h, params) + 256;  // kL, kR, M, S
+}
+
+int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count) {
+  if (count > kSgmMaxEvents || (count && !events)) return SSRLCV_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < count; ++i) g_sgm_events[i] = events[i];
+  g_sgm_event_count = count;
+  return SSRLCV_OK;
+}
+
+int ssrlcv_hip_stereo_sgm_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
+                             void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream) {
+  const int rc = sgm_params_status(w, h, params);
+  if (rc) return rc;
+  if (!left || !right || !workspace || !disparity) return SSRLCV_ERR_INVALID_ARG;
+  if (workspaceBytes < ssrlcv_hip_stereo_sgm_workspace_bytes(w, h, params)) return SSRLCV_ERR_WORKSPACE;
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)w * h;
+  if (n == 0) return SSRLCV_OK;
+  unsigned fillBlocks = (unsigned)((n + 255) / 256);
+  if (fillBlocks > 2048u) fillBlocks = 2048u;
+  uint32_t marks = 0;
+  auto mark = [&]() {  // the next pass event, if the caller of set_pass_events asked for one
+    if (marks < g_sgm_event_count && g_sgm_events[marks]) (void)hipEventRecord((hipEvent_t)g_sgm_events[marks], st);
+    ++marks;
+  };
+  mark();
+  hipLaunchKernelGGL(k_stereo_fill, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, n);
+  const uint32_t side = 2 * params->radius + 1;
+  if (w >= side && h >= side) {  // else: no pixel has a window
+    const ssrlcv_stereo_params sp = sgm_as_stereo(params);
+    StereoArgs a = stereo_args(w, h, &sp);
+    uint8_t* kL = (uint8_t*)workspace;
+    uint8_t* kR = kL + stereo_map_bytes(w, h);
+    uint16_t* M = (uint16_t*)(kR + stereo_map_bytes(w, h));
+    uint16_t* S = (uint16_t*)((uint8_t*)M + sgm_volume_bytes(w, h, params));
+    a.maxCost = params->costClamp;  // the volume form's clamp
+    const int tilesY = ((int)h - 2 * a.r + a.TY - 1) / a.TY;
+    const size_t lds = (size_t)a.ring * (a.pitchB + a.pitchO);
+    hipLaunchKernelGGL((k_stereo_sad<false, true>), dim3((unsigned)(a.tilesX * tilesY)), dim3(a.threads), lds, st, left, right, a,
+                       reinterpret_cast<float*>(M), (uint32_t*)nullptr, (uint8_t*)nullptr);
+    mark();
+    SgmArgs g;
+    g.w = a.w; g.h = a.h; g.r = a.r;
+    g.wi = a.w - 2 * a.r; g.hi = a.h - 2 * a.r;
+    g.D = a.D; g.dmin = a.dmin; g.nD = a.nD; g.nDlog = a.nDlog; g.K8 = a.nD * kDc;
+    g.P1 = params->P1; g.P2 = params->P2;
+    g.subpixel = a.subpixel;
+    g.wantRight = params->lrTolerance >= 0 ? 1 : 0;
+    g.M = M; g.S = S;
+    bool first = true;
+    for (int dir = 0; dir < 8; ++dir) {
+      if (!((params->paths >> dir) & 1u)) continue;
+      g.nPaths = dir < 2 ? g.hi : dir < 4 ? g.wi : g.wi + g.hi - 1;
+      const unsigned blocks = (unsigned)(((size_t)g.nPaths * g.nD + 63) / 64);
+      if (first) sgm_launch_path<true>(dir, blocks, st, g);
+      else sgm_launch_path<false>(dir, blocks, st, g);
+      first = false;
+      mark();
+    }
+    int T = 16384 / g.K8;  // pixels of a row per block of the winner pass: a tile of 32 KB, 64 .. 1024 pixels
+    if (T > 1024) T = 1024;
+    const int strips = (g.wi + T - 1) / T;
+    hipLaunchKernelGGL(k_sgm_winners, dim3((unsigned)strips * (unsigned)g.hi), dim3(256), (size_t)T * g.K8 * 2, st, g, T, strips, disparity, cost,
+                       kL, kR);
+    mark();
+    if (params->lrTolerance >= 0)
+      hipLaunchKernelGGL(k_stereo_lr, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, kL, kR, (int)w, n, a.dmin, params->lrTolerance);
+    mark();
   }
   SSRLCV_LAUNCH_CHECK();
   return SSRLCV_OK;

@@ -9,6 +9,11 @@
 //   auto matches = factory.generateMatches(disparity, left, right);   // Unity<Match>, gpu: the sparse path's records
 //   auto cloud = PointCloudFactory().stereo_disparity(matches, foc, baseline, doffset);
 //
+// Semi-global matching over the same costs (include/ssrlcv_hip.h "semi-global matching") is one setter away; the maps and
+// everything after them are the same:
+//
+//   factory.setSemiGlobal(1000, 40, 400);           // costClamp, P1, P2, paths = 0xFF; clearSemiGlobal() returns to SAD winners
+//
 // An unrectified pair of pinhole Images goes through rectify() first (include/ssrlcv_hip.h "rectification"):
 //
 //   ptr::value<Image> leftR, rightR;
@@ -30,6 +35,8 @@ typedef ssrlcv_rectification Rectification;
 class DisparityFactory {
   ssrlcv_stereo_params params;
   unsigned int step = 1;
+  bool semiGlobal = false;
+  unsigned int sgmClamp = 0, sgmP1 = 0, sgmP2 = 0, sgmPaths = 0xFFu;
 
   static void toGpu(ptr::value<Image> image, MemoryState& origin, bool& keepHost) {
     if (image->colorDepth != 1) {
@@ -64,6 +71,16 @@ class DisparityFactory {
   void setLeftRightTolerance(int tolerance) { params.lrTolerance = tolerance; }  // < 0: no check
   void setSubpixel(bool on) { params.subpixel = on ? 1u : 0u; }
   void setStep(unsigned int s) { step = s; }  // generateMatches takes every s-th pixel of every s-th row
+  // generateDisparities aggregates the clamped costs along the directions of `paths` (ssrlcv_hip_stereo_sgm_u8) instead of
+  // taking each pixel's own winner; it has no cost limit, so maxCost must stay at "no limit"
+  void setSemiGlobal(unsigned int costClamp, unsigned int P1, unsigned int P2, unsigned int paths = 0xFFu) {
+    semiGlobal = true;
+    sgmClamp = costClamp;
+    sgmP1 = P1;
+    sgmP2 = P2;
+    sgmPaths = paths;
+  }
+  void clearSemiGlobal() { semiGlobal = false; }
 
   // disparity of every left pixel (row-major, w x h), in state gpu; `cost` (optional out) receives the winners' costs
   ptr::value<Unity<float>> generateDisparities(ptr::value<Image> left, ptr::value<Image> right,
@@ -73,9 +90,26 @@ class DisparityFactory {
       std::exit(-1);
     }
     const uint32_t w = left->size.x, h = left->size.y;
-    const size_t wsBytes = ssrlcv_hip_stereo_workspace_bytes(w, h, &params);
+    ssrlcv_sgm_params sgm;
+    sgm.radius = params.radius;
+    sgm.minDisparity = params.minDisparity;
+    sgm.numDisparities = params.numDisparities;
+    sgm.costClamp = sgmClamp;
+    sgm.P1 = sgmP1;
+    sgm.P2 = sgmP2;
+    sgm.paths = sgmPaths;
+    sgm.lrTolerance = params.lrTolerance;
+    sgm.subpixel = params.subpixel;
+    if (semiGlobal && params.maxCost != 0xFFFFFFFFu) {
+      logger.err << "ERROR: semi-global matching has no cost limit (setMaxCost(0xFFFFFFFF) or clearSemiGlobal())";
+      std::exit(-1);
+    }
+    const size_t wsBytes = semiGlobal ? ssrlcv_hip_stereo_sgm_workspace_bytes(w, h, &sgm) : ssrlcv_hip_stereo_workspace_bytes(w, h, &params);
     if (wsBytes == 0) {
-      logger.err << "ERROR: dense stereo parameters outside the contract (radius 1..15, 1..256 disparities from -32768..32767)";
+      if (semiGlobal)
+        logger.err << "ERROR: semi-global parameters outside the contract (P1 <= P2, paths 1..0xFF, popcount(paths) (costClamp + P2) <= 65535)";
+      else
+        logger.err << "ERROR: dense stereo parameters outside the contract (radius 1..15, 1..256 disparities from -32768..32767)";
       std::exit(-1);
     }
     MemoryState originL, originR;
@@ -87,8 +121,12 @@ class DisparityFactory {
     ptr::value<Unity<float>> disparity(nullptr, n ? n : 1ul, gpu);
     ptr::value<Unity<unsigned int>> costs;
     if (cost) costs = ptr::value<Unity<unsigned int>>(nullptr, n ? n : 1ul, gpu);
-    HipSafeCall(ssrlcv_hip_stereo_sad_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &params, workspace.get(), wsBytes,
-                                         disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
+    if (semiGlobal)
+      HipSafeCall(ssrlcv_hip_stereo_sgm_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &sgm, workspace.get(), wsBytes,
+                                           disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
+    else
+      HipSafeCall(ssrlcv_hip_stereo_sad_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &params, workspace.get(), wsBytes,
+                                           disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
     HipCheckError();
     HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
     restore(left, originL, keepL);

@@ -146,17 +146,39 @@ def stereo_disparity(left, right, radius=4, min_disparity=0, num_disparities=64,
     return capi.stereo_disparity(left, right, radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel, want_cost)
 
 
-def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, **disparity_args):
+def stereo_sgm(left, right, radius=2, min_disparity=0, num_disparities=64, cost_clamp=1000, p1=40, p2=400, paths=0xFF, lr_tolerance=1,
+               subpixel=True, want_cost=False):
+    """Dense stereo by semi-global matching on a rectified pair (u8 CUDA tensors (H, W)): the SAD costs of stereo_disparity,
+    clamped at cost_clamp, aggregated along the directions of the bit mask `paths` (0x0F: 4 paths, 0xFF: 8) with the penalties
+    p1 <= p2, then the winner, left-right check and sub-pixel step on the summed costs (include/ssrlcv_hip.h "semi-global
+    matching"; popcount(paths) (cost_clamp + p2) <= 65535).  -> (disparity float32 (H, W), cost or None) like stereo_disparity."""
+    return capi.stereo_sgm(left, right, radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, subpixel, want_cost)
+
+
+def _dense_disparity(left, right, sgm, disparity_args):
+    """stereo_cloud's and stereo_cloud_cameras' disparity map: SAD winners, or semi-global matching when sgm is a dict"""
+    if sgm is None:
+        return stereo_disparity(left, right, want_cost=False, **disparity_args)[0]
+    if "max_cost" in disparity_args:
+        raise TypeError("semi-global matching has no cost limit: max_cost cannot be combined with sgm")
+    unknown = set(sgm) - {"cost_clamp", "p1", "p2", "paths"}
+    if unknown or not {"cost_clamp", "p1", "p2"} <= set(sgm):
+        raise TypeError("sgm takes cost_clamp, p1, p2 and optionally paths")
+    return stereo_sgm(left, right, want_cost=False, **sgm, **disparity_args)[0]
+
+
+def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, **disparity_args):
     """Rectified pair -> dense cloud: stereo_disparity, then capi.stereo_matches (the valid pixels of the `step` grid as Match
     records), then capi.stereo_points (upstream's stereo_disparity: Z = foc baseline / (d + doffset)).  cx, cy default to the
     image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel
-    (the cost map is not computed: want_cost is not taken).  -> (points float32 (n, 3), Match bytes, n, disparity).
+    (the cost map is not computed: want_cost is not taken).  sgm = dict(cost_clamp=, p1=, p2=[, paths=]): the disparity comes
+    from stereo_sgm with the remaining disparity_args (max_cost is then a TypeError).  -> (points float32 (n, 3), Match bytes, n, disparity).
     The Match records are the sparse path's: with real cameras they also go through capi.matchset_from_matches and
     triangulate() unchanged (tests/test_gpu_stereo.py does)."""
     h, w = left.shape
     if "want_cost" in disparity_args:
         raise TypeError("stereo_cloud computes no cost map: call stereo_disparity for one")
-    disp, _ = stereo_disparity(left, right, want_cost=False, **disparity_args)
+    disp = _dense_disparity(left, right, sgm, disparity_args)
     matches, n = capi.stereo_matches(disp, step, left_id, right_id)
     pts = capi.stereo_points(matches, n, foc, baseline, doffset, w / 2.0 if cx is None else cx, h / 2.0 if cy is None else cy)
     return pts, matches, n, disp
@@ -172,17 +194,17 @@ def rectify_pair(left, right, cam_l, cam_r):
     return capi.warp_homography(left, rect["Hl"], shape), capi.warp_homography(right, rect["Hr"], shape), rect
 
 
-def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, **disparity_args):
+def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, **disparity_args):
     """Unrectified pair -> dense cloud in the world frame of triangulate()'s clouds: rectify_pair, stereo_disparity, the mask
     of the windows that left a source image (capi.stereo_mask_rectified), capi.stereo_matches, the records mapped back into
     source pixels (capi.matches_apply_homography), compacted, then capi.matchset_from_matches and the two-view triangulation
-    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args as for stereo_cloud.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
+    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args and sgm as for stereo_cloud.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
     matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
     if "want_cost" in disparity_args:
         raise TypeError("stereo_cloud_cameras computes no cost map: call stereo_disparity for one")
     left_r, right_r, rect = rectify_pair(left, right, cam_l, cam_r)
-    disp, _ = stereo_disparity(left_r, right_r, want_cost=False, **disparity_args)
-    capi.stereo_mask_rectified(disp, None, disparity_args.get("radius", 4), rect)
+    disp = _dense_disparity(left_r, right_r, sgm, disparity_args)
+    capi.stereo_mask_rectified(disp, None, disparity_args.get("radius", 4 if sgm is None else 2), rect)
     matches, n = capi.stereo_matches(disp, step, 0, 1)
     capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
     if n:
