@@ -570,22 +570,27 @@ def stereo_workspace(w, h, params):
     return dev_bytes(int(LIB.ssrlcv_hip_stereo_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(params))))
 
 
+def _stereo_call(entry, workspace_bytes, p, left_d, right_d, want_cost, workspace):
+    """what stereo_disparity and stereo_sgm share: `entry` on the pair with parameters `p`, the workspace reused if it is large
+    enough (`workspace_bytes` says how large).  -> (disparity, cost or None)"""
+    h, w = left_d.shape
+    assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
+    assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
+    need = int(workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
+    disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
+    check(entry(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()), ptr(disp), ptr(cost), stream_ptr()))
+    return disp, cost
+
+
 def stereo_disparity(left_d, right_d, radius=4, min_disparity=0, num_disparities=64, max_cost=STEREO_NO_LIMIT, lr_tolerance=1,
                      subpixel=True, want_cost=True, workspace=None):
     """SAD block matching (ssrlcv_hip_stereo_sad_u8) of two rectified u8 CUDA tensors (H, W).
     -> (disparity float32 (H, W), invalid pixels hold STEREO_INVALID_BITS; cost int32 (H, W) holding the uint32 bits, or
     None).  Asynchronous on the current stream."""
-    h, w = left_d.shape
-    assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
-    assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
     p = StereoParams(radius, min_disparity, num_disparities, max_cost, lr_tolerance, 1 if subpixel else 0)
-    need = int(LIB.ssrlcv_hip_stereo_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
-    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
-    disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
-    cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
-    check(LIB.ssrlcv_hip_stereo_sad_u8(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()),
-                                       ptr(disp), ptr(cost), stream_ptr()))
-    return disp, cost
+    return _stereo_call(LIB.ssrlcv_hip_stereo_sad_u8, LIB.ssrlcv_hip_stereo_workspace_bytes, p, left_d, right_d, want_cost, workspace)
 
 
 class SgmParams(ctypes.Structure):
@@ -599,17 +604,8 @@ def stereo_sgm(left_d, right_d, radius=2, min_disparity=0, num_disparities=64, c
     matching") of two rectified u8 CUDA tensors (H, W).  -> (disparity, cost or None) as stereo_disparity gives them; the cost
     is the winner's summed path cost.  The workspace holds two uint16 volumes of H W num_disparities entries each.
     Asynchronous on the current stream."""
-    h, w = left_d.shape
-    assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
-    assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
     p = SgmParams(radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, 1 if subpixel else 0)
-    need = int(LIB.ssrlcv_hip_stereo_sgm_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
-    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
-    disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
-    cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
-    check(LIB.ssrlcv_hip_stereo_sgm_u8(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()),
-                                       ptr(disp), ptr(cost), stream_ptr()))
-    return disp, cost
+    return _stereo_call(LIB.ssrlcv_hip_stereo_sgm_u8, LIB.ssrlcv_hip_stereo_sgm_workspace_bytes, p, left_d, right_d, want_cost, workspace)
 
 
 def stereo_sgm_set_pass_events(events):

@@ -13,15 +13,17 @@
 //                    2 ceil((2r + 1) / 4) SADs whatever the window's height.  The rows are staged with the strip's first
 //                    window column on a dword boundary, so every unaligned dword a lane needs is v_alignbyte_b32 of two
 //                    aligned ones at a compile-time shift; the window's last, partial dword is masked on both sides.
-//                    The winner of a pixel is one min over keys (cost << 8 | k): least cost, smallest disparity on ties;
-//                    the eight-disparity groups of a pixel sit in neighbouring lanes and meet through a shuffle butterfly;
-//                    the lane that owns the winner has its two neighbours' costs (its own registers, or one shuffle from
-//                    the next group) and writes the pixel: cost limit, sub-pixel offset, disparity, cost, k.
-//                    RIGHT = true is the same pass seen from the right image (partner at x + d): the right winners of the
-//                    left-right check, as a second pass (it runs only when the check is asked for).
+//                    The winner form takes the winner of every pixel (below) and writes it: cost limit, sub-pixel offset,
+//                    disparity, cost, k.  RIGHT = true is the same pass seen from the right image (partner at x + d): the
+//                    right winners of the left-right check, k alone, as a second pass (only when the check is asked for).
 //                    VOLUME = true is the cost pass of semi-global matching: the same march and the same 32 running sums,
-//                    but instead of choosing a winner a lane stores its eight costs of a column, clamped (costClamp, also
-//                    for a non-candidate), as eight uint16 in one 16-byte store into the volume M[y][x][k].
+//                    but a lane stores its eight costs of a column, clamped (costClamp, also for a non-candidate), as eight
+//                    uint16 in one 16-byte store (pack8) into the volume M[y][x][k].
+//   the winner       of a pixel, for k_stereo_sad over its window sums and for k_sgm_winners over S, either view: winner_key is
+//                    one min over keys (cost << 8 | k) of the candidates: least cost, smallest disparity on ties; the
+//                    eight-disparity groups of a pixel sit in neighbouring lanes and meet through a shuffle butterfly.  The
+//                    lane that owns the winner has the costs of k - 1 and k + 1 (its own registers, or edge_costs: one shuffle
+//                    from the next group) and winner_disparity adds the sub-pixel offset of the parabola through the three.
 //   k_stereo_lr      the left-right check over the two k maps
 //   k_sgm_path       semi-global matching (include/ssrlcv_hip.h "semi-global matching"; tests/sgm_ref.py restates it): one
 //                    direction's pass.  A group of nD lanes -- 8 disparities a lane, the SAD kernel's ownership -- owns ONE
@@ -29,16 +31,16 @@
 //                    waits for another.  The state L(q, .) lives in 32-bit registers; a step takes L(q, k -/+ 1) of the group's
 //                    edge disparities from the neighbouring lanes (one lane up, one down, the group's ends and k >= D
 //                    holding a sentinel no minimum picks and no penalty wraps) and min over k of L(q, k) through the xor
-//                    butterfly, both as DPP moves inside a row of 16 lanes (shuffles only for 32-lane groups).  The addresses of M and S along a path do not depend on the chain: the 16-byte loads of
-//                    the next kSgmAhead steps are in flight in a register ring while a step is computed, and S, read
-//                    ahead with M, is updated beside the chain (the first selected direction stores S, the others add).
+//                    butterfly, both as DPP moves inside a row of 16 lanes (shuffles only for 32-lane groups).  The
+//                    addresses of M and S along a path do not depend on the chain: the 16-byte loads of the next kSgmAhead
+//                    steps are in flight in a register ring while a step is computed, and S, read ahead with M, is
+//                    updated beside the chain (the first selected direction stores S, the others add).
 //                    Every pixel of the interior lies on exactly one path of a pass; the passes are ordered on the stream.
 //                    Diagonals are enumerated in coordinates flipped so that the direction is (+1, +1): wi paths start on
 //                    the first row, hi - 1 on the first column below it.
-//   k_sgm_winners    the left winner of every interior pixel from S over its candidates (the SAD kernel's key and
-//                    butterfly), the sub-pixel offset, both maps and kL; and, when the check is asked for, the right
-//                    winners into kR for k_stereo_lr: S(x' + d, y, d) reaches right pixel x' through an LDS tile of the
-//                    block's row strip, so S is read in whole 16-byte entries only
+//   k_sgm_winners    the left winner of every interior pixel from S over its candidates, both maps and kL; and, when the
+//                    check is asked for, the right winners into kR for k_stereo_lr: S(x' + d, y, d) reaches right pixel x'
+//                    through an LDS tile of the block's row strip, so S is read in whole 16-byte entries only
 //   StereoKeep / StereoEmit + compact.h   the valid pixels of the sampling grid as Match records, in raster order
 //   k_stereo_points  upstream's stereo_disparity
 #include <hip/hip_runtime.h>
@@ -70,6 +72,66 @@ struct StereoArgs {
   uint32_t maxCost;
   int subpixel;
 };
+
+// a lane's eight uint16 of a pixel's entry of either volume, as one 16-byte word
+__device__ __forceinline__ uint4 pack8(const uint32_t (&c)[kDc]) {
+  return make_uint4(c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16));
+}
+__device__ __forceinline__ void unpack8(const uint4& v, uint32_t (&o)[kDc]) {
+  o[0] = v.x & 0xFFFFu; o[1] = v.x >> 16;
+  o[2] = v.y & 0xFFFFu; o[3] = v.y >> 16;
+  o[4] = v.z & 0xFFFFu; o[5] = v.z >> 16;
+  o[6] = v.w & 0xFFFFu; o[7] = v.w >> 16;
+}
+
+// ---- the winner of a pixel.  `c`: the eight costs of lane dl of the pixel's nD lanes (k = 8 dl .. 8 dl + 7); cand[dk]: whether
+// k = 8 dl + dk is a candidate, eight bools or the bits of a mask.  Every lane of the group takes winner_key and edge_costs.
+struct CandidateBits {
+  uint32_t bits;
+  __device__ __forceinline__ bool operator[](int dk) const { return (bits >> dk) & 1u; }
+};
+// the pixel's least key, the same in all its lanes; kNoKey without a candidate
+template <class Cand>
+__device__ __forceinline__ uint32_t winner_key(const uint32_t (&c)[kDc], const Cand& cand, int dl, int nD) {
+  uint32_t best = kNoKey;
+#pragma unroll
+  for (int dk = 0; dk < kDc; ++dk) {
+    const uint32_t key = (c[dk] << 8) | (uint32_t)(dl * kDc + dk);
+    best = min(best, cand[dk] ? key : kNoKey);
+  }
+  for (int s = 1; s < nD; s <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, s, 64));
+  return best;
+}
+
+// the edge costs of the neighbouring lanes, for a winner at either end of a lane's eight
+struct EdgeCosts { uint32_t below, above; };
+__device__ __forceinline__ EdgeCosts edge_costs(const uint32_t (&c)[kDc]) {
+  return {(uint32_t)__shfl_up((int)c[kDc - 1], 1, 64), (uint32_t)__shfl_down((int)c[0], 1, 64)};
+}
+
+// the disparity of winner k of left pixel x, in the lane that owns it (Args: StereoArgs or SgmArgs)
+template <class Args>
+__device__ __forceinline__ float winner_disparity(const Args& a, const uint32_t (&c)[kDc], const EdgeCosts& edge, int k, uint32_t cost, int x) {
+  const int d = a.dmin + k;
+  float disp = (float)d;
+  if (a.subpixel) {
+    const int partner = x - d, lo = a.r, hi = a.w - 1 - a.r;
+    const bool hasM = k >= 1 && partner + 1 >= lo && partner + 1 <= hi;
+    const bool hasP = k + 1 < a.D && partner - 1 >= lo && partner - 1 <= hi;
+    if (hasM && hasP) {
+      const int idx = k & 7;
+      uint32_t cm = edge.below, cp = edge.above;
+#pragma unroll
+      for (int dk = 0; dk < kDc; ++dk) {  // not c[idx -/+ 1]: no run-time register index
+        if (idx == dk + 1) cm = c[dk];
+        if (idx + 1 == dk) cp = c[dk];
+      }
+      const int den = (int)cm - 2 * (int)cost + (int)cp;
+      if (den != 0) disp = (float)d + __fdiv_rn((float)((int)cm - (int)cp), (float)(2 * den));
+    }
+  }
+  return disp;
+}
 
 // horizontal sums of one staged row: acc[xi][dk] += sum over the window of |B - O|
 template <bool RIGHT>
@@ -107,13 +169,14 @@ __global__ __launch_bounds__(256) void k_stereo_fill(float* __restrict__ dispari
   }
 }
 
-// RIGHT = false: base = left image, other = right, partner of (x, d) at x - d; writes disparity, cost and kwin.
+// RIGHT = false: base = left image, other = right, partner of (x, d) at x - d; writes disparity, cost (or null) and kwin.
 // RIGHT = true:  base = right image, other = left, partner at x + d; writes kwin alone.
-// VOLUME = true: stores the clamped costs instead of choosing winners.  The arguments keep their places, so that the winner
-// form's code does not move: `disparity` carries the volume M (uint16 [y][x][nD * 8]), a.maxCost the clamp; cost, kwin unused.
+// VOLUME = true: stores the costs, clamped to `clamp`, into `volume` (uint16 [y][x][nD * 8]) instead of choosing winners.
+// Every output has its own parameter; those a form does not write are null.
 template <bool RIGHT, bool VOLUME = false>
 __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ base, const uint8_t* __restrict__ other, StereoArgs a,
-                                                    float* __restrict__ disparity, uint32_t* __restrict__ cost, uint8_t* __restrict__ kwin) {
+                                                    float* __restrict__ disparity, uint32_t* __restrict__ cost, uint8_t* __restrict__ kwin,
+                                                    uint16_t* __restrict__ volume, uint32_t clamp) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint8_t* sB = smem;                                   // [ring][pitchB]
   uint8_t* sO = smem + (size_t)a.ring * a.pitchB;       // [ring][pitchO]
@@ -216,64 +279,29 @@ __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ 
     if (y < Y0) continue;  // block-uniform: the window is not full yet
 
     if constexpr (VOLUME) {
-      uint16_t* volume = reinterpret_cast<uint16_t*>(disparity);
 #pragma unroll
       for (int xi = 0; xi < kXs; ++xi) {
         const int x = X0 + offB + xi;
         if (x <= a.w - 1 - a.r) {
           uint32_t c[kDc];
 #pragma unroll
-          for (int dk = 0; dk < kDc; ++dk) c[dk] = (valid[xi] >> dk) & 1u ? min(V[xi][dk], a.maxCost) : a.maxCost;
-          uint4 o;
-          o.x = c[0] | (c[1] << 16);
-          o.y = c[2] | (c[3] << 16);
-          o.z = c[4] | (c[5] << 16);
-          o.w = c[6] | (c[7] << 16);
-          *reinterpret_cast<uint4*>(volume + ((size_t)y * a.w + x) * Dtile + dl * kDc) = o;
+          for (int dk = 0; dk < kDc; ++dk) c[dk] = (valid[xi] >> dk) & 1u ? min(V[xi][dk], clamp) : clamp;
+          *reinterpret_cast<uint4*>(volume + ((size_t)y * a.w + x) * Dtile + dl * kDc) = pack8(c);
         }
       }
-      continue;
-    }
-
+    } else {
 #pragma unroll
-    for (int xi = 0; xi < kXs; ++xi) {
-      uint32_t best = kNoKey;
-#pragma unroll
-      for (int dk = 0; dk < kDc; ++dk) {
-        const uint32_t key = (V[xi][dk] << 8) | (uint32_t)(dl * kDc + dk);
-        best = min(best, (valid[xi] >> dk) & 1u ? key : kNoKey);
-      }
-      for (int s = 1; s < a.nD; s <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, s, 64));
-      // the edge costs of the neighbouring groups, for a winner at either end of a group
-      const uint32_t fromBelow = (uint32_t)__shfl_up((int)V[xi][kDc - 1], 1, 64);
-      const uint32_t fromAbove = (uint32_t)__shfl_down((int)V[xi][0], 1, 64);
-      const int k = (int)(best & 0xFFu);
-      if (best != kNoKey && (k >> 3) == dl) {
-        const int x = X0 + offB + xi;
-        const size_t p = (size_t)y * a.w + x;
-        kwin[p] = (uint8_t)k;
-        if (!RIGHT) {
+      for (int xi = 0; xi < kXs; ++xi) {
+        const uint32_t best = winner_key(V[xi], CandidateBits{valid[xi]}, dl, a.nD);
+        const EdgeCosts edge = edge_costs(V[xi]);
+        const int k = (int)(best & 0xFFu);
+        if (best != kNoKey && (k >> 3) == dl) {  // the lane that owns the winner writes the pixel
+          const int x = X0 + offB + xi;
+          const size_t p = (size_t)y * a.w + x;
+          kwin[p] = (uint8_t)k;
           const uint32_t c = best >> 8;
-          if (c <= a.maxCost) {
-            const int d = a.dmin + k;
-            float disp = (float)d;
-            if (a.subpixel) {
-              const int partner = x - d, lo = a.r, hi = a.w - 1 - a.r;
-              const bool hasM = k >= 1 && partner + 1 >= lo && partner + 1 <= hi;
-              const bool hasP = k + 1 < a.D && partner - 1 >= lo && partner - 1 <= hi;
-              if (hasM && hasP) {
-                const int idx = k & 7;
-                uint32_t cm = fromBelow, cp = fromAbove;
-#pragma unroll
-                for (int dk = 0; dk < kDc; ++dk) {
-                  if (idx == dk + 1) cm = V[xi][dk];
-                  if (idx + 1 == dk) cp = V[xi][dk];
-                }
-                const int den = (int)cm - 2 * (int)c + (int)cp;
-                if (den != 0) disp = (float)d + __fdiv_rn((float)((int)cm - (int)cp), (float)(2 * den));
-              }
-            }
-            disparity[p] = disp;
+          if (!RIGHT && c <= a.maxCost) {
+            disparity[p] = winner_disparity(a, V[xi], edge, k, c, x);
             if (cost) cost[p] = c;
           }
         }
@@ -310,13 +338,6 @@ struct SgmArgs {
   const uint16_t* M;
   uint16_t* S;
 };
-
-__device__ __forceinline__ void sgm_unpack(const uint4& v, uint32_t (&o)[kDc]) {
-  o[0] = v.x & 0xFFFFu; o[1] = v.x >> 16;
-  o[2] = v.y & 0xFFFFu; o[3] = v.y >> 16;
-  o[4] = v.z & 0xFFFFu; o[5] = v.z >> 16;
-  o[6] = v.w & 0xFFFFu; o[7] = v.w >> 16;
-}
 
 // One DPP move: lane i takes `v` of the lane CTRL names, or `old` where that lane does not exist (bound_ctrl off).
 template <int CTRL>
@@ -380,8 +401,8 @@ __global__ __launch_bounds__(64) void k_sgm_path(SgmArgs a) {
     for (int j = 0; j < kSgmAhead; ++j) {
       const int s = s0 + j;
       uint32_t Mk[kDc], Sk[kDc];
-      sgm_unpack(mq[j], Mk);
-      sgm_unpack(sq[j], Sk);
+      unpack8(mq[j], Mk);
+      unpack8(sq[j], Sk);
       if (s + kSgmAhead < len) {
         mq[j] = *reinterpret_cast<const uint4*>(a.M + at0 + (s + kSgmAhead) * stride);
         if (!FIRST) sq[j] = *reinterpret_cast<const uint4*>(a.S + at0 + (s + kSgmAhead) * stride);
@@ -419,12 +440,7 @@ __global__ __launch_bounds__(64) void k_sgm_path(SgmArgs a) {
         uint32_t o[kDc];
 #pragma unroll
         for (int dk = 0; dk < kDc; ++dk) o[dk] = (inD >> dk) & 1u ? (FIRST ? L[dk] : Sk[dk] + L[dk]) : 0u;  // <= 65535 (the host's bound)
-        uint4 ov;
-        ov.x = o[0] | (o[1] << 16);
-        ov.y = o[2] | (o[3] << 16);
-        ov.z = o[4] | (o[5] << 16);
-        ov.w = o[6] | (o[7] << 16);
-        *reinterpret_cast<uint4*>(a.S + at0 + s * stride) = ov;
+        *reinterpret_cast<uint4*>(a.S + at0 + s * stride) = pack8(o);
       }
     }
   }
@@ -456,42 +472,21 @@ __global__ __launch_bounds__(256) void k_sgm_winners(SgmArgs a, int T, int strip
     const bool there = x <= last;
     const size_t p = rowAt + (there ? x : first);
     uint32_t S[kDc];
-    sgm_unpack(*reinterpret_cast<const uint4*>(a.S + p * a.K8 + dl * kDc), S);
-    uint32_t best = kNoKey;
+    unpack8(*reinterpret_cast<const uint4*>(a.S + p * a.K8 + dl * kDc), S);
+    bool cand[kDc];
 #pragma unroll
     for (int dk = 0; dk < kDc; ++dk) {
       const int k = dl * kDc + dk, partner = x - (a.dmin + k);
-      const bool cand = k < a.D && partner >= lo && partner <= hi;
-      best = min(best, cand ? (S[dk] << 8) | (uint32_t)k : kNoKey);
-      if (a.wantRight && there && cand && partner >= x0 && partner <= x1) tile[(partner - x0) * a.K8 + k] = (uint16_t)S[dk];
+      cand[dk] = k < a.D && partner >= lo && partner <= hi;
+      if (a.wantRight && there && cand[dk] && partner >= x0 && partner <= x1) tile[(partner - x0) * a.K8 + k] = (uint16_t)S[dk];
     }
-    for (int s = 1; s < a.nD; s <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, s, 64));
-    const uint32_t fromBelow = (uint32_t)__shfl_up((int)S[kDc - 1], 1, 64);
-    const uint32_t fromAbove = (uint32_t)__shfl_down((int)S[0], 1, 64);
+    const uint32_t best = winner_key(S, cand, dl, a.nD);
+    const EdgeCosts edge = edge_costs(S);
     const int k = (int)(best & 0xFFu);
     if (there && x >= x0 && x <= x1 && best != kNoKey && (k >> 3) == dl) {
       kL[p] = (uint8_t)k;
-      const uint32_t c = best >> 8;
-      const int d = a.dmin + k;
-      float disp = (float)d;
-      if (a.subpixel) {
-        const int partner = x - d;
-        const bool hasM = k >= 1 && partner + 1 >= lo && partner + 1 <= hi;
-        const bool hasP = k + 1 < a.D && partner - 1 >= lo && partner - 1 <= hi;
-        if (hasM && hasP) {
-          const int idx = k & 7;
-          uint32_t cm = fromBelow, cp = fromAbove;
-#pragma unroll
-          for (int dk = 0; dk < kDc; ++dk) {
-            if (idx == dk + 1) cm = S[dk];
-            if (idx + 1 == dk) cp = S[dk];
-          }
-          const int den = (int)cm - 2 * (int)c + (int)cp;
-          if (den != 0) disp = (float)d + __fdiv_rn((float)((int)cm - (int)cp), (float)(2 * den));
-        }
-      }
-      disparity[p] = disp;
-      if (cost) cost[p] = c;
+      disparity[p] = winner_disparity(a, S, edge, k, best >> 8, x);
+      if (cost) cost[p] = best >> 8;
     }
   }
   if (!a.wantRight) return;  // block-uniform
@@ -499,14 +494,14 @@ __global__ __launch_bounds__(256) void k_sgm_winners(SgmArgs a, int T, int strip
   for (int t = pl; t < T; t += P) {  // T is a multiple of P: wave-uniform trip count
     const int xr = x0 + t;
     uint32_t S[kDc];
-    sgm_unpack(*reinterpret_cast<const uint4*>(tile + t * a.K8 + dl * kDc), S);
-    uint32_t bestR = kNoKey;
+    unpack8(*reinterpret_cast<const uint4*>(tile + t * a.K8 + dl * kDc), S);
+    bool cand[kDc];
 #pragma unroll
     for (int dk = 0; dk < kDc; ++dk) {  // an entry nobody wrote belongs to no candidate: never looked at
       const int k = dl * kDc + dk, xl = xr + a.dmin + k;
-      bestR = min(bestR, k < a.D && xl >= lo && xl <= hi ? (S[dk] << 8) | (uint32_t)k : kNoKey);
+      cand[dk] = k < a.D && xl >= lo && xl <= hi;
     }
-    for (int s = 1; s < a.nD; s <<= 1) bestR = min(bestR, (uint32_t)__shfl_xor((int)bestR, s, 64));
+    const uint32_t bestR = winner_key(S, cand, dl, a.nD);
     if (dl == 0 && xr <= x1 && bestR != kNoKey) kR[rowAt + xr] = (uint8_t)(bestR & 0xFFu);
   }
 }
@@ -564,30 +559,54 @@ __global__ __launch_bounds__(256) void k_stereo_points(const ssrlcv_match* __res
 }
 
 // ---- host side
-int stereo_params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) {
-  if (!p) return SSRLCV_ERR_INVALID_ARG;
-  if (p->radius == 0 || p->numDisparities == 0 || p->minDisparity < -32768 || p->minDisparity > 32767 || p->subpixel > 1)
+// The parameter check of both calls, in the contract's order: every invalid argument (the image size last), then what is
+// valid and unsupported.  `alsoInvalid` / `alsoUnsupported`: what semi-global matching adds to either tier.
+int params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p, bool alsoInvalid = false, bool alsoUnsupported = false) {
+  if (p.radius == 0 || p.numDisparities == 0 || p.minDisparity < -32768 || p.minDisparity > 32767 || p.subpixel > 1 || alsoInvalid)
     return SSRLCV_ERR_INVALID_ARG;
   if ((unsigned long long)w * h >= (1ull << 31)) return SSRLCV_ERR_INVALID_ARG;
-  if (p->radius > 15 || p->numDisparities > 256) return SSRLCV_ERR_UNSUPPORTED;
+  if (p.radius > 15 || p.numDisparities > 256 || alsoUnsupported) return SSRLCV_ERR_UNSUPPORTED;
   return SSRLCV_OK;
+}
+
+int stereo_params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) { return p ? params_status(w, h, *p) : SSRLCV_ERR_INVALID_ARG; }
+
+// dense stereo's share of the parameters: the cost limit is off, the winner pass of semi-global matching has none
+ssrlcv_stereo_params sgm_as_stereo(const ssrlcv_sgm_params& p) {
+  return {p.radius, p.minDisparity, p.numDisparities, 0xFFFFFFFFu, p.lrTolerance, p.subpixel};
+}
+
+int sgm_params_status(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
+  if (!p) return SSRLCV_ERR_INVALID_ARG;
+  // M, L and S live in 16 bits: S <= popcount(paths) (costClamp + P2)
+  const bool wide = (unsigned long long)__builtin_popcount(p->paths) * ((unsigned long long)p->costClamp + p->P2) > 65535ull;
+  return params_status(w, h, sgm_as_stereo(*p), p->P1 > p->P2 || p->paths == 0 || p->paths > 0xFFu, wide);
 }
 
 // samples 0, step, 2 step, ... below n: ceil(n / step) without the sum n + step - 1, which wraps for a step near 2^32
 uint32_t stereo_grid(uint32_t n, uint32_t step) { return n ? (n - 1) / step + 1 : 0; }
 
-size_t stereo_map_bytes(uint32_t w, uint32_t h) { return align256((size_t)w * h); }
+// The workspace of either call, as byte offsets: the winners' k of both views, one byte per pixel each, and for semi-global
+// matching (numDisparities != 0) the volumes M and S, uint16 [h][w][8 nD] each, 8 nD = numDisparities rounded up to 8, 16, .. 256.
+struct StereoLayout { size_t kL, kR, M, S, total; };
+StereoLayout stereo_layout(uint32_t w, uint32_t h, uint32_t numDisparities) {
+  const size_t map = align256((size_t)w * h);
+  size_t k8 = 8;
+  while (k8 < numDisparities) k8 <<= 1;
+  const size_t volume = numDisparities ? align256((size_t)w * h * k8 * 2) : 0;
+  return {0, map, 2 * map, 2 * map + volume, 2 * map + 2 * volume + 256};
+}
 
-StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) {
+StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p) {
   StereoArgs a;
   a.w = (int)w;
   a.h = (int)h;
-  a.r = (int)p->radius;
+  a.r = (int)p.radius;
   const int W = 2 * a.r + 1;
   a.G = (W + 3) / 4;
   a.remMask = W - 4 * (a.G - 1) == 1 ? 0xFFu : 0xFFFFFFu;  // W is odd: 1 or 3 bytes in the last dword
-  a.D = (int)p->numDisparities;
-  a.dmin = p->minDisparity;
+  a.D = (int)p.numDisparities;
+  a.dmin = p.minDisparity;
   a.nDlog = 0;
   while ((kDc << a.nDlog) < a.D) ++a.nDlog;
   a.nD = 1 << a.nDlog;                                     // 1 .. 32
@@ -606,58 +625,71 @@ StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) {
   if (segs > (hi + minRows - 1) / minRows) segs = (hi + minRows - 1) / minRows;
   if (segs < 1) segs = 1;
   a.TY = (hi + segs - 1) / segs;
-  a.maxCost = p->maxCost;
-  a.subpixel = (int)p->subpixel;
+  a.maxCost = p.maxCost;
+  a.subpixel = (int)p.subpixel;
   return a;
 }
 
-int sgm_params_status(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
-  if (!p) return SSRLCV_ERR_INVALID_ARG;
-  if (p->radius == 0 || p->numDisparities == 0 || p->minDisparity < -32768 || p->minDisparity > 32767 || p->subpixel > 1 || p->P1 > p->P2 ||
-      p->paths == 0 || p->paths > 0xFFu)
-    return SSRLCV_ERR_INVALID_ARG;
-  if ((unsigned long long)w * h >= (1ull << 31)) return SSRLCV_ERR_INVALID_ARG;
-  if (p->radius > 15 || p->numDisparities > 256) return SSRLCV_ERR_UNSUPPORTED;
-  // M, L and S live in 16 bits: S <= popcount(paths) (costClamp + P2)
-  if ((unsigned long long)__builtin_popcount(p->paths) * ((unsigned long long)p->costClamp + p->P2) > 65535ull) return SSRLCV_ERR_UNSUPPORTED;
-  return SSRLCV_OK;
+SgmArgs sgm_args(const StereoArgs& a, const ssrlcv_sgm_params& p, const uint16_t* M, uint16_t* S) {
+  SgmArgs g;
+  g.w = a.w; g.h = a.h; g.r = a.r;
+  g.wi = a.w - 2 * a.r; g.hi = a.h - 2 * a.r;
+  g.D = a.D; g.dmin = a.dmin; g.nD = a.nD; g.nDlog = a.nDlog; g.K8 = a.nD * kDc;
+  g.P1 = p.P1; g.P2 = p.P2;
+  g.nPaths = 0;  // set per direction
+  g.subpixel = a.subpixel; g.wantRight = p.lrTolerance >= 0 ? 1 : 0;
+  g.M = M; g.S = S;
+  return g;
 }
 
-ssrlcv_stereo_params sgm_as_stereo(const ssrlcv_sgm_params* p) {
-  ssrlcv_stereo_params s;
-  s.radius = p->radius;
-  s.minDisparity = p->minDisparity;
-  s.numDisparities = p->numDisparities;
-  s.maxCost = 0xFFFFFFFFu;
-  s.lrTolerance = p->lrTolerance;
-  s.subpixel = p->subpixel;
-  return s;
+template <bool RIGHT, bool VOLUME = false>
+void launch_sad(const StereoArgs& a, hipStream_t st, const uint8_t* base, const uint8_t* other, float* disparity, uint32_t* cost, uint8_t* kwin,
+                uint16_t* volume = nullptr, uint32_t clamp = 0) {
+  const int tilesY = (a.h - 2 * a.r + a.TY - 1) / a.TY;
+  const size_t lds = (size_t)a.ring * (a.pitchB + a.pitchO);
+  hipLaunchKernelGGL((k_stereo_sad<RIGHT, VOLUME>), dim3((unsigned)(a.tilesX * tilesY)), dim3(a.threads), lds, st, base, other, a, disparity, cost,
+                     kwin, volume, clamp);
 }
 
-// one volume: uint16 [h][w][8 nD], 8 nD = numDisparities rounded up to 8, 16, 32, .. 256
-size_t sgm_volume_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
-  size_t k8 = 8;
-  while (k8 < p->numDisparities) k8 <<= 1;
-  return align256((size_t)w * h * k8 * 2);
-}
+// the directions in the order of the `paths` bits, [first selected direction: it stores S][dir]
+using SgmPathKernel = void (*)(SgmArgs);
+const SgmPathKernel kSgmPath[2][8] = {
+    {k_sgm_path<1, 0, false>, k_sgm_path<-1, 0, false>, k_sgm_path<0, 1, false>, k_sgm_path<0, -1, false>,
+     k_sgm_path<1, 1, false>, k_sgm_path<-1, 1, false>, k_sgm_path<1, -1, false>, k_sgm_path<-1, -1, false>},
+    {k_sgm_path<1, 0, true>, k_sgm_path<-1, 0, true>, k_sgm_path<0, 1, true>, k_sgm_path<0, -1, true>,
+     k_sgm_path<1, 1, true>, k_sgm_path<-1, 1, true>, k_sgm_path<1, -1, true>, k_sgm_path<-1, -1, true>}};
 
 // ssrlcv_hip_stereo_sgm_set_pass_events: the events later calls record between their passes (tools/bench_sgm.py)
 constexpr uint32_t kSgmMaxEvents = 12;
 void* g_sgm_events[kSgmMaxEvents];
 uint32_t g_sgm_event_count = 0;
 
-template <bool FIRST>
-void sgm_launch_path(int dir, unsigned blocks, hipStream_t st, const SgmArgs& a) {
-  switch (dir) {
-    case 0: hipLaunchKernelGGL((k_sgm_path<1, 0, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 1: hipLaunchKernelGGL((k_sgm_path<-1, 0, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_sgm_path<0, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_sgm_path<0, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_sgm_path<1, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_sgm_path<-1, 1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_sgm_path<1, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_sgm_path<-1, -1, FIRST>), dim3(blocks), dim3(64), 0, st, a); break;
+// What both calls do around their passes, once the parameters have passed their check (first: its codes do not depend on the
+// buffers).  `sp`: dense stereo's share of the parameters.  `passes(a, kL, kR)` launches what leaves disparity, cost, kL and, when
+// the check is asked for, kR; `mark()` is called before the first launch and behind the last one.
+template <class Passes, class Mark>
+int stereo_call(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params& sp, const StereoLayout& lay,
+                void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, hipStream_t st, Passes passes, Mark mark) {
+  if (!left || !right || !workspace || !disparity) return SSRLCV_ERR_INVALID_ARG;
+  if (workspaceBytes < lay.total) return SSRLCV_ERR_WORKSPACE;
+  const size_t n = (size_t)w * h;
+  if (n == 0) return SSRLCV_OK;
+  unsigned fillBlocks = (unsigned)((n + 255) / 256);
+  if (fillBlocks > 2048u) fillBlocks = 2048u;
+  mark();
+  hipLaunchKernelGGL(k_stereo_fill, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, n);
+  const uint32_t side = 2 * sp.radius + 1;
+  if (w >= side && h >= side) {  // else: no pixel has a window
+    const StereoArgs a = stereo_args(w, h, sp);
+    uint8_t* kL = (uint8_t*)workspace + lay.kL;
+    uint8_t* kR = (uint8_t*)workspace + lay.kR;
+    passes(a, kL, kR);
+    if (sp.lrTolerance >= 0)
+      hipLaunchKernelGGL(k_stereo_lr, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, kL, kR, (int)w, n, a.dmin, sp.lrTolerance);
+    mark();
   }
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
 }
 
 }  // namespace
@@ -665,43 +697,24 @@ void sgm_launch_path(int dir, unsigned blocks, hipStream_t st, const SgmArgs& a)
 extern "C" {
 
 size_t ssrlcv_hip_stereo_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_stereo_params* params) {
-  if (stereo_params_status(w, h, params)) return 0;
-  return 2 * stereo_map_bytes(w, h) + 256;  // the winners' k of both views, one byte per pixel each
+  return stereo_params_status(w, h, params) ? 0 : stereo_layout(w, h, 0).total;
 }
 
 int ssrlcv_hip_stereo_sad_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params* params,
                              void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream) {
-  const int rc = stereo_params_status(w, h, params);  // the parameters first: their codes do not depend on the buffers
-  if (rc) return rc;
-  if (!left || !right || !workspace || !disparity) return SSRLCV_ERR_INVALID_ARG;
-  if (workspaceBytes < ssrlcv_hip_stereo_workspace_bytes(w, h, params)) return SSRLCV_ERR_WORKSPACE;
+  if (const int rc = stereo_params_status(w, h, params)) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)w * h;
-  if (n == 0) return SSRLCV_OK;
-  unsigned fillBlocks = (unsigned)((n + 255) / 256);
-  if (fillBlocks > 2048u) fillBlocks = 2048u;
-  hipLaunchKernelGGL(k_stereo_fill, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, n);
-  const uint32_t side = 2 * params->radius + 1;
-  if (w >= side && h >= side) {  // else: no pixel has a window
-    const StereoArgs a = stereo_args(w, h, params);
-    uint8_t* kL = (uint8_t*)workspace;
-    uint8_t* kR = kL + stereo_map_bytes(w, h);
-    const int tilesY = ((int)h - 2 * a.r + a.TY - 1) / a.TY;
-    const size_t lds = (size_t)a.ring * (a.pitchB + a.pitchO);
-    const dim3 grid((unsigned)(a.tilesX * tilesY));
-    hipLaunchKernelGGL(k_stereo_sad<false>, grid, dim3(a.threads), lds, st, left, right, a, disparity, cost, kL);
-    if (params->lrTolerance >= 0) {
-      hipLaunchKernelGGL(k_stereo_sad<true>, grid, dim3(a.threads), lds, st, right, left, a, (float*)nullptr, (uint32_t*)nullptr, kR);
-      hipLaunchKernelGGL(k_stereo_lr, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, kL, kR, (int)w, n, a.dmin, params->lrTolerance);
-    }
-  }
-  SSRLCV_LAUNCH_CHECK();
-  return SSRLCV_OK;
+  return stereo_call(
+      left, right, w, h, *params, stereo_layout(w, h, 0), workspace, workspaceBytes, disparity, cost, st,
+      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
+        launch_sad<false>(a, st, left, right, disparity, cost, kL);
+        if (params->lrTolerance >= 0) launch_sad<true>(a, st, right, left, nullptr, nullptr, kR);
+      },
+      [] {});
 }
 
 size_t ssrlcv_hip_stereo_sgm_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params) {
-  if (sgm_params_status(w, h, params)) return 0;
-  return 2 * stereo_map_bytes(w, h) + 2 * sgm_volume_bytes(w, h, params) + 256;  // kL, kR, M, S
+  return sgm_params_status(w, h, params) ? 0 : stereo_layout(w, h, params->numDisparities).total;
 }
 
 int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count) {
@@ -713,66 +726,39 @@ int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count) {
 
 int ssrlcv_hip_stereo_sgm_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
                              void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream) {
-  const int rc = sgm_params_status(w, h, params);
-  if (rc) return rc;
-  if (!left || !right || !workspace || !disparity) return SSRLCV_ERR_INVALID_ARG;
-  if (workspaceBytes < ssrlcv_hip_stereo_sgm_workspace_bytes(w, h, params)) return SSRLCV_ERR_WORKSPACE;
+  if (const int rc = sgm_params_status(w, h, params)) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)w * h;
-  if (n == 0) return SSRLCV_OK;
-  unsigned fillBlocks = (unsigned)((n + 255) / 256);
-  if (fillBlocks > 2048u) fillBlocks = 2048u;
+  const StereoLayout lay = stereo_layout(w, h, params->numDisparities);
   uint32_t marks = 0;
   auto mark = [&]() {  // the next pass event, if the caller of set_pass_events asked for one
     if (marks < g_sgm_event_count && g_sgm_events[marks]) (void)hipEventRecord((hipEvent_t)g_sgm_events[marks], st);
     ++marks;
   };
-  mark();
-  hipLaunchKernelGGL(k_stereo_fill, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, n);
-  const uint32_t side = 2 * params->radius + 1;
-  if (w >= side && h >= side) {  // else: no pixel has a window
-    const ssrlcv_stereo_params sp = sgm_as_stereo(params);
-    StereoArgs a = stereo_args(w, h, &sp);
-    uint8_t* kL = (uint8_t*)workspace;
-    uint8_t* kR = kL + stereo_map_bytes(w, h);
-    uint16_t* M = (uint16_t*)(kR + stereo_map_bytes(w, h));
-    uint16_t* S = (uint16_t*)((uint8_t*)M + sgm_volume_bytes(w, h, params));
-    a.maxCost = params->costClamp;  // the volume form's clamp
-    const int tilesY = ((int)h - 2 * a.r + a.TY - 1) / a.TY;
-    const size_t lds = (size_t)a.ring * (a.pitchB + a.pitchO);
-    hipLaunchKernelGGL((k_stereo_sad<false, true>), dim3((unsigned)(a.tilesX * tilesY)), dim3(a.threads), lds, st, left, right, a,
-                       reinterpret_cast<float*>(M), (uint32_t*)nullptr, (uint8_t*)nullptr);
-    mark();
-    SgmArgs g;
-    g.w = a.w; g.h = a.h; g.r = a.r;
-    g.wi = a.w - 2 * a.r; g.hi = a.h - 2 * a.r;
-    g.D = a.D; g.dmin = a.dmin; g.nD = a.nD; g.nDlog = a.nDlog; g.K8 = a.nD * kDc;
-    g.P1 = params->P1; g.P2 = params->P2;
-    g.subpixel = a.subpixel;
-    g.wantRight = params->lrTolerance >= 0 ? 1 : 0;
-    g.M = M; g.S = S;
-    bool first = true;
-    for (int dir = 0; dir < 8; ++dir) {
-      if (!((params->paths >> dir) & 1u)) continue;
-      g.nPaths = dir < 2 ? g.hi : dir < 4 ? g.wi : g.wi + g.hi - 1;
-      const unsigned blocks = (unsigned)(((size_t)g.nPaths * g.nD + 63) / 64);
-      if (first) sgm_launch_path<true>(dir, blocks, st, g);
-      else sgm_launch_path<false>(dir, blocks, st, g);
-      first = false;
-      mark();
-    }
-    int T = 16384 / g.K8;  // pixels of a row per block of the winner pass: a tile of 32 KB, 64 .. 1024 pixels
-    if (T > 1024) T = 1024;
-    const int strips = (g.wi + T - 1) / T;
-    hipLaunchKernelGGL(k_sgm_winners, dim3((unsigned)strips * (unsigned)g.hi), dim3(256), (size_t)T * g.K8 * 2, st, g, T, strips, disparity, cost,
-                       kL, kR);
-    mark();
-    if (params->lrTolerance >= 0)
-      hipLaunchKernelGGL(k_stereo_lr, dim3(fillBlocks), dim3(256), 0, st, disparity, cost, kL, kR, (int)w, n, a.dmin, params->lrTolerance);
-    mark();
-  }
-  SSRLCV_LAUNCH_CHECK();
-  return SSRLCV_OK;
+  return stereo_call(
+      left, right, w, h, sgm_as_stereo(*params), lay, workspace, workspaceBytes, disparity, cost, st,
+      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
+        uint16_t* M = (uint16_t*)((uint8_t*)workspace + lay.M);
+        uint16_t* S = (uint16_t*)((uint8_t*)workspace + lay.S);
+        launch_sad<false, true>(a, st, left, right, nullptr, nullptr, nullptr, M, params->costClamp);
+        mark();
+        SgmArgs g = sgm_args(a, *params, M, S);
+        bool first = true;
+        for (int dir = 0; dir < 8; ++dir) {
+          if (!((params->paths >> dir) & 1u)) continue;
+          g.nPaths = dir < 2 ? g.hi : dir < 4 ? g.wi : g.wi + g.hi - 1;
+          const unsigned blocks = (unsigned)(((size_t)g.nPaths * g.nD + 63) / 64);
+          hipLaunchKernelGGL(kSgmPath[first][dir], dim3(blocks), dim3(64), 0, st, g);
+          first = false;
+          mark();
+        }
+        int T = 16384 / g.K8;  // pixels of a row per block of the winner pass: a tile of 32 KB, 64 .. 1024 pixels
+        if (T > 1024) T = 1024;
+        const int strips = (g.wi + T - 1) / T;
+        hipLaunchKernelGGL(k_sgm_winners, dim3((unsigned)strips * (unsigned)g.hi), dim3(256), (size_t)T * g.K8 * 2, st, g, T, strips, disparity,
+                           cost, kL, kR);
+        mark();
+      },
+      mark);
 }
 
 size_t ssrlcv_hip_stereo_matches_workspace_bytes(uint32_t w, uint32_t h, uint32_t step) {

@@ -53,6 +53,8 @@ CASES = {
     "nd16_r12": _from("nd16_r12", 14000, 500, 2000, 0x0F, lr=1),   # 25 x 25 windows: four paths leave room for a clamp of 14000
     "all_256": _from("all_256", 1500, 50, 450),
     "two_wide_tiles": _from("two_wide_tiles", 1000, 40, 400, lr=0),
+    "edge_below": _from("edge_below", 1500, 60, 500),              # the winner pass's sub-pixel neighbour from the adjacent lane
+    "edge_above": _from("edge_above", 1500, 60, 500),
     # degenerate shapes
     "one_column": _from("one_column", 1000, 40, 400, lr=1, subpixel=1),
     "one_row": _from("one_row", 1000, 40, 400, lr=1, subpixel=1),

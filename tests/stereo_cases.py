@@ -36,6 +36,11 @@ CASES = {
     "two_wide_tiles": _c(290, 24, 1, 0, 12, lr=-1, subpixel=1, seed=7),
     "nd4_r7": _c(90, 50, 7, -2, 27, lr=0, subpixel=0, seed=8),
     "nd16_r12": _c(190, 60, 12, -40, 100, lr=-1, subpixel=1, seed=9),
+    # a sub-pixel winner at either end of a lane's eight disparities, in a 4-lane group: with the planes at d = 2 and 6, dmin = -2
+    # puts the near plane's winner on k = 8 (the cost of k - 1 comes from the lane below) and dmin = -5 the far plane's on k = 7
+    # (the cost of k + 1 comes from the lane above)
+    "edge_below": _c(96, 72, 2, -2, 20, lr=1, subpixel=1, seed=15),
+    "edge_above": _c(96, 72, 2, -5, 20, lr=1, subpixel=1, seed=16),
     # no left-right check, no sub-pixel, a cost limit on the scene
     "limit": _c(96, 72, 4, -1, 12, max_cost=400, lr=-1, subpixel=0, seed=2),
     # degenerate

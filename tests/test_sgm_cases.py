@@ -80,6 +80,14 @@ def test_two_cases_sit_on_the_bound_itself():
     assert 4 * (c.clamp + c.P2) == 65532                      # four paths: 16383 each is the most that fits
 
 
+@pytest.mark.parametrize("name", ["edge_below", "edge_above"])
+def test_the_edge_cases_take_a_neighbour_from_the_adjacent_lane(name):
+    """as tests/test_stereo_cases.py counts it, on the winners of the summed costs"""
+    from test_stereo_cases import edge_winners
+    n = edge_winners(C.reference(name), C.CASES[name], name)
+    assert n >= 1000, n                                       # measured 1102 and 4458
+
+
 def test_the_constant_band_is_what_aggregation_repairs():
     c = C.CASES["base_r1"]
     g, s = C.reference("base_r1"), SC.reference("base_r1")

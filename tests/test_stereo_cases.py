@@ -83,6 +83,21 @@ def test_the_scene_field_is_recovered(name):
     assert share(np.abs(ref["disparity"][v] - C.field(C.CASES[name])[v]) <= 0.5) >= 0.75
 
 
+def edge_winners(ref, case, name):
+    """the valid pixels of a reference whose disparity is not an integer and whose winner k sits at the end of a lane's eight
+    disparities that the case is named for: the other lane of the pixel's group holds the sub-pixel neighbour's cost"""
+    k = ref["k"]
+    moved = ref["valid"] & (ref["disparity"] != np.floor(ref["disparity"]))
+    at_edge = (k % 8 == 0) & (k >= 8) if name == "edge_below" else (k % 8 == 7) & (k + 1 < case.D)
+    return int((moved & at_edge).sum())
+
+
+@pytest.mark.parametrize("name", ["edge_below", "edge_above"])
+def test_the_edge_cases_take_a_neighbour_from_the_adjacent_lane(name):
+    n = edge_winners(C.reference(name), C.CASES[name], name)
+    assert n >= 1000, n                                       # measured 1106 and 3932
+
+
 def test_degenerate_cases():
     for name in ("narrower_than_window", "lower_than_window"):
         assert not C.reference(name)["has"].any()
