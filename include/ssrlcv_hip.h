@@ -818,8 +818,16 @@ int ssrlcv_sift_plan_overflow(const ssrlcv_sift_plan* plan, const void* workspac
  * valid only for the last octave processed unless the plan keeps all levels).  minmax_dev: device pointer to {min,max}. */
 int ssrlcv_sift_plan_level(const ssrlcv_sift_plan* plan, void* workspace, int kind, int octave, int blur, float** data,
                            uint32_t* w, uint32_t* h, float** minmax_dev);
-/* Device key-point list of an octave after ssrlcv_hip_sift_describe: pointer, count pointer, blur-index pointer
- * (6 ints: extremaBlurIndices[0..4] + total). */
+/* Device key-point list of an octave after ssrlcv_hip_sift_describe or any ssrlcv_hip_sift_stage call: the list and the
+ * octave's state words (8 ints: extremaBlurIndices[0..4], the count n, hasExtrema, overflow).
+ * Both may be WRITTEN between two stage calls (behind a synchronisation of the stream, and before the next call): the next
+ * stage runs on what it finds; stage 7 books the features from the state words.  The writer keeps what the kernels rely
+ * on: blur in 1..3 for every key point (the levels that have gradient tables), the list sorted by blur and the indices
+ * its ordered partition (idx[0] = idx[1] = 0), n at most the list capacity (ssrlcv_sift_params.maxKeyPointsPerOctave),
+ * hasExtrema = (n > 0), overflow = 0, discard = 0, sigma / pixelWidth below 8, and every key point inside checkKeyPoints'
+ * window at the plan's descriptorContribWidth (src/SIFT_FeatureFactory.cu:449-461, evaluated in float32): the sampling
+ * kernels do not re-check it.  A key point whose orientation window leaves the level is legal and gets no orientation.
+ * tests/test_gpu_sampling.py drives the sampling kernels this way. */
 int ssrlcv_sift_plan_keypoints(const ssrlcv_sift_plan* plan, void* workspace, int octave, ssrlcv_sskeypoint** list,
                                int** blurIndices_dev);
 /* Debug/test control: stop the key-point stage after `stage` (0 raw extrema, 1 removeNoise(0.8 thr), 2 refine,

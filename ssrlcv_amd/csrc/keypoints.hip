@@ -418,6 +418,9 @@ __global__ __launch_bounds__(256) void k_polar(PolarJobs jobs) {
     if (tile == 0) {  // the zero entries around the table (see svp::polar_level_stride)
       if (t == 0) lvlOut[0] = make_float2(0.0f, 0.0f);
       for (int i = t; i < W + 1; i += 256) lvlOut[1 + (size_t)W * H + i] = make_float2(0.0f, 0.0f);
+      // row -1 of level 1 (flat indices -W - 1 .. -2): svp::polar_front_pad; for levels 2 and 3 it is the run just written
+      if (lvl == 1)
+        for (int i = t; i < W + 1; i += 256) lvlOut[-1 - i] = make_float2(0.0f, 0.0f);
     }
     if (x < W) {
       float2* __restrict__ o = lvlOut + 1 + (size_t)y0 * W + x;
@@ -454,7 +457,7 @@ __device__ __forceinline__ int round_pos(float v) {
 // fmodf(v, p) for -p < v < 2p, exact: fmod is an exact operation and v - p is exact for p <= v < 2p (Sterbenz).  That
 // range is all the sampling kernels feed it: atan2 in [-pi, pi], theta in [0, 2 pi), plus 2 pi.
 __device__ __forceinline__ float fmod_2pi_above(float v, float p) { return v >= p ? v - p : v; }
-// pixel (x, y) of a polar table by its flat index y * W + x (-1 .. W*H + W: see svp::polar_level_stride; `pl` points at
+// pixel (x, y) of a polar table by its flat index y * W + x (-W - 1 .. W*H + W: see svp::polar_level_stride; `pl` points at
 // flat index 0): the index fits 32 bits for any level up to 32768^2, which keeps the multiply 32-bit
 __device__ __forceinline__ float2 polar_px(const float2* __restrict__ pl, int W, int x, int y) {
   return pl[y * W + x];

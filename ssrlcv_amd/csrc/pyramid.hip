@@ -2108,6 +2108,7 @@ int ssrlcv_sift_plan_create(uint32_t w, uint32_t h, const ssrlcv_sift_params* pa
     }
     size_t P = (size_t)ow * oh;
     oc.off_flags = take(P);
+    (void)take(svp::polar_front_pad(oc.w) * 8);  // zero entries in front of level 1's table: row -1 of a descriptor window
     oc.off_polar = take(svp::polar_level_stride(oc.w, oc.h) * 3 * 8);
     uint32_t cap = params->maxKeyPointsPerOctave ? params->maxKeyPointsPerOctave : (uint32_t)(P / 16);
     if (cap < 4096) cap = 4096;

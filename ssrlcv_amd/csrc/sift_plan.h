@@ -50,7 +50,12 @@ struct OctaveState {
 // row, as upstream) or one row below it and column -1 of row 0 (upstream: a read outside the array, undefined).  Each
 // level's table therefore carries one zero entry in front and W + 1 behind: an outside read returns a zero gradient,
 // which votes nothing -- the definition the oracle uses too.  Entry of flat index i of level l: l * stride + 1 + i.
+// The window can also reach ROW -1 (a key point at y = sigma lambda / pixelWidth exactly, whose ceiling is more than half
+// a pixel larger), flat indices -W - 1 .. -2: for levels 2 and 3 those are the zero entries behind the level in front of
+// them; level 1 has polar_front_pad zero entries of its own in front of the tables (k_polar writes them), a multiple of
+// 256 bytes so that the tables keep their alignment.
 __host__ __device__ inline size_t polar_level_stride(uint32_t w, uint32_t h) { return (size_t)w * h + w + 2; }
+__host__ __device__ inline size_t polar_front_pad(uint32_t w) { return ((size_t)w + 1 + 31) / 32 * 32; }
 
 struct OctavePlan {
   uint32_t w, h;
@@ -60,7 +65,7 @@ struct OctavePlan {
   float weights[kGauss][kMaxTaps];
   uint32_t cap;            // key-point list capacity
   size_t off_flags;
-  size_t off_polar;        // float2 {|grad|, atan2} of the normalised DoG levels 1..3 (3 * polar_level_stride * 8 bytes)
+  size_t off_polar;        // float2 {|grad|, atan2} of the normalised DoG levels 1..3 (3 * polar_level_stride * 8 bytes), behind polar_front_pad zero entries
   size_t off_kpA, off_kpB; // SSKeyPoint ping-pong lists
   size_t off_theta;        // cap * kMaxOrient floats
   size_t off_thetaCnt;     // cap uint32 (number of orientations per key point)

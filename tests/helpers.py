@@ -435,6 +435,29 @@ class OracleSift:
         return f
 
 
+def oracle_thetas(lib, level, pixel_width, lam, kp, max_orientations, thr):
+    """oracle_compute_thetas of ONE SSKEYPOINT record on a (twice-normalised DoG) level -> its valid thetas, strongest first
+    (float32 array, possibly empty)"""
+    lvl = np.ascontiguousarray(level, np.float32)
+    h, w = lvl.shape
+    rec = np.ascontiguousarray(np.asarray(kp, SSKEYPOINT).reshape(1))
+    thetas, valid = np.zeros(8, np.float32), np.zeros(8, np.int32)
+    lib.oracle_compute_thetas(P(lvl), ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.c_float(pixel_width), ctypes.c_float(lam),
+                              P(rec), ctypes.c_uint32(max_orientations), ctypes.c_float(thr), P(thetas), P(valid))
+    return thetas[:max_orientations][valid[:max_orientations] != 0].copy()
+
+
+def oracle_descriptor(lib, level, pixel_width, lam, kp):
+    """oracle_fill_descriptor of ONE oriented SSKEYPOINT record on a level -> FEATURE[1]"""
+    lvl = np.ascontiguousarray(level, np.float32)
+    h, w = lvl.shape
+    rec = np.ascontiguousarray(np.asarray(kp, SSKEYPOINT).reshape(1))
+    out = np.zeros(1, FEATURE)
+    lib.oracle_fill_descriptor(P(lvl), ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.c_float(pixel_width), ctypes.c_float(lam),
+                               P(rec), P(out))
+    return out
+
+
 def oracle_gauss_kernel(lib, sigma, pixel_width):
     w = np.zeros(257, np.float32)
     lib.oracle_gauss_kernel.restype = ctypes.c_int
