@@ -48,7 +48,9 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      dense SIFT: sift_dense_grid, sift_dense_max_features, sift_dense_workspace_bytes, sift_dense_u8;
  *      dense stereo: stereo_workspace_bytes, stereo_sad_u8, stereo_matches_workspace_bytes, stereo_matches, stereo_points;
  *      rectification: rectify_cameras_host, warp_homography_u8, stereo_mask_rectified, matches_apply_homography;
- *      semi-global matching: stereo_sgm_workspace_bytes, stereo_sgm_u8, stereo_sgm_set_pass_events */
+ *      semi-global matching: stereo_sgm_workspace_bytes, stereo_sgm_u8, stereo_sgm_set_pass_events;
+ *      census cost: census_u8, stereo_census_workspace_bytes, stereo_census_u8, stereo_sgm_census_workspace_bytes,
+ *      stereo_sgm_census_u8 */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -635,8 +637,9 @@ int ssrlcv_hip_sift_dense_u8(const uint8_t* pixels, uint32_t w, uint32_t h, cons
  * workspace.  An image smaller than one window is no error: every pixel is invalid.
  * Workspace (ssrlcv_hip_stereo_workspace_bytes; host only; 0 for parameters the call refuses): two bytes per pixel, the
  * winners' k of the two views.  Asynchronous on `stream`; no host synchronisation; no atomics: bit-equal run to run.
- * Out of scope here: a uniqueness ratio, colour, census or NCC costs.  Aggregating these costs along paths is the next
- * section, "semi-global matching".  (An unrectified pair of pinhole cameras is rectified first: "rectification" below.) */
+ * Out of scope here: a uniqueness ratio, colour or NCC costs (census costs: the section "census cost" below).  Aggregating
+ * these costs along paths is the next section, "semi-global matching".  (An unrectified pair of pinhole cameras is rectified
+ * first: "rectification" below.) */
 typedef struct {
   uint32_t radius;          /* r in 1..15; the window is (2r + 1)^2.  Upstream's five sizes: r = 1, 4, 7, 12, 15 */
   int32_t minDisparity;     /* -32768 .. 32767 */
@@ -702,7 +705,8 @@ int ssrlcv_hip_stereo_points(const ssrlcv_match* matches, uint32_t n, float foc,
  *     2 a256(w h) + 2 a256(2 w h K) + 256 bytes
  * -- the winners' k of the two views and the two uint16 volumes M and S, [y][x][k] (at 4096 x 4096, D = 64: 2 x 2.1 GB).
  * Asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.
- * Out of scope: a uniqueness ratio, colour, census or NCC costs, more than 8 paths, penalties adapted to the image gradient. */
+ * Out of scope: a uniqueness ratio, colour or NCC costs (census costs: the section "census cost" below), more than 8 paths,
+ * penalties adapted to the image gradient. */
 typedef struct {
   uint32_t radius;          /* 1..15 */
   int32_t minDisparity;     /* -32768 .. 32767 */
@@ -722,6 +726,56 @@ int ssrlcv_hip_stereo_sgm_u8(const uint8_t* left, const uint8_t* right, uint32_t
  * one behind the winner pass and one behind the left-right check (at most 12).  count 0 removes the hook; count > 12 or events
  * NULL with count > 0: SSRLCV_ERR_INVALID_ARG.  The caller keeps the events alive until it removes the hook. */
 int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count);
+
+/* ---- census cost: the census transform of both views and the Hamming distance of the codes as the matching cost of dense
+ * stereo and of semi-global matching, in place of the sum of absolute differences.  A code keeps only which neighbours are
+ * darker than the centre, so the cost does not change under any strictly increasing map of either image's grey levels: two
+ * exposures, two gains, the softening of a bilinear warp.  Integer arithmetic throughout: the kernels of csrc/stereo.hip are
+ * held to a numpy restatement bit for bit (tests/census_ref.py, tests/test_gpu_census.py).
+ *   parameters  c = censusRadius, 1, 2 or 3: the census window is (2c + 1)^2 and a code has n = 8, 24 or 48 bits.
+ *               r = params->radius is the AGGREGATION radius in these calls, 0 .. 7; r = 0 is legal here: the cost of a pixel
+ *               is its own Hamming distance, the usual form under semi-global matching.
+ *               rho = r + c is the footprint radius, at most 10.
+ *   1 census    for c <= x <= w - 1 - c and c <= y <= h - 1 - c: number the window's offsets (i, j), the centre skipped, as
+ *               b = 0 .. n - 1 with j = -c .. c outer and i = -c .. c inner; bit b of T(x, y) is 1 iff I(x + i, y + j) < I(x, y),
+ *               strictly.  T is a uint64 with bit b at 2^b and the upper bits zero.  Everywhere else the exported map holds 0;
+ *               no cost ever reads those entries.
+ *   2 Hamming   H(x, y, d) = popcount(T_L(x, y) xor T_R(x - d, y)).
+ *   3 cost      C(x, y, d) = sum over |i| <= r, |j| <= r of H(x + i, y + j, d): an integer, at most n (2r + 1)^2 <= 10800.
+ *               Defined only where rho <= x <= w - 1 - rho, rho <= y <= h - 1 - rho and rho <= x - d <= w - 1 - rho; elsewhere d
+ *               is not a candidate of (x, y).  No border is replicated.
+ *   4 the rest  is the existing text with this C, and rho wherever it says r: items 2-6 of "dense stereo" (the winner, the
+ *               smallest d on ties, maxCost, the left-right check from the right view's winners over the same C, the sub-pixel
+ *               parabola, both maps fully written) for ssrlcv_hip_stereo_census_u8; items 1-8 of "semi-global matching" with
+ *               I = [rho, w - 1 - rho] x [rho, h - 1 - rho] and the bound popcount(paths) (costClamp + P2) <= 65535 unchanged for
+ *               ssrlcv_hip_stereo_sgm_census_u8.  C fits 16 bits without a clamp: costClamp >= n (2r + 1)^2 cuts nothing.
+ * Refusals keep the order of the SAD calls, the parameters before the buffers and invalid before unsupported:
+ * SSRLCV_ERR_INVALID_ARG for params NULL, censusRadius 0 (it takes the place of radius 0, which is no error here), and every
+ * other invalid parameter of the SAD call, w h >= 2^31 last; SSRLCV_ERR_UNSUPPORTED for censusRadius > 3 or radius > 7 (in
+ * place of radius > 15), numDisparities > 256 and the 16-bit bound; then SSRLCV_ERR_INVALID_ARG for a NULL buffer (cost may be
+ * NULL) and SSRLCV_ERR_WORKSPACE for a short workspace.  An image smaller than the footprint is no error: every pixel is
+ * invalid.
+ * Workspace (host only; 0 for parameters the call refuses; computed in size_t): the SAD call's layout plus the code maps of
+ * the two views, uint64 [h][w] each:
+ *     block matching         2 a256(w h) + 256 + 2 a256(8 w h) bytes
+ *     semi-global matching   2 a256(w h) + 2 a256(2 w h K) + 256 + 2 a256(8 w h) bytes
+ * The caller's workspace pointer is at least 8-byte aligned (any device allocation is).  Asynchronous on `stream`; no host
+ * synchronisation; no atomics; no block waits for another: bit-equal run to run.
+ * ssrlcv_hip_census_u8 is the per-kernel export of item 1: it writes every entry of codes[w h].  SSRLCV_ERR_INVALID_ARG for
+ * censusRadius 0 or w h >= 2^31, SSRLCV_ERR_UNSUPPORTED for censusRadius > 3, then SSRLCV_ERR_INVALID_ARG for a NULL buffer.
+ * The pass-events hook of ssrlcv_hip_stereo_sgm_set_pass_events applies to ssrlcv_hip_stereo_sgm_census_u8 with the same
+ * marks; the two census passes count into mark [1], "behind the fill and the cost pass".
+ * Still out of scope: census windows that are not square (9 x 7), the centre-symmetric and the ternary census, colour, NCC
+ * costs, a uniqueness ratio. */
+int ssrlcv_hip_census_u8(const uint8_t* image, uint32_t w, uint32_t h, uint32_t censusRadius, uint64_t* codes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_stereo_census_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_stereo_params* params, uint32_t censusRadius);
+int ssrlcv_hip_stereo_census_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params* params,
+                                uint32_t censusRadius, void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost,
+                                ssrlcv_stream_t stream);
+size_t ssrlcv_hip_stereo_sgm_census_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params, uint32_t censusRadius);
+int ssrlcv_hip_stereo_sgm_census_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
+                                    uint32_t censusRadius, void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost,
+                                    ssrlcv_stream_t stream);
 
 /* ---- rectification: a converging pair of Image::Camera records -> two homographies -> a rectified pair for the dense stereo
  * above, and its matches back in source pixels, where they triangulate with the original cameras into the sparse path's world

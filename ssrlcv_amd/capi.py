@@ -570,27 +570,47 @@ def stereo_workspace(w, h, params):
     return dev_bytes(int(LIB.ssrlcv_hip_stereo_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(params))))
 
 
-def _stereo_call(entry, workspace_bytes, p, left_d, right_d, want_cost, workspace):
-    """what stereo_disparity and stereo_sgm share: `entry` on the pair with parameters `p`, the workspace reused if it is large
-    enough (`workspace_bytes` says how large).  -> (disparity, cost or None)"""
+def _stereo_call(entries, p, left_d, right_d, want_cost, workspace, census):
+    """what stereo_disparity and stereo_sgm share: the call on the pair with parameters `p`, the workspace reused if it is
+    large enough.  entries = ((SAD call, its workspace query), (census call, its workspace query)): census = 0 takes the first
+    pair, a census radius the second, which takes the radius behind the parameters.  -> (disparity, cost or None)"""
     h, w = left_d.shape
     assert right_d.shape == left_d.shape and left_d.dtype == torch.uint8 and right_d.dtype == torch.uint8
     assert left_d.is_cuda and right_d.is_cuda and left_d.is_contiguous() and right_d.is_contiguous()  # read with pitch w
-    need = int(workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    assert isinstance(census, int) and not isinstance(census, bool) and 0 <= census <= 0xFFFFFFFF  # c_u32 would wrap or truncate it
+    entry, workspace_bytes = entries[1 if census else 0]
+    extra = (c_u32(census),) if census else ()
+    need = int(workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p), *extra))
     ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
     disp = torch.empty((h, w), dtype=torch.float32, device="cuda")
     cost = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_cost else None
-    check(entry(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()), ptr(disp), ptr(cost), stream_ptr()))
+    check(entry(ptr(left_d), ptr(right_d), c_u32(w), c_u32(h), ctypes.byref(p), *extra, ptr(ws), c_sz(ws.numel()), ptr(disp), ptr(cost),
+                stream_ptr()))
     return disp, cost
 
 
 def stereo_disparity(left_d, right_d, radius=4, min_disparity=0, num_disparities=64, max_cost=STEREO_NO_LIMIT, lr_tolerance=1,
-                     subpixel=True, want_cost=True, workspace=None):
-    """SAD block matching (ssrlcv_hip_stereo_sad_u8) of two rectified u8 CUDA tensors (H, W).
+                     subpixel=True, want_cost=True, workspace=None, census=0):
+    """Block matching of two rectified u8 CUDA tensors (H, W): SAD (ssrlcv_hip_stereo_sad_u8), or with census = 1, 2 or 3 the
+    census cost of that radius (ssrlcv_hip_stereo_census_u8; include/ssrlcv_hip.h "census cost"), `radius` then being the
+    aggregation radius 0 .. 7.
     -> (disparity float32 (H, W), invalid pixels hold STEREO_INVALID_BITS; cost int32 (H, W) holding the uint32 bits, or
     None).  Asynchronous on the current stream."""
     p = StereoParams(radius, min_disparity, num_disparities, max_cost, lr_tolerance, 1 if subpixel else 0)
-    return _stereo_call(LIB.ssrlcv_hip_stereo_sad_u8, LIB.ssrlcv_hip_stereo_workspace_bytes, p, left_d, right_d, want_cost, workspace)
+    return _stereo_call(((LIB.ssrlcv_hip_stereo_sad_u8, LIB.ssrlcv_hip_stereo_workspace_bytes),
+                         (LIB.ssrlcv_hip_stereo_census_u8, LIB.ssrlcv_hip_stereo_census_workspace_bytes)), p, left_d, right_d, want_cost,
+                        workspace, census)
+
+
+def census(img_d, census):
+    """The census codes of a u8 CUDA tensor (H, W) (ssrlcv_hip_census_u8; include/ssrlcv_hip.h "census cost" item 1), census =
+    1, 2 or 3 -> int64 (H, W) holding the uint64 bits.  Asynchronous on the current stream."""
+    assert img_d.dim() == 2 and img_d.dtype == torch.uint8 and img_d.is_cuda and img_d.is_contiguous()  # read with pitch w
+    assert isinstance(census, int) and not isinstance(census, bool) and 0 <= census <= 0xFFFFFFFF
+    h, w = img_d.shape
+    codes = torch.empty((h, w), dtype=torch.int64, device="cuda")
+    check(LIB.ssrlcv_hip_census_u8(ptr(img_d), c_u32(w), c_u32(h), c_u32(census), ptr(codes), stream_ptr()))
+    return codes
 
 
 class SgmParams(ctypes.Structure):
@@ -599,13 +619,16 @@ class SgmParams(ctypes.Structure):
 
 
 def stereo_sgm(left_d, right_d, radius=2, min_disparity=0, num_disparities=64, cost_clamp=1000, p1=40, p2=400, paths=0xFF,
-               lr_tolerance=1, subpixel=True, want_cost=False, workspace=None):
+               lr_tolerance=1, subpixel=True, want_cost=False, workspace=None, census=0):
     """Semi-global matching over the clamped SAD costs (ssrlcv_hip_stereo_sgm_u8; include/ssrlcv_hip.h "semi-global
-    matching") of two rectified u8 CUDA tensors (H, W).  -> (disparity, cost or None) as stereo_disparity gives them; the cost
-    is the winner's summed path cost.  The workspace holds two uint16 volumes of H W num_disparities entries each.
-    Asynchronous on the current stream."""
+    matching") of two rectified u8 CUDA tensors (H, W), or with census = 1, 2 or 3 over the census costs of that radius
+    (ssrlcv_hip_stereo_sgm_census_u8; "census cost"), `radius` then being the aggregation radius 0 .. 7.  -> (disparity, cost or
+    None) as stereo_disparity gives them; the cost is the winner's summed path cost.  The workspace holds two uint16 volumes of
+    H W num_disparities entries each.  Asynchronous on the current stream."""
     p = SgmParams(radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, 1 if subpixel else 0)
-    return _stereo_call(LIB.ssrlcv_hip_stereo_sgm_u8, LIB.ssrlcv_hip_stereo_sgm_workspace_bytes, p, left_d, right_d, want_cost, workspace)
+    return _stereo_call(((LIB.ssrlcv_hip_stereo_sgm_u8, LIB.ssrlcv_hip_stereo_sgm_workspace_bytes),
+                         (LIB.ssrlcv_hip_stereo_sgm_census_u8, LIB.ssrlcv_hip_stereo_sgm_census_workspace_bytes)), p, left_d, right_d, want_cost,
+                        workspace, census)
 
 
 def stereo_sgm_set_pass_events(events):

@@ -24,6 +24,10 @@
 //                    eight-disparity groups of a pixel sit in neighbouring lanes and meet through a shuffle butterfly.  The
 //                    lane that owns the winner has the costs of k - 1 and k + 1 (its own registers, or edge_costs: one shuffle
 //                    from the next group) and winner_disparity adds the sub-pixel offset of the parabola through the three.
+//   k_census         the census cost (include/ssrlcv_hip.h "census cost"; tests/census_ref.py restates it): the code of every pixel
+//                    of one view, a uint64 per pixel
+//   k_stereo_census  the census sibling of k_stereo_sad: the same ownership, march and three forms over the Hamming distances of
+//                    the codes summed over the aggregation window; cost_row_out is the end of a row of either cost pass
 //   k_stereo_lr      the left-right check over the two k maps
 //   k_sgm_path       semi-global matching (include/ssrlcv_hip.h "semi-global matching"; tests/sgm_ref.py restates it): one
 //                    direction's pass.  A group of nD lanes -- 8 disparities a lane, the SAD kernel's ownership -- owns ONE
@@ -57,6 +61,7 @@ constexpr int kXs = 4;                      // columns per lane
 constexpr int kDc = 8;                      // disparities per lane
 constexpr int kMaxG = 8;                    // dwords of the widest window row (31 bytes)
 constexpr int kPre = 10;                    // staged bytes per thread and row, at most
+constexpr int kPreCodes = 10;               // staged census codes per thread and row, at most (census_tile)
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr uint32_t kNaN = 0x7FC00000u;
 constexpr uint32_t kMatchPerThread = 16;
@@ -71,6 +76,7 @@ struct StereoArgs {
   int threads;
   uint32_t maxCost;
   int subpixel;
+  int ra;                  // census cost pass only: the aggregation radius; r is then the footprint's rho = ra + censusRadius
 };
 
 // a lane's eight uint16 of a pixel's entry of either volume, as one 16-byte word
@@ -162,6 +168,63 @@ __device__ __forceinline__ void row_sums(const uint8_t* __restrict__ rowB, const
   }
 }
 
+// What a cost pass does with row y of its running sums V, for the lane's four columns x0 .. x0 + 3 and its eight disparities
+// (valid[xi]: which of them are candidates).  The winner form takes the winner of every pixel and the lane that owns it writes
+// k, and for the left view the disparity and the cost under the limit; VOLUME stores the eight costs, clamped, a non-candidate
+// as the clamp itself.  The SAD and the census cost pass both end their row here.
+template <bool RIGHT, bool VOLUME>
+__device__ __forceinline__ void cost_row_out(const StereoArgs& a, const uint32_t (&V)[kXs][kDc], const uint32_t (&valid)[kXs], int dl, int x0, int y,
+                                             float* __restrict__ disparity, uint32_t* __restrict__ cost, uint8_t* __restrict__ kwin,
+                                             uint16_t* __restrict__ volume, uint32_t clamp) {
+  if constexpr (VOLUME) {
+    const int Dtile = a.nD * kDc;
+#pragma unroll
+    for (int xi = 0; xi < kXs; ++xi) {
+      const int x = x0 + xi;
+      if (x <= a.w - 1 - a.r) {
+        uint32_t c[kDc];
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) c[dk] = (valid[xi] >> dk) & 1u ? min(V[xi][dk], clamp) : clamp;
+        *reinterpret_cast<uint4*>(volume + ((size_t)y * a.w + x) * Dtile + dl * kDc) = pack8(c);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int xi = 0; xi < kXs; ++xi) {
+      const uint32_t best = winner_key(V[xi], CandidateBits{valid[xi]}, dl, a.nD);
+      const EdgeCosts edge = edge_costs(V[xi]);
+      const int k = (int)(best & 0xFFu);
+      if (best != kNoKey && (k >> 3) == dl) {  // the lane that owns the winner writes the pixel
+        const int x = x0 + xi;
+        const size_t p = (size_t)y * a.w + x;
+        kwin[p] = (uint8_t)k;
+        const uint32_t c = best >> 8;
+        if (!RIGHT && c <= a.maxCost) {
+          disparity[p] = winner_disparity(a, V[xi], edge, k, c, x);
+          if (cost) cost[p] = c;
+        }
+      }
+    }
+  }
+}
+
+// which of a lane's (column, disparity) pairs are candidates, columns x0 .. x0 + 3: the same for every row
+template <bool RIGHT>
+__device__ __forceinline__ void candidate_bits(const StereoArgs& a, int dl, int x0, uint32_t (&valid)[kXs]) {
+#pragma unroll
+  for (int xi = 0; xi < kXs; ++xi) {
+    const int x = x0 + xi;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int dk = 0; dk < kDc; ++dk) {
+      const int k = dl * kDc + dk, d = a.dmin + k;
+      const int partner = RIGHT ? x + d : x - d;
+      if (x <= a.w - 1 - a.r && k < a.D && partner >= a.r && partner <= a.w - 1 - a.r) bits |= 1u << dk;
+    }
+    valid[xi] = bits;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_stereo_fill(float* __restrict__ disparity, uint32_t* __restrict__ cost, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     disparity[i] = __uint_as_float(kNaN);
@@ -194,20 +257,8 @@ __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ 
   const int offO = kXs * xl + kDc * (RIGHT ? dl : a.nD - 1 - dl);
   const int nb = a.pitchB + a.pitchO;
 
-  // which of this lane's (column, disparity) pairs are candidates: the same for every row
   uint32_t valid[kXs];
-#pragma unroll
-  for (int xi = 0; xi < kXs; ++xi) {
-    const int x = X0 + offB + xi;
-    uint32_t bits = 0;
-#pragma unroll
-    for (int dk = 0; dk < kDc; ++dk) {
-      const int k = dl * kDc + dk, d = a.dmin + k;
-      const int partner = RIGHT ? x + d : x - d;
-      if (x <= a.w - 1 - a.r && k < a.D && partner >= a.r && partner <= a.w - 1 - a.r) bits |= 1u << dk;
-    }
-    valid[xi] = bits;
-  }
+  candidate_bits<RIGHT>(a, dl, X0 + offB, valid);
 
   uint32_t V[kXs][kDc];
 #pragma unroll
@@ -278,35 +329,157 @@ __global__ __launch_bounds__(256) void k_stereo_sad(const uint8_t* __restrict__ 
     const int y = t - a.r;
     if (y < Y0) continue;  // block-uniform: the window is not full yet
 
-    if constexpr (VOLUME) {
+    cost_row_out<RIGHT, VOLUME>(a, V, valid, dl, X0 + offB, y, disparity, cost, kwin, volume, clamp);
+  }
+}
+
+// ---- census cost (include/ssrlcv_hip.h "census cost"; tests/census_ref.py restates it)
+// The code of every pixel whose (2 C + 1)^2 window lies inside the image, 0 elsewhere: bit b = [I(x + i, y + j) < I(x, y)], the
+// offsets numbered row by row with the centre skipped.  Every entry of `codes` is written.
+template <int C>
+__global__ __launch_bounds__(256) void k_census(const uint8_t* __restrict__ image, int w, int h, uint64_t* __restrict__ codes) {
+  const size_t n = (size_t)w * h;
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256) {
+    const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
+    uint64_t code = 0;
+    if (x >= C && x <= w - 1 - C && y >= C && y <= h - 1 - C) {
+      const uint32_t centre = image[p];
+      int b = 0;
 #pragma unroll
-      for (int xi = 0; xi < kXs; ++xi) {
-        const int x = X0 + offB + xi;
-        if (x <= a.w - 1 - a.r) {
-          uint32_t c[kDc];
+      for (int j = -C; j <= C; ++j)
 #pragma unroll
-          for (int dk = 0; dk < kDc; ++dk) c[dk] = (valid[xi] >> dk) & 1u ? min(V[xi][dk], clamp) : clamp;
-          *reinterpret_cast<uint4*>(volume + ((size_t)y * a.w + x) * Dtile + dl * kDc) = pack8(c);
+        for (int i = -C; i <= C; ++i) {
+          if (i == 0 && j == 0) continue;
+          const uint32_t v = image[(size_t)(y + j) * w + (x + i)];
+          code |= (uint64_t)(v < centre ? 1u : 0u) << b;
+          ++b;
         }
+    }
+    codes[p] = code;
+  }
+}
+
+// acc + popcount(a xor b): v_bcnt_u32_b32 takes the addend, so a distance costs one xor and one count per 32 bits
+__device__ __forceinline__ uint32_t hamming_add(uint8_t a, uint8_t b, uint32_t acc) { return (uint32_t)__popc((uint32_t)(a ^ b)) + acc; }
+__device__ __forceinline__ uint32_t hamming_add(uint32_t a, uint32_t b, uint32_t acc) { return (uint32_t)__popc(a ^ b) + acc; }
+__device__ __forceinline__ uint32_t hamming_add(uint64_t a, uint64_t b, uint32_t acc) {
+  const uint64_t v = a ^ b;
+  return (uint32_t)__popc((uint32_t)(v >> 32)) + ((uint32_t)__popc((uint32_t)v) + acc);
+}
+
+// horizontal sums of one staged row of codes: acc[xi][dk] += sum over the 2 ra + 1 columns of popcount(B xor O)
+template <class CW, bool RIGHT>
+__device__ __forceinline__ void census_row_sums(const CW* __restrict__ rowB, const CW* __restrict__ rowO, int ra, uint32_t (&acc)[kXs][kDc]) {
+  for (int j = 0; j <= 2 * ra; ++j) {  // wave-uniform
+    CW B[kXs], O[kXs + kDc - 1];
+#pragma unroll
+    for (int xi = 0; xi < kXs; ++xi) B[xi] = rowB[j + xi];
+#pragma unroll
+    for (int o = 0; o < kXs + kDc - 1; ++o) O[o] = rowO[j + o];
+#pragma unroll
+    for (int xi = 0; xi < kXs; ++xi)
+#pragma unroll
+      for (int dk = 0; dk < kDc; ++dk) acc[xi][dk] = hamming_add(B[xi], O[xi + (RIGHT ? dk : kDc - 1 - dk)], acc[xi][dk]);
+  }
+}
+
+// The census sibling of k_stereo_sad: the same ownership (a lane owns four columns and eight disparities, nD lanes share a
+// pixel, a block marches down a strip with V += h(entering row) - h(leaving row)) and the same three output forms
+// (cost_row_out), over C(x, y, d) = sum over the (2 ra + 1)^2 aggregation window of popcount(T_base xor T_other).  `base` and
+// `other` are the code maps k_census wrote; a.r is the footprint radius rho = ra + censusRadius, so the strip, the candidate
+// test and everything behind the pass see the interior [rho, w - 1 - rho] x [rho, h - 1 - rho]; the rows and columns the
+// pass reads reach ra further, where the codes are still defined.  The rows are staged in LDS as CW, the narrowest type that
+// holds the code (uint8 for 3 x 3, uint32 for 5 x 5, uint64 for 7 x 7), in a ring of 2 ra + 3 rows from which the leaving row's
+// h is recomputed.  ra = 0 has no leaving row: V is the row's h itself and the ring is the two slots the barrier needs.
+// LDS: ring * (pitchB + pitchO) * sizeof(CW) with pitchB = TX + 2 ra, pitchO = TX + 2 ra + 8 nD; census_tile halves the strip's
+// width TX from k_stereo_sad's until that is at most 64 KB (only 7 x 7 codes need it: at ra = 7 with nD <= 4 and at ra = 6 with
+// nD = 2 or 4, TX = 128; the largest ring is 65280 bytes, ra = 6 at nD = 1).
+template <class CW, bool RIGHT, bool VOLUME>
+__global__ __launch_bounds__(256) void k_stereo_census(const uint64_t* __restrict__ base, const uint64_t* __restrict__ other, StereoArgs a,
+                                                       float* __restrict__ disparity, uint32_t* __restrict__ cost, uint8_t* __restrict__ kwin,
+                                                       uint16_t* __restrict__ volume, uint32_t clamp) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  CW* sB = reinterpret_cast<CW*>(smem);  // [ring][pitchB]
+  CW* sO = sB + a.ring * a.pitchB;       // [ring][pitchO]
+  const int tid = threadIdx.x;
+  const int dl = tid & (a.nD - 1), xl = tid >> a.nDlog;
+  const int tx = blockIdx.x % a.tilesX, ty = blockIdx.x / a.tilesX;
+  const int X0 = a.r + tx * a.TX;
+  const int Y0 = a.r + ty * a.TY;
+  const int Y1 = min(Y0 + a.TY, a.h - a.r);
+  const int Dtile = a.nD * kDc;
+  // global column of staged entry 0 of either map
+  const int cb0 = X0 - a.ra;
+  const int co0 = RIGHT ? X0 - a.ra + a.dmin : X0 - a.ra - (a.dmin + Dtile - 1);
+  const int offB = kXs * xl;
+  const int offO = kXs * xl + kDc * (RIGHT ? dl : a.nD - 1 - dl);
+  const int nb = a.pitchB + a.pitchO;
+
+  uint32_t valid[kXs];
+  candidate_bits<RIGHT>(a, dl, X0 + offB, valid);
+
+  uint32_t V[kXs][kDc];
+#pragma unroll
+  for (int xi = 0; xi < kXs; ++xi)
+#pragma unroll
+    for (int dk = 0; dk < kDc; ++dk) V[xi][dk] = 0;
+
+  CW pre[kPreCodes];
+  auto fetch = [&](int row) {
+    const size_t rowAt = (size_t)row * a.w;
+#pragma unroll
+    for (int q = 0; q < kPreCodes; ++q) {
+      const int i = tid + q * a.threads;
+      CW v = 0;
+      if (i < nb) {
+        const bool inB = i < a.pitchB;
+        const int col = inB ? cb0 + i : co0 + (i - a.pitchB);
+        if (col >= 0 && col < a.w) v = (CW)(inB ? base : other)[rowAt + col];
       }
-    } else {
+      pre[q] = v;
+    }
+  };
+
+  const int T0 = Y0 - a.ra, T1 = Y1 - 1 + a.ra;  // rows of codes this block reads: all inside the image
+  fetch(T0);
+  for (int t = T0; t <= T1; ++t) {
+    const int slot = t % a.ring;
 #pragma unroll
-      for (int xi = 0; xi < kXs; ++xi) {
-        const uint32_t best = winner_key(V[xi], CandidateBits{valid[xi]}, dl, a.nD);
-        const EdgeCosts edge = edge_costs(V[xi]);
-        const int k = (int)(best & 0xFFu);
-        if (best != kNoKey && (k >> 3) == dl) {  // the lane that owns the winner writes the pixel
-          const int x = X0 + offB + xi;
-          const size_t p = (size_t)y * a.w + x;
-          kwin[p] = (uint8_t)k;
-          const uint32_t c = best >> 8;
-          if (!RIGHT && c <= a.maxCost) {
-            disparity[p] = winner_disparity(a, V[xi], edge, k, c, x);
-            if (cost) cost[p] = c;
-          }
-        }
+    for (int q = 0; q < kPreCodes; ++q) {
+      const int i = tid + q * a.threads;
+      if (i < nb) {
+        if (i < a.pitchB) sB[slot * a.pitchB + i] = pre[q];
+        else sO[slot * a.pitchO + (i - a.pitchB)] = pre[q];
       }
     }
+    __syncthreads();  // row t is staged; the slot it took was last read two iterations ago
+    if (t < T1) fetch(t + 1);
+
+    if (a.ra == 0) {  // block-uniform: the cost is the row's own h
+#pragma unroll
+      for (int xi = 0; xi < kXs; ++xi)
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) V[xi][dk] = 0;
+    }
+    census_row_sums<CW, RIGHT>(sB + slot * a.pitchB + offB, sO + slot * a.pitchO + offO, a.ra, V);
+    const int leaving = t - 2 * a.ra - 1;
+    if (a.ra != 0 && leaving >= T0) {  // block-uniform
+      const int gone = leaving % a.ring;
+      uint32_t acc[kXs][kDc];
+#pragma unroll
+      for (int xi = 0; xi < kXs; ++xi)
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) acc[xi][dk] = 0;
+      census_row_sums<CW, RIGHT>(sB + gone * a.pitchB + offB, sO + gone * a.pitchO + offO, a.ra, acc);
+#pragma unroll
+      for (int xi = 0; xi < kXs; ++xi)
+#pragma unroll
+        for (int dk = 0; dk < kDc; ++dk) V[xi][dk] -= acc[xi][dk];
+    }
+    const int y = t - a.ra;
+    if (y < Y0) continue;  // block-uniform: the window is not full yet
+
+    cost_row_out<RIGHT, VOLUME>(a, V, valid, dl, X0 + offB, y, disparity, cost, kwin, volume, clamp);
   }
 }
 
@@ -559,42 +732,58 @@ __global__ __launch_bounds__(256) void k_stereo_points(const ssrlcv_match* __res
 }
 
 // ---- host side
-// The parameter check of both calls, in the contract's order: every invalid argument (the image size last), then what is
-// valid and unsupported.  `alsoInvalid` / `alsoUnsupported`: what semi-global matching adds to either tier.
-int params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p, bool alsoInvalid = false, bool alsoUnsupported = false) {
-  if (p.radius == 0 || p.numDisparities == 0 || p.minDisparity < -32768 || p.minDisparity > 32767 || p.subpixel > 1 || alsoInvalid)
+// The parameter check of every call, in the contract's order: every invalid argument (the image size last), then what is
+// valid and unsupported.  `alsoInvalid` / `alsoUnsupported`: what semi-global matching adds to either tier.  `census`: null for
+// the SAD calls; else the census radius, which takes radius 0's place in the invalid tier (an aggregation radius of 0 is
+// legal) and narrows the supported radii to the footprint the census cost pass is built for.
+int params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p, bool alsoInvalid = false, bool alsoUnsupported = false,
+                  const uint32_t* census = nullptr) {
+  const bool noWindow = census ? *census == 0 : p.radius == 0;
+  if (noWindow || p.numDisparities == 0 || p.minDisparity < -32768 || p.minDisparity > 32767 || p.subpixel > 1 || alsoInvalid)
     return SSRLCV_ERR_INVALID_ARG;
   if ((unsigned long long)w * h >= (1ull << 31)) return SSRLCV_ERR_INVALID_ARG;
-  if (p.radius > 15 || p.numDisparities > 256 || alsoUnsupported) return SSRLCV_ERR_UNSUPPORTED;
+  const bool wideWindow = census ? *census > 3 || p.radius > 7 : p.radius > 15;
+  if (wideWindow || p.numDisparities > 256 || alsoUnsupported) return SSRLCV_ERR_UNSUPPORTED;
   return SSRLCV_OK;
 }
 
-int stereo_params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p) { return p ? params_status(w, h, *p) : SSRLCV_ERR_INVALID_ARG; }
+int stereo_params_status(uint32_t w, uint32_t h, const ssrlcv_stereo_params* p, const uint32_t* census = nullptr) {
+  return p ? params_status(w, h, *p, false, false, census) : SSRLCV_ERR_INVALID_ARG;
+}
 
 // dense stereo's share of the parameters: the cost limit is off, the winner pass of semi-global matching has none
 ssrlcv_stereo_params sgm_as_stereo(const ssrlcv_sgm_params& p) {
   return {p.radius, p.minDisparity, p.numDisparities, 0xFFFFFFFFu, p.lrTolerance, p.subpixel};
 }
 
-int sgm_params_status(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p) {
+int sgm_params_status(uint32_t w, uint32_t h, const ssrlcv_sgm_params* p, const uint32_t* census = nullptr) {
   if (!p) return SSRLCV_ERR_INVALID_ARG;
   // M, L and S live in 16 bits: S <= popcount(paths) (costClamp + P2)
   const bool wide = (unsigned long long)__builtin_popcount(p->paths) * ((unsigned long long)p->costClamp + p->P2) > 65535ull;
-  return params_status(w, h, sgm_as_stereo(*p), p->P1 > p->P2 || p->paths == 0 || p->paths > 0xFFu, wide);
+  return params_status(w, h, sgm_as_stereo(*p), p->P1 > p->P2 || p->paths == 0 || p->paths > 0xFFu, wide, census);
+}
+
+// what everything behind a census cost pass sees: the parameters with the footprint radius rho = radius + censusRadius
+ssrlcv_stereo_params census_footprint(ssrlcv_stereo_params p, uint32_t censusRadius) {
+  p.radius += censusRadius;
+  return p;
 }
 
 // samples 0, step, 2 step, ... below n: ceil(n / step) without the sum n + step - 1, which wraps for a step near 2^32
 uint32_t stereo_grid(uint32_t n, uint32_t step) { return n ? (n - 1) / step + 1 : 0; }
 
-// The workspace of either call, as byte offsets: the winners' k of both views, one byte per pixel each, and for semi-global
-// matching (numDisparities != 0) the volumes M and S, uint16 [h][w][8 nD] each, 8 nD = numDisparities rounded up to 8, 16, .. 256.
-struct StereoLayout { size_t kL, kR, M, S, total; };
-StereoLayout stereo_layout(uint32_t w, uint32_t h, uint32_t numDisparities) {
+// The workspace of every call, as byte offsets: the winners' k of both views, one byte per pixel each; for semi-global
+// matching (numDisparities != 0) the volumes M and S, uint16 [h][w][8 nD] each, 8 nD = numDisparities rounded up to 8, 16, .. 256;
+// and for the census calls the code maps of both views behind them, uint64 [h][w] each.
+struct StereoLayout { size_t kL, kR, M, S, TL, TR, total; };
+StereoLayout stereo_layout(uint32_t w, uint32_t h, uint32_t numDisparities, bool census = false) {
   const size_t map = align256((size_t)w * h);
   size_t k8 = 8;
   while (k8 < numDisparities) k8 <<= 1;
   const size_t volume = numDisparities ? align256((size_t)w * h * k8 * 2) : 0;
-  return {0, map, 2 * map, 2 * map + volume, 2 * map + 2 * volume + 256};
+  const size_t codes = census ? align256((size_t)w * h * 8) : 0;
+  const size_t sad = 2 * map + 2 * volume + 256;
+  return {0, map, 2 * map, 2 * map + volume, sad, sad + codes, sad + 2 * codes};
 }
 
 StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p) {
@@ -627,6 +816,27 @@ StereoArgs stereo_args(uint32_t w, uint32_t h, const ssrlcv_stereo_params& p) {
   a.TY = (hi + segs - 1) / segs;
   a.maxCost = p.maxCost;
   a.subpixel = (int)p.subpixel;
+  a.ra = 0;
+  return a;
+}
+
+// The strip of the census cost pass, from stereo_args of the footprint radius: codes of `codeBytes` bytes staged in a ring of
+// 2 ra + 3 rows (two slots for ra = 0), the strip as wide as k_stereo_sad's unless the ring would pass 64 KB of LDS, then half
+// as wide (7 x 7 codes only, at ra = 7 with nD <= 4 and at ra = 6 with nD = 2 or 4: 128 columns, and 32 threads a block at
+// nD = 1).  TY stays stereo_args' on purpose: a halved strip only means more blocks of the same march.  A thread stages at most
+// kPreCodes codes a row: (8 NX + 4 ra + 8 nD) / (NX nD) <= 9.2 at nD = 1, NX = 32, ra = 7.
+StereoArgs census_tile(StereoArgs a, int ra, int codeBytes) {
+  a.ra = ra;
+  a.ring = ra ? 2 * ra + 3 : 2;
+  int NX = a.nD >= 4 ? 256 / a.nD : 64;
+  for (;; NX >>= 1) {
+    a.TX = kXs * NX;
+    a.pitchB = a.TX + 2 * ra;
+    a.pitchO = a.TX + 2 * ra + a.nD * kDc;
+    if ((size_t)a.ring * (a.pitchB + a.pitchO) * codeBytes <= 65536) break;
+  }
+  a.threads = NX * a.nD;
+  a.tilesX = (a.w - 2 * a.r + a.TX - 1) / a.TX;
   return a;
 }
 
@@ -651,6 +861,38 @@ void launch_sad(const StereoArgs& a, hipStream_t st, const uint8_t* base, const 
                      kwin, volume, clamp);
 }
 
+template <int C>
+void launch_census_codes(hipStream_t st, const uint8_t* image, uint32_t w, uint32_t h, uint64_t* codes) {
+  const size_t n = (size_t)w * h;
+  unsigned blocks = (unsigned)((n + 255) / 256);
+  if (blocks > 8192u) blocks = 8192u;
+  hipLaunchKernelGGL(k_census<C>, dim3(blocks), dim3(256), 0, st, image, (int)w, (int)h, codes);
+}
+void launch_census_codes(uint32_t censusRadius, hipStream_t st, const uint8_t* image, uint32_t w, uint32_t h, uint64_t* codes) {
+  if (censusRadius == 1) launch_census_codes<1>(st, image, w, h, codes);
+  else if (censusRadius == 2) launch_census_codes<2>(st, image, w, h, codes);
+  else launch_census_codes<3>(st, image, w, h, codes);
+}
+
+template <class CW, bool RIGHT, bool VOLUME>
+void launch_census_cost(const StereoArgs& sa, int ra, hipStream_t st, const uint64_t* base, const uint64_t* other, float* disparity, uint32_t* cost,
+                        uint8_t* kwin, uint16_t* volume, uint32_t clamp) {
+  const StereoArgs a = census_tile(sa, ra, (int)sizeof(CW));
+  const int tilesY = (a.h - 2 * a.r + a.TY - 1) / a.TY;
+  const size_t lds = (size_t)a.ring * (a.pitchB + a.pitchO) * sizeof(CW);
+  hipLaunchKernelGGL((k_stereo_census<CW, RIGHT, VOLUME>), dim3((unsigned)(a.tilesX * tilesY)), dim3(a.threads), lds, st, base, other, a, disparity,
+                     cost, kwin, volume, clamp);
+}
+// `a`: stereo_args of the footprint radius; the aggregation radius is what the census window leaves of it
+template <bool RIGHT, bool VOLUME = false>
+void launch_census_cost(const StereoArgs& a, uint32_t censusRadius, hipStream_t st, const uint64_t* base, const uint64_t* other, float* disparity,
+                        uint32_t* cost, uint8_t* kwin, uint16_t* volume = nullptr, uint32_t clamp = 0) {
+  const int ra = a.r - (int)censusRadius;
+  if (censusRadius == 1) launch_census_cost<uint8_t, RIGHT, VOLUME>(a, ra, st, base, other, disparity, cost, kwin, volume, clamp);
+  else if (censusRadius == 2) launch_census_cost<uint32_t, RIGHT, VOLUME>(a, ra, st, base, other, disparity, cost, kwin, volume, clamp);
+  else launch_census_cost<uint64_t, RIGHT, VOLUME>(a, ra, st, base, other, disparity, cost, kwin, volume, clamp);
+}
+
 // the directions in the order of the `paths` bits, [first selected direction: it stores S][dir]
 using SgmPathKernel = void (*)(SgmArgs);
 const SgmPathKernel kSgmPath[2][8] = {
@@ -664,8 +906,31 @@ constexpr uint32_t kSgmMaxEvents = 12;
 void* g_sgm_events[kSgmMaxEvents];
 uint32_t g_sgm_event_count = 0;
 
-// What both calls do around their passes, once the parameters have passed their check (first: its codes do not depend on the
-// buffers).  `sp`: dense stereo's share of the parameters.  `passes(a, kL, kR)` launches what leaves disparity, cost, kL and, when
+// semi-global matching behind its cost pass: the selected directions' passes over M into S, then the winner pass; `mark()`
+// behind each
+template <class Mark>
+void sgm_passes(const StereoArgs& a, const ssrlcv_sgm_params& p, const uint16_t* M, uint16_t* S, float* disparity, uint32_t* cost, uint8_t* kL,
+                uint8_t* kR, hipStream_t st, Mark& mark) {
+  SgmArgs g = sgm_args(a, p, M, S);
+  bool first = true;
+  for (int dir = 0; dir < 8; ++dir) {
+    if (!((p.paths >> dir) & 1u)) continue;
+    g.nPaths = dir < 2 ? g.hi : dir < 4 ? g.wi : g.wi + g.hi - 1;
+    const unsigned blocks = (unsigned)(((size_t)g.nPaths * g.nD + 63) / 64);
+    hipLaunchKernelGGL(kSgmPath[first][dir], dim3(blocks), dim3(64), 0, st, g);
+    first = false;
+    mark();
+  }
+  int T = 16384 / g.K8;  // pixels of a row per block of the winner pass: a tile of 32 KB, 64 .. 1024 pixels
+  if (T > 1024) T = 1024;
+  const int strips = (g.wi + T - 1) / T;
+  hipLaunchKernelGGL(k_sgm_winners, dim3((unsigned)strips * (unsigned)g.hi), dim3(256), (size_t)T * g.K8 * 2, st, g, T, strips, disparity,
+                     cost, kL, kR);
+  mark();
+}
+
+// What every call does around its passes, once the parameters have passed their check (first: its codes do not depend on the
+// buffers).  `sp`: dense stereo's share of the parameters, its radius the footprint's.  `passes(a, kL, kR)` launches what leaves disparity, cost, kL and, when
 // the check is asked for, kR; `mark()` is called before the first launch and behind the last one.
 template <class Passes, class Mark>
 int stereo_call(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params& sp, const StereoLayout& lay,
@@ -692,6 +957,57 @@ int stereo_call(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t 
   return SSRLCV_OK;
 }
 
+// Block matching, SAD (censusRadius == 0) or census: the parameters have passed their check
+int block_matching_call(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params& p, uint32_t censusRadius,
+                        void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, hipStream_t st) {
+  const StereoLayout lay = stereo_layout(w, h, 0, censusRadius != 0);
+  return stereo_call(
+      left, right, w, h, census_footprint(p, censusRadius), lay, workspace, workspaceBytes, disparity, cost, st,
+      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
+        if (censusRadius == 0) {
+          launch_sad<false>(a, st, left, right, disparity, cost, kL);
+          if (p.lrTolerance >= 0) launch_sad<true>(a, st, right, left, nullptr, nullptr, kR);
+          return;
+        }
+        uint64_t* TL = (uint64_t*)((uint8_t*)workspace + lay.TL);
+        uint64_t* TR = (uint64_t*)((uint8_t*)workspace + lay.TR);
+        launch_census_codes(censusRadius, st, left, w, h, TL);
+        launch_census_codes(censusRadius, st, right, w, h, TR);
+        launch_census_cost<false>(a, censusRadius, st, TL, TR, disparity, cost, kL);
+        if (p.lrTolerance >= 0) launch_census_cost<true>(a, censusRadius, st, TR, TL, nullptr, nullptr, kR);
+      },
+      [] {});
+}
+
+// Semi-global matching over the SAD (censusRadius == 0) or the census costs: the parameters have passed their check
+int sgm_call(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params& p, uint32_t censusRadius, void* workspace,
+             size_t workspaceBytes, float* disparity, uint32_t* cost, hipStream_t st) {
+  const StereoLayout lay = stereo_layout(w, h, p.numDisparities, censusRadius != 0);
+  uint32_t marks = 0;
+  auto mark = [&]() {  // the next pass event, if the caller of set_pass_events asked for one
+    if (marks < g_sgm_event_count && g_sgm_events[marks]) (void)hipEventRecord((hipEvent_t)g_sgm_events[marks], st);
+    ++marks;
+  };
+  return stereo_call(
+      left, right, w, h, census_footprint(sgm_as_stereo(p), censusRadius), lay, workspace, workspaceBytes, disparity, cost, st,
+      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
+        uint16_t* M = (uint16_t*)((uint8_t*)workspace + lay.M);
+        uint16_t* S = (uint16_t*)((uint8_t*)workspace + lay.S);
+        if (censusRadius == 0) {
+          launch_sad<false, true>(a, st, left, right, nullptr, nullptr, nullptr, M, p.costClamp);
+        } else {
+          uint64_t* TL = (uint64_t*)((uint8_t*)workspace + lay.TL);
+          uint64_t* TR = (uint64_t*)((uint8_t*)workspace + lay.TR);
+          launch_census_codes(censusRadius, st, left, w, h, TL);
+          launch_census_codes(censusRadius, st, right, w, h, TR);
+          launch_census_cost<false, true>(a, censusRadius, st, TL, TR, nullptr, nullptr, nullptr, M, p.costClamp);
+        }
+        mark();
+        sgm_passes(a, p, M, S, disparity, cost, kL, kR, st, mark);
+      },
+      mark);
+}
+
 }  // namespace
 
 extern "C" {
@@ -703,14 +1019,7 @@ size_t ssrlcv_hip_stereo_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_st
 int ssrlcv_hip_stereo_sad_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params* params,
                              void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream) {
   if (const int rc = stereo_params_status(w, h, params)) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return stereo_call(
-      left, right, w, h, *params, stereo_layout(w, h, 0), workspace, workspaceBytes, disparity, cost, st,
-      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
-        launch_sad<false>(a, st, left, right, disparity, cost, kL);
-        if (params->lrTolerance >= 0) launch_sad<true>(a, st, right, left, nullptr, nullptr, kR);
-      },
-      [] {});
+  return block_matching_call(left, right, w, h, *params, 0, workspace, workspaceBytes, disparity, cost, (hipStream_t)stream);
 }
 
 size_t ssrlcv_hip_stereo_sgm_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params) {
@@ -727,38 +1036,39 @@ int ssrlcv_hip_stereo_sgm_set_pass_events(void* const* events, uint32_t count) {
 int ssrlcv_hip_stereo_sgm_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
                              void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost, ssrlcv_stream_t stream) {
   if (const int rc = sgm_params_status(w, h, params)) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  const StereoLayout lay = stereo_layout(w, h, params->numDisparities);
-  uint32_t marks = 0;
-  auto mark = [&]() {  // the next pass event, if the caller of set_pass_events asked for one
-    if (marks < g_sgm_event_count && g_sgm_events[marks]) (void)hipEventRecord((hipEvent_t)g_sgm_events[marks], st);
-    ++marks;
-  };
-  return stereo_call(
-      left, right, w, h, sgm_as_stereo(*params), lay, workspace, workspaceBytes, disparity, cost, st,
-      [&](const StereoArgs& a, uint8_t* kL, uint8_t* kR) {
-        uint16_t* M = (uint16_t*)((uint8_t*)workspace + lay.M);
-        uint16_t* S = (uint16_t*)((uint8_t*)workspace + lay.S);
-        launch_sad<false, true>(a, st, left, right, nullptr, nullptr, nullptr, M, params->costClamp);
-        mark();
-        SgmArgs g = sgm_args(a, *params, M, S);
-        bool first = true;
-        for (int dir = 0; dir < 8; ++dir) {
-          if (!((params->paths >> dir) & 1u)) continue;
-          g.nPaths = dir < 2 ? g.hi : dir < 4 ? g.wi : g.wi + g.hi - 1;
-          const unsigned blocks = (unsigned)(((size_t)g.nPaths * g.nD + 63) / 64);
-          hipLaunchKernelGGL(kSgmPath[first][dir], dim3(blocks), dim3(64), 0, st, g);
-          first = false;
-          mark();
-        }
-        int T = 16384 / g.K8;  // pixels of a row per block of the winner pass: a tile of 32 KB, 64 .. 1024 pixels
-        if (T > 1024) T = 1024;
-        const int strips = (g.wi + T - 1) / T;
-        hipLaunchKernelGGL(k_sgm_winners, dim3((unsigned)strips * (unsigned)g.hi), dim3(256), (size_t)T * g.K8 * 2, st, g, T, strips, disparity,
-                           cost, kL, kR);
-        mark();
-      },
-      mark);
+  return sgm_call(left, right, w, h, *params, 0, workspace, workspaceBytes, disparity, cost, (hipStream_t)stream);
+}
+
+int ssrlcv_hip_census_u8(const uint8_t* image, uint32_t w, uint32_t h, uint32_t censusRadius, uint64_t* codes, ssrlcv_stream_t stream) {
+  if (censusRadius == 0 || (unsigned long long)w * h >= (1ull << 31)) return SSRLCV_ERR_INVALID_ARG;
+  if (censusRadius > 3) return SSRLCV_ERR_UNSUPPORTED;
+  if (!image || !codes) return SSRLCV_ERR_INVALID_ARG;
+  if ((size_t)w * h == 0) return SSRLCV_OK;
+  launch_census_codes(censusRadius, (hipStream_t)stream, image, w, h, codes);
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+size_t ssrlcv_hip_stereo_census_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_stereo_params* params, uint32_t censusRadius) {
+  return stereo_params_status(w, h, params, &censusRadius) ? 0 : stereo_layout(w, h, 0, true).total;
+}
+
+int ssrlcv_hip_stereo_census_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_stereo_params* params,
+                                uint32_t censusRadius, void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost,
+                                ssrlcv_stream_t stream) {
+  if (const int rc = stereo_params_status(w, h, params, &censusRadius)) return rc;
+  return block_matching_call(left, right, w, h, *params, censusRadius, workspace, workspaceBytes, disparity, cost, (hipStream_t)stream);
+}
+
+size_t ssrlcv_hip_stereo_sgm_census_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_sgm_params* params, uint32_t censusRadius) {
+  return sgm_params_status(w, h, params, &censusRadius) ? 0 : stereo_layout(w, h, params->numDisparities, true).total;
+}
+
+int ssrlcv_hip_stereo_sgm_census_u8(const uint8_t* left, const uint8_t* right, uint32_t w, uint32_t h, const ssrlcv_sgm_params* params,
+                                    uint32_t censusRadius, void* workspace, size_t workspaceBytes, float* disparity, uint32_t* cost,
+                                    ssrlcv_stream_t stream) {
+  if (const int rc = sgm_params_status(w, h, params, &censusRadius)) return rc;
+  return sgm_call(left, right, w, h, *params, censusRadius, workspace, workspaceBytes, disparity, cost, (hipStream_t)stream);
 }
 
 size_t ssrlcv_hip_stereo_matches_workspace_bytes(uint32_t w, uint32_t h, uint32_t step) {

@@ -14,6 +14,11 @@
 //
 //   factory.setSemiGlobal(1000, 40, 400);           // costClamp, P1, P2, paths = 0xFF; clearSemiGlobal() returns to SAD winners
 //
+// The census cost (include/ssrlcv_hip.h "census cost") is another setter, for block matching and semi-global matching alike;
+// the radius is then the AGGREGATION radius (0 .. 7, 0 being the usual form under semi-global matching):
+//
+//   factory.setCensus(2);                           // 5 x 5 census codes; clearCensus() returns to SAD costs
+//
 // An unrectified pair of pinhole Images goes through rectify() first (include/ssrlcv_hip.h "rectification"):
 //
 //   ptr::value<Image> leftR, rightR;
@@ -37,6 +42,7 @@ class DisparityFactory {
   unsigned int step = 1;
   bool semiGlobal = false;
   unsigned int sgmClamp = 0, sgmP1 = 0, sgmP2 = 0, sgmPaths = 0xFFu;
+  unsigned int census = 0;  // 0: SAD costs
 
   static void toGpu(ptr::value<Image> image, MemoryState& origin, bool& keepHost) {
     if (image->colorDepth != 1) {
@@ -81,6 +87,12 @@ class DisparityFactory {
     sgmPaths = paths;
   }
   void clearSemiGlobal() { semiGlobal = false; }
+  // the matching cost becomes the Hamming distance of (2 censusRadius + 1)^2 census codes (ssrlcv_hip_stereo_census_u8,
+  // ssrlcv_hip_stereo_sgm_census_u8), censusRadius 1, 2 or 3; the radius is then the aggregation radius, 0 .. 7
+  void setCensus(unsigned int censusRadius) { census = censusRadius; }
+  void clearCensus() { census = 0; }
+  // the radius of everything a pixel's cost reads: what maskRectified masks with
+  unsigned int footprintRadius() const { return params.radius + census; }
 
   // disparity of every left pixel (row-major, w x h), in state gpu; `cost` (optional out) receives the winners' costs
   ptr::value<Unity<float>> generateDisparities(ptr::value<Image> left, ptr::value<Image> right,
@@ -104,9 +116,13 @@ class DisparityFactory {
       logger.err << "ERROR: semi-global matching has no cost limit (setMaxCost(0xFFFFFFFF) or clearSemiGlobal())";
       std::exit(-1);
     }
-    const size_t wsBytes = semiGlobal ? ssrlcv_hip_stereo_sgm_workspace_bytes(w, h, &sgm) : ssrlcv_hip_stereo_workspace_bytes(w, h, &params);
+    const size_t wsBytes = census ? (semiGlobal ? ssrlcv_hip_stereo_sgm_census_workspace_bytes(w, h, &sgm, census)
+                                                : ssrlcv_hip_stereo_census_workspace_bytes(w, h, &params, census))
+                                  : (semiGlobal ? ssrlcv_hip_stereo_sgm_workspace_bytes(w, h, &sgm) : ssrlcv_hip_stereo_workspace_bytes(w, h, &params));
     if (wsBytes == 0) {
-      if (semiGlobal)
+      if (census)
+        logger.err << "ERROR: census parameters outside the contract (census radius 1..3, aggregation radius 0..7, and the SAD call's other limits)";
+      else if (semiGlobal)
         logger.err << "ERROR: semi-global parameters outside the contract (P1 <= P2, paths 1..0xFF, popcount(paths) (costClamp + P2) <= 65535)";
       else
         logger.err << "ERROR: dense stereo parameters outside the contract (radius 1..15, 1..256 disparities from -32768..32767)";
@@ -121,7 +137,13 @@ class DisparityFactory {
     ptr::value<Unity<float>> disparity(nullptr, n ? n : 1ul, gpu);
     ptr::value<Unity<unsigned int>> costs;
     if (cost) costs = ptr::value<Unity<unsigned int>>(nullptr, n ? n : 1ul, gpu);
-    if (semiGlobal)
+    if (census && semiGlobal)
+      HipSafeCall(ssrlcv_hip_stereo_sgm_census_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &sgm, census, workspace.get(), wsBytes,
+                                                  disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
+    else if (census)
+      HipSafeCall(ssrlcv_hip_stereo_census_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &params, census, workspace.get(), wsBytes,
+                                              disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
+    else if (semiGlobal)
       HipSafeCall(ssrlcv_hip_stereo_sgm_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &sgm, workspace.get(), wsBytes,
                                            disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
     else
@@ -200,14 +222,14 @@ class DisparityFactory {
     return rect;
   }
 
-  // in place on generateDisparities' maps of a pair rectify() made: the pixels whose windows left a source image become
-  // invalid (it only removes pixels); cost may be nullptr
+  // in place on generateDisparities' maps of a pair rectify() made: the pixels whose windows (with a census cost: whose
+  // footprints, radius + census radius) left a source image become invalid (it only removes pixels); cost may be nullptr
   void maskRectified(ptr::value<Unity<float>> disparity, ptr::value<Unity<unsigned int>> cost, const Rectification& rect) {
     MemoryState origin = disparity->getMemoryState(), originC = cost != nullptr ? cost->getMemoryState() : gpu;
     if (origin != gpu) disparity->setMemoryState(gpu);
     if (cost != nullptr && originC != gpu) cost->setMemoryState(gpu);
     HipSafeCall(ssrlcv_hip_stereo_mask_rectified(disparity->device.get(), cost != nullptr ? cost->device.get() : nullptr, rect.w, rect.h,
-                                                 params.radius, rect.Hl, rect.Hr, rect.w, rect.h, nullptr));
+                                                 footprintRadius(), rect.Hl, rect.Hr, rect.w, rect.h, nullptr));
     HipCheckError();
     if (origin != gpu) disparity->setMemoryState(origin);
     if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);

@@ -138,21 +138,26 @@ def extract_features_dense(pixel_tensors, stride=1, sigma=1.6, max_orientations=
 
 
 def stereo_disparity(left, right, radius=4, min_disparity=0, num_disparities=64, max_cost=capi.STEREO_NO_LIMIT, lr_tolerance=1,
-                     subpixel=True, want_cost=True):
+                     subpixel=True, want_cost=True, census=0):
     """Dense stereo on a rectified pair (u8 CUDA tensors (H, W)): SAD block matching over (2 radius + 1)^2 windows, the
     disparities min_disparity .. min_disparity + num_disparities - 1, with the cost limit, left-right check and sub-pixel
-    step of include/ssrlcv_hip.h "dense stereo".  -> (disparity float32 (H, W), cost or None): invalid pixels hold the bit
-    pattern capi.STEREO_INVALID_BITS (a NaN) and cost 0xFFFFFFFF."""
-    return capi.stereo_disparity(left, right, radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel, want_cost)
+    step of include/ssrlcv_hip.h "dense stereo".  census = 1, 2 or 3: the cost is the Hamming distance of (2 census + 1)^2
+    census codes instead ("census cost"), unchanged by any strictly increasing map of either image's grey levels; `radius` is then the
+    AGGREGATION radius, 0 .. 7, and the footprint is radius + census.  -> (disparity float32 (H, W), cost or None): invalid
+    pixels hold the bit pattern capi.STEREO_INVALID_BITS (a NaN) and cost 0xFFFFFFFF."""
+    return capi.stereo_disparity(left, right, radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel, want_cost, census=census)
 
 
 def stereo_sgm(left, right, radius=2, min_disparity=0, num_disparities=64, cost_clamp=1000, p1=40, p2=400, paths=0xFF, lr_tolerance=1,
-               subpixel=True, want_cost=False):
+               subpixel=True, want_cost=False, census=0):
     """Dense stereo by semi-global matching on a rectified pair (u8 CUDA tensors (H, W)): the SAD costs of stereo_disparity,
     clamped at cost_clamp, aggregated along the directions of the bit mask `paths` (0x0F: 4 paths, 0xFF: 8) with the penalties
     p1 <= p2, then the winner, left-right check and sub-pixel step on the summed costs (include/ssrlcv_hip.h "semi-global
-    matching"; popcount(paths) (cost_clamp + p2) <= 65535).  -> (disparity float32 (H, W), cost or None) like stereo_disparity."""
-    return capi.stereo_sgm(left, right, radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, subpixel, want_cost)
+    matching"; popcount(paths) (cost_clamp + p2) <= 65535).  census = 1, 2 or 3: the census costs of stereo_disparity instead,
+    `radius` then being the AGGREGATION radius, 0 .. 7 (0: each pixel's own Hamming distance, the usual form here).
+    -> (disparity float32 (H, W), cost or None) like stereo_disparity."""
+    return capi.stereo_sgm(left, right, radius, min_disparity, num_disparities, cost_clamp, p1, p2, paths, lr_tolerance, subpixel, want_cost,
+                           census=census)
 
 
 def _dense_disparity(left, right, sgm, disparity_args):
@@ -170,8 +175,8 @@ def _dense_disparity(left, right, sgm, disparity_args):
 def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, **disparity_args):
     """Rectified pair -> dense cloud: stereo_disparity, then capi.stereo_matches (the valid pixels of the `step` grid as Match
     records), then capi.stereo_points (upstream's stereo_disparity: Z = foc baseline / (d + doffset)).  cx, cy default to the
-    image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel
-    (the cost map is not computed: want_cost is not taken).  sgm = dict(cost_clamp=, p1=, p2=[, paths=]): the disparity comes
+    image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel,
+    census (radius is the aggregation radius when census is set; the cost map is not computed: want_cost is not taken).  sgm = dict(cost_clamp=, p1=, p2=[, paths=]): the disparity comes
     from stereo_sgm with the remaining disparity_args (max_cost is then a TypeError).  -> (points float32 (n, 3), Match bytes, n, disparity).
     The Match records are the sparse path's: with real cameras they also go through capi.matchset_from_matches and
     triangulate() unchanged (tests/test_gpu_stereo.py does)."""
@@ -198,13 +203,15 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, **disparit
     """Unrectified pair -> dense cloud in the world frame of triangulate()'s clouds: rectify_pair, stereo_disparity, the mask
     of the windows that left a source image (capi.stereo_mask_rectified), capi.stereo_matches, the records mapped back into
     source pixels (capi.matches_apply_homography), compacted, then capi.matchset_from_matches and the two-view triangulation
-    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args and sgm as for stereo_cloud.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
+    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args and sgm as for stereo_cloud; with
+    census set, radius is the aggregation radius and the mask takes the footprint radius + census.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
     matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
     if "want_cost" in disparity_args:
         raise TypeError("stereo_cloud_cameras computes no cost map: call stereo_disparity for one")
     left_r, right_r, rect = rectify_pair(left, right, cam_l, cam_r)
     disp = _dense_disparity(left_r, right_r, sgm, disparity_args)
-    capi.stereo_mask_rectified(disp, None, disparity_args.get("radius", 4 if sgm is None else 2), rect)
+    footprint = disparity_args.get("radius", 4 if sgm is None else 2) + disparity_args.get("census", 0)
+    capi.stereo_mask_rectified(disp, None, footprint, rect)
     matches, n = capi.stereo_matches(disp, step, 0, 1)
     capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
     if n:
