@@ -52,6 +52,7 @@ class SIFT_FeatureFactory : public FeatureFactory {
 
   unsigned int denseStride = 1;
   float denseSigma = 1.6f;
+  unsigned int maxKeyPointsPerOctave = 0;
 
   void build(Slot& slot, uint2 size, const ssrlcv_sift_params& params) {
     if (slot.plan) ssrlcv_sift_plan_destroy(slot.plan);
@@ -85,6 +86,11 @@ class SIFT_FeatureFactory : public FeatureFactory {
   // the dense branch's grid step (pixels, >= 1) and the scale of its key points
   void setDenseStride(unsigned int stride) { denseStride = stride; }
   void setDenseSigma(float sigma) { denseSigma = sigma; }
+
+  // Capacity of the key-point lists (per octave) a NEW (image size, parameters) slot starts from; 0 = the plan's default
+  // density bound.  For dense imagery: a list that outgrows its capacity costs a re-run with twice the capacity (below), and
+  // a caller who knows the density starts high enough.  Slots that exist keep the capacity they have grown to.
+  void setMaxKeyPointsPerOctave(unsigned int perOctave) { maxKeyPointsPerOctave = perOctave; }
 
   ptr::value<Unity<Feature<SIFT_Descriptor>>> generateFeatures(ptr::value<Image> image, bool dense,
                                                                unsigned int maxOrientations,
@@ -151,7 +157,10 @@ class SIFT_FeatureFactory : public FeatureFactory {
     const Key key(image->size.x, image->size.y, maxOrientations, orientationThreshold, this->orientationContribWidth,
                   this->descriptorContribWidth);
     std::shared_ptr<Slot>& slotRef = (*pool)[key];
-    if (!slotRef) slotRef = std::make_shared<Slot>();
+    if (!slotRef) {
+      slotRef = std::make_shared<Slot>();
+      slotRef->perOctave = maxKeyPointsPerOctave;
+    }
     Slot& slot = *slotRef;
     params.maxKeyPointsPerOctave = slot.perOctave;
     if (!slot.plan) build(slot, image->size, params);
