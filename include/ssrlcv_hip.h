@@ -50,7 +50,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      rectification: rectify_cameras_host, warp_homography_u8, stereo_mask_rectified, matches_apply_homography;
  *      semi-global matching: stereo_sgm_workspace_bytes, stereo_sgm_u8, stereo_sgm_set_pass_events;
  *      census cost: census_u8, stereo_census_workspace_bytes, stereo_census_u8, stereo_sgm_census_workspace_bytes,
- *      stereo_sgm_census_u8 */
+ *      stereo_sgm_census_u8;
+ *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -857,6 +858,63 @@ int ssrlcv_hip_stereo_mask_rectified(float* disparity, uint32_t* cost, uint32_t 
                                      const float* Hr_host, uint32_t srcW, uint32_t srcH, ssrlcv_stream_t stream);
 int ssrlcv_hip_matches_apply_homography(ssrlcv_match* matches, uint32_t n, const float* H0_host, const float* H1_host,
                                         ssrlcv_stream_t stream);
+
+/* ---- disparity post-filters: the last stage of the dense stereo chain looks at the winner map as an image.  The left-right
+ * check, maxCost and the rectification mask judge one pixel at a time; what survives them are small islands of wrong disparity
+ * along occlusion edges and in repeated texture, and single-pixel spikes.  The speckle filter invalidates the connected regions
+ * of similar disparity that are too small to be a surface; the median filter (Hirschmueller's step behind semi-global matching)
+ * removes the spikes.  Both work on the maps of every call above: float[w h], pitch w, and uint32 cost[w h].  The contract is
+ * this project's own; the kernels of csrc/disparity_filter.hip are held to a numpy restatement of it bit for bit
+ * (tests/speckle_ref.py, tests/test_gpu_speckle.py).
+ *   validity    as everywhere in this file: a pixel is valid iff its bit pattern is not 0x7FC00000.  Any other value, other
+ *               NaNs and the infinities included, is a valid pixel and follows the items below as written.
+ *   1 links     two valid pixels that are 4-adjacent, (x +- 1, y) or (x, y +- 1), are linked iff fabsf(d(p) - d(q)) <= maxDiff:
+ *               one IEEE float subtraction and a comparison that is false for a NaN (a NaN pixel links to nothing; inf - inf is
+ *               a NaN).  Symmetric, because a - b = -(b - a) exactly.  No link across an invalid pixel, none diagonally.
+ *   2 components  the connected components of the graph (valid pixels, links): the transitive closure.  A ramp that rises by
+ *               maxDiff per pixel is ONE component, however far its ends are apart.  label(p) = the smallest raster index
+ *               y w + x in p's component; size(p) = the number of pixels of p's component; an invalid pixel has label
+ *               UINT32_MAX and size 0.  w h < 2^31, so both fit.
+ *   3 speckles  in place: a valid pixel with size(p) <= maxSpeckleSize becomes invalid: its disparity becomes 0x7FC00000 and,
+ *               if a cost map is given, its cost UINT32_MAX; nothing else is written.  maxSpeckleSize = 0 removes nothing and is
+ *               legal.  The filter only removes pixels, and whole components at that, so no survivor's component changes: the
+ *               filter is idempotent (twice with the same parameters equals once).
+ *   4 median    out of place, m = radius = 1 or 2.  An invalid input pixel gives an invalid output pixel: holes are never
+ *               filled.  For a valid pixel take the valid pixels of the (2m + 1)^2 window clipped to the image -- the pixel
+ *               itself is among them, so there are n >= 1 -- ordered by the integer key k(f) = b >= 0 ? b : b ^ 0x7FFFFFFF, b the
+ *               bits as int32: the float order, made total, with -0 below +0.  The output is the element of rank (n - 1) / 2
+ *               (integer division): the LOWER median.  It is always one of the input values: no arithmetic, no tolerance.
+ *               The cost map is NOT touched by the median: it goes on describing the winner of the matching call, which
+ *               the output pixel may no longer be.
+ * Refusals, decided on the host before any launch, the parameters before the buffers, invalid before unsupported:
+ *   components, speckles   SSRLCV_ERR_INVALID_ARG for maxDiff a NaN or negative (+inf is legal: every adjacent valid pair whose
+ *               difference is no NaN links), then for w h >= 2^31; a map of 0 pixels is then SSRLCV_OK; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL disparity, labels or workspace (cost and sizes may be NULL); then
+ *               SSRLCV_ERR_WORKSPACE for a short workspace.
+ *   median      SSRLCV_ERR_INVALID_ARG for radius 0 or w h >= 2^31; SSRLCV_ERR_UNSUPPORTED for radius > 2; a map of 0 pixels
+ *               is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL buffer or in == out.  No workspace.
+ * Workspace (host only; 0 for a size the call refuses; computed in size_t), with a256(n) = n rounded up to 256:
+ *     components     a256(4 w h) bytes        the tile-local component counts (needed whether sizes is given or not)
+ *     speckles       2 a256(4 w h) bytes      the labels and those counts: 8 bytes per pixel, 128 MB at 4096 x 4096
+ * The workspace may hold anything on entry: every entry the call reads it has written before.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another (no grid barrier, no spin: the
+ * labelling is union-find in three passes -- tiles in LDS, tile seams, tile roots -- and none is repeated until nothing changes,
+ * so a serpentine through every tile costs what a blob costs).  These are the first calls of the stereo chain with atomics,
+ * integer ones: atomicMin on labels and atomicAdd on counts.  The result is bit-equal run to run all the same, because it is
+ * a property of the component and not of the order in which unions happen: a parent is always a smaller index of the same
+ * component, so whatever the order of the hooks the root of a finished tree is the component's smallest index; a size is a
+ * sum of integers, which has one value in every order.  (A float atomic would not have that property; there is none.)
+ * ssrlcv_hip_disparity_components is the per-kernel export of items 1-2: it writes every entry of labels[w h] and, if given,
+ * of sizes[w h].
+ * Out of scope: hole filling or interpolation of invalid pixels, 8-connectivity, a weighted or bilateral median, radius 3 and
+ * above, a uniqueness ratio, the right view's map. */
+size_t ssrlcv_hip_disparity_components_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_disparity_components(const float* disparity, uint32_t w, uint32_t h, float maxDiff, uint32_t* labels,
+                                    uint32_t* sizes /* may be NULL */, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_stereo_filter_speckles_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_stereo_filter_speckles(float* disparity, uint32_t* cost /* may be NULL */, uint32_t w, uint32_t h, float maxDiff,
+                                      uint32_t maxSpeckleSize, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+int ssrlcv_hip_stereo_filter_median(const float* in, float* out, uint32_t w, uint32_t h, uint32_t radius, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -67,7 +67,8 @@ def load():
                      "ssrlcv_hip_neighbor_filter_workspace_bytes", "ssrlcv_hip_match2_workspace_bytes",
                      "ssrlcv_hip_sift_dense_workspace_bytes", "ssrlcv_hip_stereo_workspace_bytes",
                      "ssrlcv_hip_stereo_matches_workspace_bytes", "ssrlcv_hip_stereo_sgm_workspace_bytes",
-                     "ssrlcv_hip_stereo_census_workspace_bytes", "ssrlcv_hip_stereo_sgm_census_workspace_bytes"):
+                     "ssrlcv_hip_stereo_census_workspace_bytes", "ssrlcv_hip_stereo_sgm_census_workspace_bytes",
+                     "ssrlcv_hip_disparity_components_workspace_bytes", "ssrlcv_hip_stereo_filter_speckles_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -113,4 +114,6 @@ EXPORTED = [
     "ssrlcv_hip_stereo_sgm_census_workspace_bytes", "ssrlcv_hip_stereo_sgm_census_u8",
     "ssrlcv_rectify_cameras_host", "ssrlcv_hip_warp_homography_u8", "ssrlcv_hip_stereo_mask_rectified",
     "ssrlcv_hip_matches_apply_homography",
+    "ssrlcv_hip_disparity_components_workspace_bytes", "ssrlcv_hip_disparity_components",
+    "ssrlcv_hip_stereo_filter_speckles_workspace_bytes", "ssrlcv_hip_stereo_filter_speckles", "ssrlcv_hip_stereo_filter_median",
 ]

@@ -728,6 +728,55 @@ def matches_apply_homography(matches_d, n, H0, H1):
     return matches_d
 
 
+# ------------------------------------------------------------------ disparity post-filters
+def _disparity_map(disp_d):
+    assert disp_d.dim() == 2 and disp_d.dtype == torch.float32 and disp_d.is_cuda and disp_d.is_contiguous()  # read with pitch w
+    return disp_d.shape
+
+
+def _filter_workspace(query, w, h, workspace):
+    need = int(query(c_u32(w), c_u32(h)))
+    return workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
+
+
+def disparity_components(disp_d, max_diff, want_sizes=True, workspace=None):
+    """The connected components of a disparity map (ssrlcv_hip_disparity_components; include/ssrlcv_hip.h "disparity
+    post-filters" items 1-2): 4-adjacent valid pixels whose disparities differ by at most max_diff.  -> (labels, sizes or
+    None), int32 (H, W) holding the uint32 bits: the smallest raster index of the pixel's component and its pixel count;
+    0xFFFFFFFF and 0 for an invalid pixel.  The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    h, w = _disparity_map(disp_d)
+    ws = _filter_workspace(LIB.ssrlcv_hip_disparity_components_workspace_bytes, w, h, workspace)
+    labels = torch.empty((h, w), dtype=torch.int32, device="cuda")
+    sizes = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_sizes else None
+    check(LIB.ssrlcv_hip_disparity_components(ptr(disp_d), c_u32(w), c_u32(h), c_f32(max_diff), ptr(labels), ptr(sizes), ptr(ws),
+                                              c_sz(ws.numel()), stream_ptr()))
+    return labels, sizes
+
+
+def stereo_filter_speckles(disp_d, cost_d, max_size, max_diff, workspace=None):
+    """Invalidates, in place, the components of at most max_size pixels (ssrlcv_hip_stereo_filter_speckles; item 3): their
+    disparity becomes STEREO_INVALID_BITS and, with a cost map (cost_d may be None), their cost 0xFFFFFFFF.
+    -> (disp_d, cost_d).  Asynchronous on the current stream."""
+    h, w = _disparity_map(disp_d)
+    assert cost_d is None or (cost_d.shape == disp_d.shape and cost_d.dtype == torch.int32 and cost_d.is_cuda and cost_d.is_contiguous())
+    assert isinstance(max_size, int) and not isinstance(max_size, bool) and 0 <= max_size <= 0xFFFFFFFF  # c_u32 would wrap it
+    ws = _filter_workspace(LIB.ssrlcv_hip_stereo_filter_speckles_workspace_bytes, w, h, workspace)
+    check(LIB.ssrlcv_hip_stereo_filter_speckles(ptr(disp_d), ptr(cost_d), c_u32(w), c_u32(h), c_f32(max_diff), c_u32(max_size), ptr(ws),
+                                                c_sz(ws.numel()), stream_ptr()))
+    return disp_d, cost_d
+
+
+def stereo_filter_median(disp_d, radius):
+    """The lower median over the valid pixels of the (2 radius + 1)^2 window, radius 1 or 2, of every valid pixel
+    (ssrlcv_hip_stereo_filter_median; item 4); invalid pixels stay invalid.  -> a new float32 (H, W) tensor; a cost map keeps
+    describing the unfiltered winners.  Asynchronous on the current stream."""
+    h, w = _disparity_map(disp_d)
+    assert isinstance(radius, int) and not isinstance(radius, bool) and 0 <= radius <= 0xFFFFFFFF
+    out = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    check(LIB.ssrlcv_hip_stereo_filter_median(ptr(disp_d), ptr(out), c_u32(w), c_u32(h), c_u32(radius), stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

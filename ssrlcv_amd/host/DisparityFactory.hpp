@@ -28,6 +28,12 @@
 //   auto matches = factory.generateMatches(disparity, left, right);
 //   factory.unrectifyMatches(matches, rect);                           // source pixels: triangulate with the original cameras
 //
+// The map-domain post-filters (include/ssrlcv_hip.h "disparity post-filters") are two explicit steps between the map and the
+// matches, behind maskRectified where there is one; the median first is the usual order:
+//
+//   disparity = factory.medianFilter(disparity, 1);                    // a new map: the lower median of the valid 3 x 3 neighbours
+//   factory.filterSpeckles(disparity, nullptr, 200, 1.0f);             // in place: components of at most 200 pixels become invalid
+//
 // Pixels keep upstream's memory-state contract: forced onto the gpu for the call, restored to their origin state after it.
 #pragma once
 #include "Image.hpp"
@@ -43,6 +49,7 @@ class DisparityFactory {
   bool semiGlobal = false;
   unsigned int sgmClamp = 0, sgmP1 = 0, sgmP2 = 0, sgmPaths = 0xFFu;
   unsigned int census = 0;  // 0: SAD costs
+  uint2 mapSize = {0u, 0u};  // of the last generateDisparities: a Unity<float> does not carry its width
 
   static void toGpu(ptr::value<Image> image, MemoryState& origin, bool& keepHost) {
     if (image->colorDepth != 1) {
@@ -93,6 +100,8 @@ class DisparityFactory {
   void clearCensus() { census = 0; }
   // the radius of everything a pixel's cost reads: what maskRectified masks with
   unsigned int footprintRadius() const { return params.radius + census; }
+  // the size of the maps filterSpeckles and medianFilter take; generateDisparities sets it to its pair's
+  void setMapSize(unsigned int w, unsigned int h) { mapSize = uint2{w, h}; }
 
   // disparity of every left pixel (row-major, w x h), in state gpu; `cost` (optional out) receives the winners' costs
   ptr::value<Unity<float>> generateDisparities(ptr::value<Image> left, ptr::value<Image> right,
@@ -102,6 +111,7 @@ class DisparityFactory {
       std::exit(-1);
     }
     const uint32_t w = left->size.x, h = left->size.y;
+    mapSize = uint2{w, h};
     ssrlcv_sgm_params sgm;
     sgm.radius = params.radius;
     sgm.minDisparity = params.minDisparity;
@@ -233,6 +243,47 @@ class DisparityFactory {
     HipCheckError();
     if (origin != gpu) disparity->setMemoryState(origin);
     if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);
+  }
+
+  // in place on a map of generateDisparities (include/ssrlcv_hip.h "disparity post-filters" item 3; the map has the size of
+  // the last pair this factory matched, or what setMapSize said): the connected components of at most maxSpeckleSize pixels
+  // become invalid, two neighbours being connected when their disparities differ by at most maxDiff; cost may be nullptr
+  // (it only removes pixels)
+  void filterSpeckles(ptr::value<Unity<float>> disparity, ptr::value<Unity<unsigned int>> cost, unsigned int maxSpeckleSize, float maxDiff) {
+    const uint32_t w = mapSize.x, h = mapSize.y;
+    const size_t wsBytes = ssrlcv_hip_stereo_filter_speckles_workspace_bytes(w, h);
+    if ((unsigned long)w * h != disparity->size() || (wsBytes == 0 && disparity->size() != 0)) {
+      logger.err << "ERROR: the speckle filter takes a map of the size of the last pair matched (setMapSize for any other)";
+      std::exit(-1);
+    }
+    MemoryState origin = disparity->getMemoryState(), originC = cost != nullptr ? cost->getMemoryState() : gpu;
+    if (origin != gpu) disparity->setMemoryState(gpu);
+    if (cost != nullptr && originC != gpu) cost->setMemoryState(gpu);
+    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+    HipSafeCall(ssrlcv_hip_stereo_filter_speckles(disparity->device.get(), cost != nullptr ? cost->device.get() : nullptr, w, h, maxDiff,
+                                                  maxSpeckleSize, workspace.get(), wsBytes, nullptr));
+    HipCheckError();
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    if (origin != gpu) disparity->setMemoryState(origin);
+    if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);
+  }
+
+  // a new map, in state gpu: every valid pixel becomes the lower median of the valid pixels of its (2 radius + 1)^2 window,
+  // radius 1 or 2; holes stay holes (item 4).  A cost map goes on describing the winners before the filter.
+  ptr::value<Unity<float>> medianFilter(ptr::value<Unity<float>> disparity, unsigned int radius) {
+    const uint32_t w = mapSize.x, h = mapSize.y;
+    if ((unsigned long)w * h != disparity->size()) {
+      logger.err << "ERROR: the median filter takes a map of the size of the last pair matched (setMapSize for any other)";
+      std::exit(-1);
+    }
+    MemoryState origin = disparity->getMemoryState();
+    if (origin != gpu) disparity->setMemoryState(gpu);
+    ptr::value<Unity<float>> filtered(nullptr, disparity->size(), gpu);
+    HipSafeCall(ssrlcv_hip_stereo_filter_median(disparity->device.get(), filtered->device.get(), w, h, radius, nullptr));
+    HipCheckError();
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the source may leave the gpu
+    if (origin != gpu) disparity->setMemoryState(origin);
+    return filtered;
   }
 
   // in place: generateMatches' records of a rectified pair, through Hl and Hr into source pixels; a record that does not

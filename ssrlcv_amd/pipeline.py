@@ -172,18 +172,44 @@ def _dense_disparity(left, right, sgm, disparity_args):
     return stereo_sgm(left, right, want_cost=False, **sgm, **disparity_args)[0]
 
 
-def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, **disparity_args):
+def stereo_filter(disp, cost=None, median=0, speckle_size=0, speckle_diff=1.0):
+    """The map-domain post-filters of include/ssrlcv_hip.h "disparity post-filters" on a disparity map (float32 CUDA tensor
+    (H, W)): median = 1 or 2 first takes every valid pixel to the lower median of the valid pixels of its (2 median + 1)^2 window
+    (a new tensor; holes stay holes; the cost map is not touched); speckle_size > 0 then invalidates, in place on that result
+    (on `disp` itself when no median ran) and on `cost` if given, the connected components of at most speckle_size pixels, two
+    neighbours being connected when their disparities differ by at most speckle_diff.  -> the filtered map."""
+    if median > 0:
+        disp = capi.stereo_filter_median(disp, median)
+    if speckle_size > 0:
+        capi.stereo_filter_speckles(disp, cost, speckle_size, speckle_diff)
+    return disp
+
+
+def _post_filter(disp, post):
+    """stereo_cloud's and stereo_cloud_cameras' post = dict(median=, speckle_size=, speckle_diff=): stereo_filter's arguments"""
+    if post is None:
+        return disp
+    unknown = set(post) - {"median", "speckle_size", "speckle_diff"}
+    if unknown:
+        raise TypeError("post takes median, speckle_size and speckle_diff")
+    return stereo_filter(disp, None, **post)
+
+
+def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, post=None,
+                 **disparity_args):
     """Rectified pair -> dense cloud: stereo_disparity, then capi.stereo_matches (the valid pixels of the `step` grid as Match
     records), then capi.stereo_points (upstream's stereo_disparity: Z = foc baseline / (d + doffset)).  cx, cy default to the
     image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel,
     census (radius is the aggregation radius when census is set; the cost map is not computed: want_cost is not taken).  sgm = dict(cost_clamp=, p1=, p2=[, paths=]): the disparity comes
-    from stereo_sgm with the remaining disparity_args (max_cost is then a TypeError).  -> (points float32 (n, 3), Match bytes, n, disparity).
+    from stereo_sgm with the remaining disparity_args (max_cost is then a TypeError).  post = dict(median=, speckle_size=,
+    speckle_diff=): stereo_filter on the disparity map before the matches are taken from it (any other key is a TypeError); the
+    returned map is the filtered one.  -> (points float32 (n, 3), Match bytes, n, disparity).
     The Match records are the sparse path's: with real cameras they also go through capi.matchset_from_matches and
     triangulate() unchanged (tests/test_gpu_stereo.py does)."""
     h, w = left.shape
     if "want_cost" in disparity_args:
         raise TypeError("stereo_cloud computes no cost map: call stereo_disparity for one")
-    disp = _dense_disparity(left, right, sgm, disparity_args)
+    disp = _post_filter(_dense_disparity(left, right, sgm, disparity_args), post)
     matches, n = capi.stereo_matches(disp, step, left_id, right_id)
     pts = capi.stereo_points(matches, n, foc, baseline, doffset, w / 2.0 if cx is None else cx, h / 2.0 if cy is None else cy)
     return pts, matches, n, disp
@@ -199,11 +225,12 @@ def rectify_pair(left, right, cam_l, cam_r):
     return capi.warp_homography(left, rect["Hl"], shape), capi.warp_homography(right, rect["Hr"], shape), rect
 
 
-def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, **disparity_args):
+def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None, **disparity_args):
     """Unrectified pair -> dense cloud in the world frame of triangulate()'s clouds: rectify_pair, stereo_disparity, the mask
     of the windows that left a source image (capi.stereo_mask_rectified), capi.stereo_matches, the records mapped back into
     source pixels (capi.matches_apply_homography), compacted, then capi.matchset_from_matches and the two-view triangulation
-    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args and sgm as for stereo_cloud; with
+    (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args, sgm and post as for stereo_cloud
+    (post runs behind the mask; a median-moved pixel that no longer maps back leaves with the compaction); with
     census set, radius is the aggregation radius and the mask takes the footprint radius + census.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
     matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
     if "want_cost" in disparity_args:
@@ -212,6 +239,7 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, **disparit
     disp = _dense_disparity(left_r, right_r, sgm, disparity_args)
     footprint = disparity_args.get("radius", 4 if sgm is None else 2) + disparity_args.get("census", 0)
     capi.stereo_mask_rectified(disp, None, footprint, rect)
+    disp = _post_filter(disp, post)    # behind the mask: it removes pixels whose evidence left a source image before the filters look at neighbourhoods
     matches, n = capi.stereo_matches(disp, step, 0, 1)
     capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
     if n:
