@@ -51,7 +51,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      semi-global matching: stereo_sgm_workspace_bytes, stereo_sgm_u8, stereo_sgm_set_pass_events;
  *      census cost: census_u8, stereo_census_workspace_bytes, stereo_census_u8, stereo_sgm_census_workspace_bytes,
  *      stereo_sgm_census_u8;
- *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median */
+ *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median;
+ *      hole filling: stereo_fill_holes (+ its workspace query) */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -906,7 +907,7 @@ int ssrlcv_hip_matches_apply_homography(ssrlcv_match* matches, uint32_t n, const
  * sum of integers, which has one value in every order.  (A float atomic would not have that property; there is none.)
  * ssrlcv_hip_disparity_components is the per-kernel export of items 1-2: it writes every entry of labels[w h] and, if given,
  * of sizes[w h].
- * Out of scope: hole filling or interpolation of invalid pixels, 8-connectivity, a weighted or bilateral median, radius 3 and
+ * Out of scope: filling the holes (the next section, "hole filling"), 8-connectivity, a weighted or bilateral median, radius 3 and
  * above, a uniqueness ratio, the right view's map. */
 size_t ssrlcv_hip_disparity_components_workspace_bytes(uint32_t w, uint32_t h);
 int ssrlcv_hip_disparity_components(const float* disparity, uint32_t w, uint32_t h, float maxDiff, uint32_t* labels,
@@ -915,6 +916,52 @@ size_t ssrlcv_hip_stereo_filter_speckles_workspace_bytes(uint32_t w, uint32_t h)
 int ssrlcv_hip_stereo_filter_speckles(float* disparity, uint32_t* cost /* may be NULL */, uint32_t w, uint32_t h, float maxDiff,
                                       uint32_t maxSpeckleSize, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 int ssrlcv_hip_stereo_filter_median(const float* in, float* out, uint32_t w, uint32_t h, uint32_t radius, ssrlcv_stream_t stream);
+
+/* ---- hole filling: every stage behind the winner only removes pixels -- the left-right check, maxCost, the rectification mask
+ * and the speckle filter each punch holes -- and this call closes them: a hole takes one of the measured disparities that lie
+ * nearest to it along up to eight directions (Hirschmueller's step behind the peak filter).  Selection only, no arithmetic on
+ * disparities: the kernels of csrc/disparity_filter.hip are held to a numpy restatement bit for bit (tests/fill_ref.py,
+ * tests/test_gpu_fill.py).  Maps as in "disparity post-filters": float[w h], pitch w.
+ *   validity    as everywhere in this file: a pixel is valid iff its bit pattern is not 0x7FC00000; other NaNs, the infinities
+ *               and -0 are valid values.  A valid pixel of `in` is MEASURED, every other pixel is a HOLE.
+ *   1 sources   bit i of `paths` selects direction i, with the (dx, dy) of "semi-global matching" item 2; direction i carries
+ *               values along (dx, dy): for a hole p, hit_i(p) is the first measured pixel among p - t (dx, dy), t = 1, 2, ...,
+ *               while that point is inside the image and t <= maxGap.  If the ray leaves the image or passes maxGap first, the
+ *               hole has no hit in that direction.  maxGap = 0 fills nothing; UINT32_MAX is no limit.  Only `in` is looked at: a
+ *               filled value is never a source, so the result does not depend on any order of evaluation.  A second call on
+ *               the output may therefore fill more: the filter is NOT idempotent.
+ *   2 count     n = the number of selected directions with a hit.  If n < minHits the hole stays a hole.
+ *   3 value     the n hit values ordered by the integer key of the median filter ("disparity post-filters" item 4),
+ *               k(f) = b >= 0 ? b : b ^ 0x7FFFFFFF: rule 0 (MIN) takes rank 0, the smallest disparity -- the background, which
+ *               is what an occlusion hides; rule 1 (MEDIAN) takes rank (n - 1) / 2, the lower median.  The output is always one
+ *               of the input values: no arithmetic, no tolerance.
+ *   4 outputs   out of place; every pixel of `out` and, if given, of `filled` is written and nothing behind either map.
+ *               out(p) = the bits of in(p) for a measured pixel; for a hole the value of item 3, or 0x7FC00000.  filled(p) = 1
+ *               for a hole that got a value, 0 everywhere else.  No cost map is touched: a filled pixel keeps the UINT32_MAX
+ *               its matching call wrote, so a caller who holds a cost map can tell measured from filled by that.
+ * Refusals, decided on the host before any launch, the parameters before the buffers, invalid before anything else:
+ * SSRLCV_ERR_INVALID_ARG for params NULL, paths 0 or above 0xFF, minHits 0 or above popcount(paths), rule > 1, then w h >= 2^31;
+ * a map of 0 pixels is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for `in`, `out` or workspace NULL, or in == out (filled may
+ * be NULL); then SSRLCV_ERR_WORKSPACE for a short workspace.
+ * Workspace (host only; computed in size_t; 0 for a refused parameter or size and for an empty map):
+ *     popcount(paths) a256(4 w h) bytes        one hit map per selected direction
+ * It may hold anything on entry: a pass stores hit_i(p) at the holes only, the invalid pattern where there is none -- the
+ * natural "no hit" entry, because no measured value has it -- and the maps are read at the holes only.
+ * Execution: asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.
+ * Until its pixels are written, `out` is the call's scratch for the carries that one strip of a column or diagonal hands to the
+ * next.  The work per pixel and direction is O(1) whatever the gap: a carry of (last measured value, steps since it) along every row,
+ * column and diagonal, never a ray walk; no loop depends on the extent of a hole or on maxGap.
+ * Out of scope: interpolation that computes new values (linear, plane fits), telling occlusions from mismatches by the right
+ * view's map, sources weighted by distance, more than 8 directions. */
+typedef struct {
+  uint32_t paths;   /* bit mask 1..0xFF, the direction numbering of semi-global matching */
+  uint32_t maxGap;  /* a source further than this many steps away does not count; 0 fills nothing; UINT32_MAX = no limit */
+  uint32_t minHits; /* 1 .. popcount(paths): a hole with fewer sources stays a hole */
+  uint32_t rule;    /* 0 = MIN (background), 1 = MEDIAN (lower) */
+} ssrlcv_fill_params; /* 16 bytes */
+size_t ssrlcv_hip_stereo_fill_holes_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_fill_params* params);
+int ssrlcv_hip_stereo_fill_holes(const float* in, float* out, uint8_t* filled /* may be NULL */, uint32_t w, uint32_t h,
+                                 const ssrlcv_fill_params* params, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

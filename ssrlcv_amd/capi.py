@@ -777,6 +777,35 @@ def stereo_filter_median(disp_d, radius):
     return out
 
 
+# ------------------------------------------------------------------ hole filling
+class FillParams(ctypes.Structure):
+    _fields_ = [("paths", c_u32), ("maxGap", c_u32), ("minHits", c_u32), ("rule", c_u32)]
+
+
+FILL_MIN = 0      # rule: the smallest of the hits, the background
+FILL_MEDIAN = 1   # rule: their lower median
+FILL_NO_LIMIT = 0xFFFFFFFF  # max_gap: a source counts however far away it is
+
+
+def stereo_fill_holes(disp_d, paths, max_gap, min_hits, rule, want_mask=False, workspace=None):
+    """Fills the holes of a disparity map (ssrlcv_hip_stereo_fill_holes; include/ssrlcv_hip.h "hole filling"): a hole takes the
+    smallest (rule = FILL_MIN) or the lower median (FILL_MEDIAN) of the first measured pixels within max_gap steps along the
+    directions of the bit mask `paths` (semi-global matching's numbering), if at least min_hits directions have one.  Out of
+    place: -> (a new float32 (H, W) tensor, mask or None); the mask is uint8 (H, W), 1 at the holes that got a value.  A cost
+    map is not touched.  The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    h, w = _disparity_map(disp_d)
+    for v in (paths, max_gap, min_hits, rule):
+        assert isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 0xFFFFFFFF  # c_u32 would wrap it
+    p = FillParams(paths, max_gap, min_hits, rule)
+    need = int(LIB.ssrlcv_hip_stereo_fill_holes_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(max(need, 1))
+    out = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    mask = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_mask else None
+    check(LIB.ssrlcv_hip_stereo_fill_holes(ptr(disp_d), ptr(out), ptr(mask), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ws), c_sz(ws.numel()),
+                                           stream_ptr()))
+    return out, mask
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -1,7 +1,10 @@
 // ssrlcv_amd/csrc/disparity_filter.hip -- the map-domain post-filters of the dense stereo chain: connected components of a
 // disparity map (4-adjacent valid pixels whose disparities differ by at most maxDiff), the speckle filter that invalidates the
-// components of at most maxSpeckleSize pixels, and the lower median over the valid pixels of a 3 x 3 or 5 x 5 window.
+// components of at most maxSpeckleSize pixels, the lower median over the valid pixels of a 3 x 3 or 5 x 5 window, and hole
+// filling from the nearest measured pixels along up to eight directions.
 // The contract is include/ssrlcv_hip.h "disparity post-filters"; tests/speckle_ref.py restates it operation by operation.
+// Hole filling is "hole filling" there and tests/fill_ref.py; its kernels (k_fill_rows, k_fill_march, k_fill_select) are
+// described where they stand, below the median.
 //
 // Labelling is union-find, never label propagation: no pass is repeated until nothing changes, so a serpentine that crosses
 // every tile costs what a blob costs.  `labels` is the parent array of one forest over the pixels; a parent is always a
@@ -29,6 +32,7 @@
 // forest (entries only ever decrease, along links).  The atomics decide at the L2, so a hook on a pixel that is no longer a
 // root is seen by its return value and taken up from there.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <math.h>
 #include <stdint.h>
 #include "ssrlcv_hip.h"
@@ -311,6 +315,181 @@ __global__ __launch_bounds__(256) void k_median(const float* __restrict__ in, fl
   }
 }
 
+// ---- hole filling (include/ssrlcv_hip.h "hole filling"; tests/fill_ref.py restates it)
+// Every selected direction gets a hit map in the workspace: at a hole, the first measured value upstream within maxGap steps,
+// else the invalid pattern.  A carry along the line -- the last measured value and the steps since it -- makes that O(1) per
+// pixel whatever the gap.  Only holes are stored to, and k_fill_select reads the maps only at holes, so the entries at measured
+// pixels may hold anything.
+struct FillDirs {
+  uint32_t count;  // selected directions, in the order of the bits
+  uint8_t dir[8];
+};
+
+// One lane per line of direction (DX, DY), DY != 0, a wave per block.  Step s of the march is row y = s (DY > 0) or h - 1 - s;
+// line c is at x = c + DX s there, so the lanes of a wave read 64 neighbouring x of one row.  c runs over -(h - 1) .. w - 1 for
+// DX = +1 (the lines with c < 0 start on the first column), 0 .. w + h - 2 for DX = -1, 0 .. w - 1 for a column.  A wave only
+// walks the rows in which one of its lines is inside the image; a line enters once and leaves once, so a lane outside has
+// nothing to carry.  The loads do not depend on the carry: kFillRows rows are in flight, loaded before the first is looked at.
+//
+// One wave per 64 lines is (w + h) / 64 waves per direction, each waiting for h / kFillRows round trips to memory one after the
+// other: too few to fill the chip.  So the steps are cut into strips of `stripRows`, and a wave marches one strip of its lines.
+// What a strip hands on is the carry itself -- the last measured value in it (the invalid pattern: none) and the steps since --
+// so a first launch (kSummary) marches every strip but the last from an empty carry and stores no hit, only that pair; the
+// second folds the pairs of the strips upstream of its own into its carry-in, at most strips - 1 coalesced loads that depend on
+// the image's height and on nothing in it, and marches with the stores.
+constexpr int kFillRows = 16;
+constexpr uint32_t kFillStripRows = 128;  // the strips of a large map; a multiple of kFillRows
+constexpr uint32_t kFillMaxStrips = 1024;
+
+struct FillStrips {
+  uint32_t rows, count;  // steps per strip, strips
+  uint32_t* carries;     // [direction slot][strip < count - 1][line][value, steps]; lineStride lines, a multiple of 64
+  uint32_t lineStride;
+};
+
+template <int DX, int DY, bool kSummary>
+__device__ __forceinline__ void fill_march(const uint32_t* __restrict__ in, uint32_t* __restrict__ hit, long long w, long long h, uint32_t maxGap,
+                                           long long block, uint32_t strip, const FillStrips& strips, uint32_t* __restrict__ carries) {
+  const long long c0 = block * 64 - (DX > 0 ? h - 1 : 0);
+  if (c0 >= (DX < 0 ? w + h - 1 : w)) return;
+  const long long c = c0 + threadIdx.x;
+  // the steps of this strip in which one of the wave's lines is inside the image
+  long long sLo = (long long)strip * strips.rows, sHi = min(h, sLo + strips.rows) - 1;
+  if (DX > 0) {
+    sLo = max(sLo, -(c0 + 63));
+    sHi = min(sHi, w - 1 - c0);
+  } else if (DX < 0) {
+    sLo = max(sLo, c0 - (w - 1));
+    sHi = min(sHi, c0 + 63);
+  }
+  const size_t line = (size_t)block * 64 + threadIdx.x;  // below lineStride
+  uint32_t value = kNaN, steps = 0;  // steps stays below w + h < 2^32: it cannot wrap, so it need not saturate
+  if (!kSummary) {
+#pragma unroll 8
+    for (uint32_t k = 0; k < strip; ++k) {
+      const uint32_t* e = carries + ((size_t)k * strips.lineStride + line) * 2;
+      const uint32_t stripValue = e[0], stripSteps = e[1];
+      steps = stripValue != kNaN ? stripSteps : steps + stripSteps;
+      value = stripValue != kNaN ? stripValue : value;
+    }
+  }
+  for (long long s = sLo; s <= sHi; s += kFillRows) {
+    uint32_t v[kFillRows];
+    size_t at[kFillRows];
+    bool inside[kFillRows];
+#pragma unroll
+    for (int j = 0; j < kFillRows; ++j) {
+      const long long sj = s + j, x = c + DX * sj;
+      inside[j] = sj <= sHi && x >= 0 && x < w;
+      // a lane outside loads the nearest pixel of the row inside instead (and drops it): no branch around the load
+      const long long y = DY > 0 ? min(sj, sHi) : h - 1 - min(sj, sHi);
+      at[j] = (size_t)(y * w + min(max(x, 0ll), w - 1));
+      v[j] = in[at[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < kFillRows; ++j) {
+      if (!inside[j]) continue;
+      if (v[j] != kNaN) {
+        value = v[j];
+        steps = 0;
+      } else {
+        ++steps;
+        if (!kSummary) hit[at[j]] = steps <= maxGap ? value : kNaN;  // value is the invalid pattern until the line has met a measured pixel
+      }
+    }
+  }
+  if (kSummary) {  // a wave with no step in this strip hands on (none, 0) like a lane that was outside throughout
+    uint32_t* e = carries + ((size_t)strip * strips.lineStride + line) * 2;
+    e[0] = value;
+    e[1] = steps;
+  }
+}
+
+// grid (blocks of 64 lines, strips -- all but the last for kSummary --, the selected non-horizontal directions)
+template <bool kSummary>
+__global__ __launch_bounds__(64) void k_fill_march(const uint32_t* __restrict__ in, uint32_t* __restrict__ hits, size_t mapStride, uint32_t w, uint32_t h,
+                                                   uint32_t maxGap, FillDirs slots, FillDirs dirs, FillStrips strips) {
+  const uint32_t dir = dirs.dir[blockIdx.z], strip = blockIdx.y;
+  uint32_t* hit = hits + slots.dir[blockIdx.z] * mapStride;
+  uint32_t* carries = strips.carries + (size_t)blockIdx.z * (strips.count - 1u) * strips.lineStride * 2;
+  switch (dir) {
+    case 2: fill_march<0, 1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+    case 3: fill_march<0, -1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+    case 4: fill_march<1, 1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+    case 5: fill_march<-1, 1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+    case 6: fill_march<1, -1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+    default: fill_march<-1, -1, kSummary>(in, hit, w, h, maxGap, blockIdx.x, strip, strips, carries); break;
+  }
+}
+
+// The two horizontal directions: a wave per row, 64 pixels at a time in the direction of the carry (lane l is pixel 64 i + l
+// from the row's upstream end).  Inside a chunk the last measured pixel below a lane comes from one ballot and one shuffle; the
+// chunk's last measured value and its distance from the chunk's end are the carry into the next.
+// grid (rows / 4, the selected horizontal directions)
+__global__ __launch_bounds__(256) void k_fill_rows(const uint32_t* __restrict__ in, uint32_t* __restrict__ hits, size_t mapStride, uint32_t w, uint32_t h,
+                                                   uint32_t maxGap, FillDirs slots, FillDirs dirs) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const size_t y = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (y >= h) return;
+  const bool mirrored = dirs.dir[blockIdx.y] == 1u;  // direction 1 carries from the right end to the left
+  const uint32_t* row = in + y * w;
+  uint32_t* hit = hits + slots.dir[blockIdx.y] * mapStride + y * w;
+  uint32_t value = kNaN, steps = 0;  // of the chunks behind: the last measured value, its distance from the last chunk's end (below w + 64)
+  for (uint32_t base = 0; base < w; base += 64u) {  // w < 2^31: base + 64 cannot wrap
+    const uint32_t i = base + lane;
+    const uint32_t x = mirrored ? w - 1u - i : i;
+    const uint32_t v = i < w ? row[x] : kNaN;
+    const unsigned long long measured = __ballot(v != kNaN);
+    const unsigned long long below = measured & ((1ull << lane) - 1ull);
+    const int source = below ? 63 - __clzll((long long)below) : 0;
+    const uint32_t near = (uint32_t)__shfl((int)v, source);
+    if (i < w && v == kNaN) {
+      const uint32_t found = below ? near : value;
+      const uint32_t t = below ? lane - (uint32_t)source : steps + lane + 1u;
+      hit[x] = t <= maxGap ? found : kNaN;
+    }
+    if (measured) {
+      const int top = 63 - __clzll((long long)measured);
+      value = (uint32_t)__shfl((int)v, top);
+      steps = 63u - (uint32_t)top;
+    } else {
+      steps += 64u;
+    }
+  }
+}
+
+// measured pixels pass through; a hole takes rank 0 or (n - 1) / 2 of the n hits its selected maps hold, if n >= minHits
+__global__ __launch_bounds__(256) void k_fill_select(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint8_t* __restrict__ filled,
+                                                     const uint32_t* __restrict__ hits, size_t mapStride, uint32_t n, uint32_t maps, uint32_t minHits,
+                                                     uint32_t rule) {
+  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < n; p += gridDim.x * 256u) {
+    uint32_t result = in[p];
+    uint8_t mark = 0;
+    if (result == kNaN) {
+      int32_t a[8];
+      int found = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t bits = (uint32_t)k < maps ? hits[k * mapStride + p] : kNaN;
+        const bool valid = bits != kNaN;
+        found += valid ? 1 : 0;
+        a[k] = valid ? order_key(bits) : INT32_MAX;
+      }
+      if (found > 0 && (uint32_t)found >= minHits) {
+        sort_network<8>(a);
+        const int rank = rule ? (found - 1) / 2 : 0;
+        int32_t key = a[0];
+#pragma unroll
+        for (int k = 1; k <= 3; ++k) key = rank == k ? a[k] : key;
+        result = (uint32_t)order_key((uint32_t)key);
+        mark = 1;
+      }
+    }
+    out[p] = result;
+    if (filled) filled[p] = mark;
+  }
+}
+
 // ---- host side
 bool too_many_pixels(uint32_t w, uint32_t h) { return (unsigned long long)w * h >= (1ull << 31); }
 
@@ -389,6 +568,64 @@ int ssrlcv_hip_stereo_filter_median(const float* in, float* out, uint32_t w, uin
     hipLaunchKernelGGL(k_median<1>, dim3(tx * ty), dim3(256), 0, (hipStream_t)stream, in, out, w, h, tx);
   else
     hipLaunchKernelGGL(k_median<2>, dim3(tx * ty), dim3(256), 0, (hipStream_t)stream, in, out, w, h, tx);
+  SSRLCV_LAUNCH_CHECK();
+  return SSRLCV_OK;
+}
+
+static bool bad_fill_params(const ssrlcv_fill_params* p) {
+  if (!p || p->paths == 0 || p->paths > 0xFFu) return true;
+  return p->minHits == 0 || p->minHits > (uint32_t)__builtin_popcount(p->paths) || p->rule > 1;
+}
+
+size_t ssrlcv_hip_stereo_fill_holes_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_fill_params* params) {
+  if (bad_fill_params(params) || too_many_pixels(w, h)) return 0;
+  return (size_t)__builtin_popcount(params->paths) * align256((size_t)4 * w * h);
+}
+
+int ssrlcv_hip_stereo_fill_holes(const float* in, float* out, uint8_t* filled, uint32_t w, uint32_t h, const ssrlcv_fill_params* params,
+                                 void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream) {
+  if (bad_fill_params(params) || too_many_pixels(w, h)) return SSRLCV_ERR_INVALID_ARG;
+  if (w == 0 || h == 0) return SSRLCV_OK;
+  if (!in || !out || !workspace || in == out) return SSRLCV_ERR_INVALID_ARG;
+  if (workspaceBytes < ssrlcv_hip_stereo_fill_holes_workspace_bytes(w, h, params)) return SSRLCV_ERR_WORKSPACE;
+  const uint32_t n = w * h;
+  const size_t mapStride = align256((size_t)4 * n) / 4;
+  // slot = the direction's place among the selected ones; the horizontal directions share a launch, and so do the six others
+  FillDirs rowDirs = {}, rowSlots = {}, marchDirs = {}, marchSlots = {};
+  uint32_t maps = 0;
+  for (uint32_t d = 0; d < 8; ++d) {
+    if (!(params->paths >> d & 1u)) continue;
+    FillDirs& dirs = d < 2 ? rowDirs : marchDirs;
+    FillDirs& slots = d < 2 ? rowSlots : marchSlots;
+    dirs.dir[dirs.count] = (uint8_t)d;
+    slots.dir[dirs.count++] = (uint8_t)maps++;
+  }
+  const uint32_t* src = (const uint32_t*)in;
+  uint32_t* hits = (uint32_t*)workspace;
+  if (params->maxGap == 0) maps = 0;  // nothing is within 0 steps: no map is written and none is read
+  if (maps && rowDirs.count)
+    hipLaunchKernelGGL(k_fill_rows, dim3((h + 3u) / 4u, rowDirs.count), dim3(256), 0, (hipStream_t)stream, src, hits, mapStride, w, h, params->maxGap,
+                       rowSlots, rowDirs);
+  if (maps && marchDirs.count) {
+    // strips of kFillStripRows steps, fewer and longer ones if their carries -- 8 bytes per direction, strip but the last and
+    // line -- would not fit where they are kept: in `out`, which nothing else touches before k_fill_select writes every pixel
+    const uint32_t lineBlocks = (uint32_t)(((size_t)w + h - 1u + 63u) / 64u);
+    FillStrips strips = {kFillStripRows, (h + kFillStripRows - 1u) / kFillStripRows, (uint32_t*)out, lineBlocks * 64u};
+    const size_t carryBytes = (size_t)marchDirs.count * strips.lineStride * 8u;  // of one strip
+    const size_t most = std::min<size_t>(kFillMaxStrips, 1u + (size_t)4 * n / carryBytes);
+    if (strips.count > most) {
+      const size_t rows = ((size_t)h + most - 1u) / most;
+      strips.rows = (uint32_t)((rows + kFillRows - 1u) / kFillRows * kFillRows);
+      strips.count = (h + strips.rows - 1u) / strips.rows;
+    }
+    if (strips.count > 1u)
+      hipLaunchKernelGGL(k_fill_march<true>, dim3(lineBlocks, strips.count - 1u, marchDirs.count), dim3(64), 0, (hipStream_t)stream, src, hits, mapStride,
+                         w, h, params->maxGap, marchSlots, marchDirs, strips);
+    hipLaunchKernelGGL(k_fill_march<false>, dim3(lineBlocks, strips.count, marchDirs.count), dim3(64), 0, (hipStream_t)stream, src, hits, mapStride, w, h,
+                       params->maxGap, marchSlots, marchDirs, strips);
+  }
+  hipLaunchKernelGGL(k_fill_select, dim3(capped_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, (uint32_t*)out, filled, hits, mapStride, n, maps,
+                     params->minHits, params->rule);
   SSRLCV_LAUNCH_CHECK();
   return SSRLCV_OK;
 }

@@ -33,6 +33,7 @@
 //
 //   disparity = factory.medianFilter(disparity, 1);                    // a new map: the lower median of the valid 3 x 3 neighbours
 //   factory.filterSpeckles(disparity, nullptr, 200, 1.0f);             // in place: components of at most 200 pixels become invalid
+//   disparity = factory.fillHoles(disparity, 0xFF, 32, 5, 0);          // a new map: holes take the smallest of >= 5 measured neighbours
 //
 // Pixels keep upstream's memory-state contract: forced onto the gpu for the call, restored to their origin state after it.
 #pragma once
@@ -284,6 +285,38 @@ class DisparityFactory {
     HipSafeCall(ssrlcv_hip_device_synchronize());  // the source may leave the gpu
     if (origin != gpu) disparity->setMemoryState(origin);
     return filtered;
+  }
+
+  // a new map, in state gpu (include/ssrlcv_hip.h "hole filling"): every hole takes the smallest (rule 0) or the lower median
+  // (rule 1) of the first measured pixels within maxGap steps along the directions of the bit mask `paths` (setSemiGlobal's
+  // numbering), if at least minHits directions have one; measured pixels pass through.  Only measured pixels are sources, so
+  // a second call may fill more.  A cost map is not touched: a filled pixel keeps its UINT32_MAX.  It runs last, behind
+  // medianFilter and filterSpeckles; with a rectification, maskRectified once more behind it.
+  ptr::value<Unity<float>> fillHoles(ptr::value<Unity<float>> disparity, unsigned int paths, unsigned int maxGap, unsigned int minHits, unsigned int rule) {
+    return fillHoles(disparity, paths, maxGap, minHits, rule, nullptr);
+  }
+
+  // ... and *filled (if not nullptr) becomes a new map in state gpu: 1 at the holes that got a value, 0 everywhere else
+  ptr::value<Unity<float>> fillHoles(ptr::value<Unity<float>> disparity, unsigned int paths, unsigned int maxGap, unsigned int minHits, unsigned int rule,
+                                     ptr::value<Unity<unsigned char>>* filled) {
+    const uint32_t w = mapSize.x, h = mapSize.y;
+    const ssrlcv_fill_params params = {paths, maxGap, minHits, rule};
+    if ((unsigned long)w * h != disparity->size()) {
+      logger.err << "ERROR: hole filling takes a map of the size of the last pair matched (setMapSize for any other)";
+      std::exit(-1);
+    }
+    const size_t wsBytes = ssrlcv_hip_stereo_fill_holes_workspace_bytes(w, h, &params);  // 0 for refused parameters: the call says so
+    MemoryState origin = disparity->getMemoryState();
+    if (origin != gpu) disparity->setMemoryState(gpu);
+    ptr::value<Unity<float>> out(nullptr, disparity->size(), gpu);
+    if (filled != nullptr) *filled = ptr::value<Unity<unsigned char>>(nullptr, disparity->size(), gpu);
+    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+    HipSafeCall(ssrlcv_hip_stereo_fill_holes(disparity->device.get(), out->device.get(), filled != nullptr ? (*filled)->device.get() : nullptr, w, h,
+                                             &params, workspace.get(), wsBytes, nullptr));
+    HipCheckError();
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    if (origin != gpu) disparity->setMemoryState(origin);
+    return out;
   }
 
   // in place: generateMatches' records of a rectified pair, through Hl and Hr into source pixels; a record that does not

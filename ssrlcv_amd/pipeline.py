@@ -185,14 +185,36 @@ def stereo_filter(disp, cost=None, median=0, speckle_size=0, speckle_diff=1.0):
     return disp
 
 
+_FILL_RULES = {"min": capi.FILL_MIN, "median": capi.FILL_MEDIAN}
+
+
+def stereo_fill(disp, paths=0xFF, max_gap=32, min_hits=5, rule="min", want_mask=False):
+    """Fills the holes of a disparity map (float32 CUDA tensor (H, W); include/ssrlcv_hip.h "hole filling"): a hole looks up to
+    max_gap steps along each direction of the bit mask `paths` (semi-global matching's numbering) for the first measured
+    pixel; with at least min_hits such sources it takes the smallest of them (rule "min": the background, which is what an
+    occlusion hides) or their lower median ("median"); any other rule is a ValueError.  Only measured pixels are sources, never
+    filled ones.  min_hits = 5 of 8 is the count a hole next to the image border still reaches; a pixel outside a straight edge
+    of the valid region sees 3 and stays a hole.  -> the filled map, a new tensor; with want_mask (map, uint8 mask of the
+    filled holes).  A cost map is not touched: a filled pixel keeps its 0xFFFFFFFF."""
+    if rule not in _FILL_RULES:
+        raise ValueError("rule is 'min' or 'median', not %r" % (rule,))
+    out, mask = capi.stereo_fill_holes(disp, paths, max_gap, min_hits, _FILL_RULES[rule], want_mask)
+    return (out, mask) if want_mask else out
+
+
 def _post_filter(disp, post):
-    """stereo_cloud's and stereo_cloud_cameras' post = dict(median=, speckle_size=, speckle_diff=): stereo_filter's arguments"""
+    """stereo_cloud's and stereo_cloud_cameras' post = dict(median=, speckle_size=, speckle_diff=, fill=): stereo_filter's
+    arguments, and fill = dict(...) of stereo_fill's (without want_mask), which runs last"""
     if post is None:
         return disp
-    unknown = set(post) - {"median", "speckle_size", "speckle_diff"}
-    if unknown:
-        raise TypeError("post takes median, speckle_size and speckle_diff")
-    return stereo_filter(disp, None, **post)
+    unknown = set(post) - {"median", "speckle_size", "speckle_diff", "fill"}
+    fill = post.get("fill")
+    if unknown or (fill is not None and (not isinstance(fill, dict) or set(fill) - {"paths", "max_gap", "min_hits", "rule"})):
+        raise TypeError("post takes median, speckle_size, speckle_diff and fill = dict(paths=, max_gap=, min_hits=, rule=)")
+    if fill is not None and fill.get("rule", "min") not in _FILL_RULES:
+        raise ValueError("rule is 'min' or 'median', not %r" % (fill["rule"],))
+    disp = stereo_filter(disp, None, **{k: v for k, v in post.items() if k != "fill"})
+    return disp if fill is None else stereo_fill(disp, **fill)
 
 
 def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, post=None,
@@ -202,8 +224,8 @@ def stereo_cloud(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step
     image centre.  disparity_args: stereo_disparity's radius, min_disparity, num_disparities, max_cost, lr_tolerance, subpixel,
     census (radius is the aggregation radius when census is set; the cost map is not computed: want_cost is not taken).  sgm = dict(cost_clamp=, p1=, p2=[, paths=]): the disparity comes
     from stereo_sgm with the remaining disparity_args (max_cost is then a TypeError).  post = dict(median=, speckle_size=,
-    speckle_diff=): stereo_filter on the disparity map before the matches are taken from it (any other key is a TypeError); the
-    returned map is the filtered one.  -> (points float32 (n, 3), Match bytes, n, disparity).
+    speckle_diff=, fill=): stereo_filter on the disparity map before the matches are taken from it, then, with fill =
+    dict(paths=, max_gap=, min_hits=, rule=), stereo_fill (any other key is a TypeError); the returned map is the filtered one.  -> (points float32 (n, 3), Match bytes, n, disparity).
     The Match records are the sparse path's: with real cameras they also go through capi.matchset_from_matches and
     triangulate() unchanged (tests/test_gpu_stereo.py does)."""
     h, w = left.shape
@@ -230,7 +252,8 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None,
     of the windows that left a source image (capi.stereo_mask_rectified), capi.stereo_matches, the records mapped back into
     source pixels (capi.matches_apply_homography), compacted, then capi.matchset_from_matches and the two-view triangulation
     (capi.generate_bundles, capi.triangulate) with the two original cameras.  disparity_args, sgm and post as for stereo_cloud
-    (post runs behind the mask; a median-moved pixel that no longer maps back leaves with the compaction); with
+    (post runs behind the mask; a median-moved pixel that no longer maps back leaves with the compaction; after a fill the
+    mask runs once more, so a value extrapolated to where a window leaves a source image is removed again); with
     census set, radius is the aggregation radius and the mask takes the footprint radius + census.  -> (points float32 (n, 3), Match bytes, n, disparity, rect); the
     matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
     if "want_cost" in disparity_args:
@@ -240,6 +263,8 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None,
     footprint = disparity_args.get("radius", 4 if sgm is None else 2) + disparity_args.get("census", 0)
     capi.stereo_mask_rectified(disp, None, footprint, rect)
     disp = _post_filter(disp, post)    # behind the mask: it removes pixels whose evidence left a source image before the filters look at neighbourhoods
+    if post is not None and post.get("fill") is not None:
+        capi.stereo_mask_rectified(disp, None, footprint, rect)   # the fill extrapolates past the mask's edge: the mask only removes, never adds
     matches, n = capi.stereo_matches(disp, step, 0, 1)
     capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
     if n:
