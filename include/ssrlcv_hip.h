@@ -52,7 +52,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      census cost: census_u8, stereo_census_workspace_bytes, stereo_census_u8, stereo_sgm_census_workspace_bytes,
  *      stereo_sgm_census_u8;
  *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median;
- *      hole filling: stereo_fill_holes (+ its workspace query) */
+ *      hole filling: stereo_fill_holes (+ its workspace query);
+ *      disparity mesh: disparity_mesh, mesh_select, mesh_triangles (+ their workspace queries), mesh_normals */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -962,6 +963,87 @@ typedef struct {
 size_t ssrlcv_hip_stereo_fill_holes_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_fill_params* params);
 int ssrlcv_hip_stereo_fill_holes(const float* in, float* out, uint8_t* filled /* may be NULL */, uint32_t w, uint32_t h,
                                  const ssrlcv_fill_params* params, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- disparity mesh: a disparity map is an organised cloud -- every point knows its neighbours -- so a triangle mesh and
+ * normals need no k-NN and no viewpoint heuristic: the sampling grid gives the connectivity, a disparity jump marks a depth
+ * edge, the vertex numbering is ssrlcv_hip_stereo_matches' (the faces index the clouds made from its records) and the face
+ * winding orients the normals.  Everything is a selection or a fixed-order float32 expression: the kernels of csrc/mesh.hip
+ * are held to a numpy restatement bit for bit (tests/mesh_ref.py, tests/test_gpu_mesh.py).
+ *   grid        the nodes are the pixels with x % step == 0 and y % step == 0: gw = (w - 1) / step + 1 columns and gh =
+ *               (h - 1) / step + 1 rows of them (0 for w or h 0), the grid of ssrlcv_hip_stereo_matches; node (i, j) is pixel
+ *               (i step, j step) and d(i, j) its disparity.  Maps over nodes are row-major with pitch gw.
+ *   validity    as everywhere in this file: a node is valid iff its disparity's bit pattern is not 0x7FC00000; other NaNs, the
+ *               infinities and -0 are valid values.
+ *   1 vertices  vertexIndex[gw gh] (uint32): a valid node holds its rank among the valid nodes in raster order -- the index of
+ *               its record in ssrlcv_hip_stereo_matches' output for the same map and step -- and an invalid node UINT32_MAX
+ *               (until the map is restricted: item 6).  *vertexCount_dev (device) = the number of valid nodes.
+ *   2 joined    nodes p and q are joined iff both are valid and fabsf(d(p) - d(q)) <= maxJump: one IEEE float subtraction and
+ *               a comparison that is false for a NaN ("disparity post-filters" item 1), so a NaN difference is not joined,
+ *               inf - inf among them.  maxJump = +inf is legal.
+ *   3 cells     cell (i, j), 0 <= i < gw - 1, 0 <= j < gh - 1, has the corners a = (i, j), b = (i + 1, j), c = (i, j + 1),
+ *               d = (i + 1, j + 1).  With fewer than three valid corners the cell is empty.  With four valid corners its
+ *               diagonal is b-c iff fabsf(d(b) - d(c)) < fabsf(d(a) - d(d)), otherwise a-d (ties and comparisons with a NaN
+ *               included); with three, the diagonal between valid corners.  Diagonal a-d gives T0 = (a, c, d) and
+ *               T1 = (a, d, b); diagonal b-c gives T0 = (a, c, b) and T1 = (b, c, d).  A triangle is emitted iff its three
+ *               edges are joined.  cells[(gw - 1) (gh - 1)] (uint8, pitch gw - 1): bit 0 = T0 emitted, bit 1 = T1 emitted,
+ *               bit 2 = the diagonal is b-c; the byte is 0 whenever neither triangle is emitted, so its values are 0, 1, 2, 3,
+ *               5, 6, 7.  All four triangles wind the same way: with image x to the right and y down, in a camera frame with
+ *               X right, Y down and Z forward (ssrlcv_hip_stereo_points') (q - p) x (r - p) of a triangle (p, q, r) has
+ *               negative z: the normals face the camera.
+ *   4 triangles ssrlcv_hip_mesh_triangles writes the emitted triangles as three uint32 vertex indices (vertexIndex of p, q, r)
+ *               each, in cell raster order, T0 before T1.  *count_dev (device) = the full count; only the first
+ *               min(count, capacity) triangles are written and nothing behind out[3 capacity) is touched; out may be NULL
+ *               with capacity 0 (the truncation contract of ssrlcv_hip_stereo_matches).
+ *   5 normals   ssrlcv_hip_mesh_normals: points[n] are the vertices' positions, e.g. ssrlcv_hip_stereo_points' of the records.
+ *               For every node with index v < n: s = (+0, +0, +0); visit the cells (i - 1, j - 1), (i, j - 1), (i - 1, j),
+ *               (i, j), in that order, where they exist, and in each T0, then T1 -- the triangle list's order; for every
+ *               emitted triangle (p, q, r) that contains the node and whose three indices are all < n, with P = points,
+ *               u = P[q] - P[p], v = P[r] - P[p]:
+ *                 t = ((u.y v.z) - (u.z v.y), (u.z v.x) - (u.x v.z), (u.x v.y) - (u.y v.x)),   s = s + t
+ *               in float32, nothing contracted.  Then len = sqrtf(((s.x s.x) + (s.y s.y)) + (s.z s.z)) and normals[v] = s / len
+ *               component by component, sqrt and division correctly rounded; if len is 0 or not finite, normals[v] =
+ *               (0, 0, 0), the "no result" value of ssrlcv_hip_point_normals, which a vertex without a triangle gets too.
+ *               Only normals[v] of the nodes with v < n are written: an index >= n contributes nothing and writes nothing, so
+ *               a map that is stale for `points` is never read or written out of bounds.
+ *   6 select    ssrlcv_hip_mesh_select restricts a mesh, in place, to a subset of its vertices: keptIndex[m] holds old vertex
+ *               indices, strictly ascending; old vertex keptIndex[j] becomes j and every other node UINT32_MAX (an index
+ *               >= nVertices in the map included).  An entry >= nVertices is ignored.  A triangle with a removed corner has
+ *               its bit cleared, a byte left without a triangle becomes 0; nothing is re-triangulated.  Two producers of
+ *               keptIndex exist: the `index` output of ssrlcv_hip_neighbor_distance_filter, and the records that survive
+ *               ssrlcv_hip_matches_apply_homography plus ssrlcv_hip_compact_matches: the mesh follows its cloud through both.
+ * Refusals of ssrlcv_hip_disparity_mesh, decided on the host before any launch, the parameters before the buffers:
+ * SSRLCV_ERR_INVALID_ARG for params NULL, step 0, maxJump negative or a NaN (!(maxJump >= 0)), then for w h >= 2^31, then for a
+ * NULL vertexCount_dev; an empty map (w or h 0) then writes count 0, looks at nothing else and is SSRLCV_OK; then
+ * SSRLCV_ERR_INVALID_ARG for a NULL disparity, vertexIndex or workspace, or a NULL cells that has an element (it has none when gw
+ * or gh is below 2); then SSRLCV_ERR_WORKSPACE for a short workspace.  The other calls: SSRLCV_ERR_INVALID_ARG for gw gh >=
+ * 2^31, then for a NULL buffer that has an element to hold (count_dev always; out unless capacity is 0; keptIndex unless m is
+ * 0; the workspace unless the query gives 0), then SSRLCV_ERR_WORKSPACE.  Where there is nothing to do the call is SSRLCV_OK
+ * before any other buffer is looked at: mesh_triangles on a grid without a cell writes count 0 and needs count_dev alone;
+ * mesh_normals with n 0, and mesh_normals and mesh_select on a grid without a node, write nothing.
+ * Workspace (host only; computed in size_t; 0 for refused input), with a256(n) = n rounded up to 256 and
+ * c(N) = a256(4 (4 ceil(N / 4096) + 3)), the tables of one ordered compaction of N elements (csrc/compact.h):
+ *     disparity_mesh   c(gw gh)                       mesh_select   a256(4 nVertices), the old -> new vertex table
+ *     mesh_triangles   c(2 (gw - 1) (gh - 1)), c(0) when gw or gh is below 2
+ * It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.
+ * Out of scope: vertex welding or decimation, closing holes in the mesh, triangle-quality tests in 3-D (a sliver between a
+ * near and a far surface is cut by maxJump alone), texture coordinates, Poisson or any other reconstruction from unorganised
+ * clouds, merging the meshes of several pairs. */
+typedef struct {
+  uint32_t step;  /* >= 1: the sampling step of ssrlcv_hip_stereo_matches */
+  float maxJump;  /* >= 0, +inf allowed: two nodes whose disparities differ by more are not joined */
+} ssrlcv_mesh_params; /* 8 bytes */
+size_t ssrlcv_hip_disparity_mesh_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_mesh_params* params);
+int ssrlcv_hip_disparity_mesh(const float* disparity, uint32_t w, uint32_t h, const ssrlcv_mesh_params* params, uint32_t* vertexIndex,
+                              uint8_t* cells, uint32_t* vertexCount_dev, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_mesh_select_workspace_bytes(uint32_t nVertices);
+int ssrlcv_hip_mesh_select(uint32_t* vertexIndex, uint8_t* cells, uint32_t gw, uint32_t gh, uint32_t nVertices, const uint32_t* keptIndex,
+                           uint32_t m, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_mesh_triangles_workspace_bytes(uint32_t gw, uint32_t gh);
+int ssrlcv_hip_mesh_triangles(const uint32_t* vertexIndex, const uint8_t* cells, uint32_t gw, uint32_t gh, uint32_t* out, uint32_t capacity,
+                              uint32_t* count_dev, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+int ssrlcv_hip_mesh_normals(const ssrlcv_float3* points, uint32_t n, const uint32_t* vertexIndex, const uint8_t* cells, uint32_t gw, uint32_t gh,
+                            float* normals, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

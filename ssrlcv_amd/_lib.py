@@ -69,7 +69,8 @@ def load():
                      "ssrlcv_hip_stereo_matches_workspace_bytes", "ssrlcv_hip_stereo_sgm_workspace_bytes",
                      "ssrlcv_hip_stereo_census_workspace_bytes", "ssrlcv_hip_stereo_sgm_census_workspace_bytes",
                      "ssrlcv_hip_disparity_components_workspace_bytes", "ssrlcv_hip_stereo_filter_speckles_workspace_bytes",
-                     "ssrlcv_hip_stereo_fill_holes_workspace_bytes"):
+                     "ssrlcv_hip_stereo_fill_holes_workspace_bytes", "ssrlcv_hip_disparity_mesh_workspace_bytes",
+                     "ssrlcv_hip_mesh_select_workspace_bytes", "ssrlcv_hip_mesh_triangles_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -118,4 +119,6 @@ EXPORTED = [
     "ssrlcv_hip_disparity_components_workspace_bytes", "ssrlcv_hip_disparity_components",
     "ssrlcv_hip_stereo_filter_speckles_workspace_bytes", "ssrlcv_hip_stereo_filter_speckles", "ssrlcv_hip_stereo_filter_median",
     "ssrlcv_hip_stereo_fill_holes_workspace_bytes", "ssrlcv_hip_stereo_fill_holes",
+    "ssrlcv_hip_disparity_mesh_workspace_bytes", "ssrlcv_hip_disparity_mesh", "ssrlcv_hip_mesh_select_workspace_bytes",
+    "ssrlcv_hip_mesh_select", "ssrlcv_hip_mesh_triangles_workspace_bytes", "ssrlcv_hip_mesh_triangles", "ssrlcv_hip_mesh_normals",
 ]

@@ -806,6 +806,82 @@ def stereo_fill_holes(disp_d, paths, max_gap, min_hits, rule, want_mask=False, w
     return out, mask
 
 
+# ------------------------------------------------------------------ disparity mesh
+class MeshParams(ctypes.Structure):
+    _fields_ = [("step", c_u32), ("maxJump", c_f32)]
+
+
+def mesh_grid(w, h, step):
+    """(gw, gh): the nodes of the `step` grid of a (h, w) map, the grid of stereo_matches"""
+    return ((w - 1) // step + 1 if w else 0), ((h - 1) // step + 1 if h else 0)
+
+
+def _mesh_maps(vertex_index_d, cells_d):
+    """the two maps of a mesh -> (gw, gh): vertex_index int32 (gh, gw) holding the uint32 bits, cells uint8 (gh - 1, gw - 1)"""
+    assert vertex_index_d.dim() == 2 and vertex_index_d.dtype == torch.int32 and vertex_index_d.is_cuda and vertex_index_d.is_contiguous()
+    gh, gw = vertex_index_d.shape
+    assert cells_d.dtype == torch.uint8 and cells_d.is_cuda and cells_d.is_contiguous()
+    assert tuple(cells_d.shape) == (max(gh - 1, 0), max(gw - 1, 0))
+    return gw, gh
+
+
+def disparity_mesh(disp_d, step, max_jump):
+    """The triangle mesh of a disparity map over the `step` grid (ssrlcv_hip_disparity_mesh; include/ssrlcv_hip.h "disparity
+    mesh" items 1-3).  -> (vertex_index int32 (gh, gw) holding the uint32 bits: a valid node's record index in stereo_matches'
+    output, -1 (UINT32_MAX) for an invalid one; cells uint8 (gh - 1, gw - 1); count int32 [1] device tensor: the number of
+    vertices).  Asynchronous on the current stream."""
+    h, w = _disparity_map(disp_d)
+    assert isinstance(step, int) and not isinstance(step, bool) and 0 <= step <= 0xFFFFFFFF  # c_u32 would wrap it
+    p = MeshParams(step, float(max_jump))
+    gw, gh = mesh_grid(w, h, step) if step else (0, 0)
+    ws = dev_bytes(int(LIB.ssrlcv_hip_disparity_mesh_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(p))))
+    vertex_index = torch.empty((gh, gw), dtype=torch.int32, device="cuda")
+    cells = torch.empty((max(gh - 1, 0), max(gw - 1, 0)), dtype=torch.uint8, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_disparity_mesh(ptr(disp_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(vertex_index), ptr(cells), ptr(count), ptr(ws),
+                                        c_sz(ws.numel()), stream_ptr()))
+    return vertex_index, cells, count
+
+
+def mesh_select(vertex_index_d, cells_d, n_vertices, kept_index_d):
+    """Restricts a mesh, IN PLACE, to the vertices kept_index_d names (ssrlcv_hip_mesh_select; item 6): int32 device tensor of old
+    vertex indices, strictly ascending; old vertex kept_index[j] becomes j, every other node -1, and a triangle that loses a
+    corner goes.  -> (vertex_index_d, cells_d).  Asynchronous on the current stream."""
+    gw, gh = _mesh_maps(vertex_index_d, cells_d)
+    assert kept_index_d.dim() == 1 and kept_index_d.dtype == torch.int32 and kept_index_d.is_cuda and kept_index_d.is_contiguous()
+    ws = dev_bytes(int(LIB.ssrlcv_hip_mesh_select_workspace_bytes(c_u32(n_vertices))))
+    check(LIB.ssrlcv_hip_mesh_select(ptr(vertex_index_d), ptr(cells_d), c_u32(gw), c_u32(gh), c_u32(n_vertices), ptr(kept_index_d),
+                                     c_u32(kept_index_d.numel()), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return vertex_index_d, cells_d
+
+
+def mesh_triangles(vertex_index_d, cells_d, capacity=None):
+    """The emitted triangles of a mesh as vertex index triples, in cell raster order, T0 before T1 (ssrlcv_hip_mesh_triangles;
+    item 4).  -> (faces int32 (min(count, capacity), 3), count).  capacity defaults to two triangles a cell.  One
+    synchronisation (the count)."""
+    gw, gh = _mesh_maps(vertex_index_d, cells_d)
+    cap = 2 * cells_d.numel() if capacity is None else int(capacity)
+    ws = dev_bytes(int(LIB.ssrlcv_hip_mesh_triangles_workspace_bytes(c_u32(gw), c_u32(gh))))
+    out = torch.empty((cap, 3), dtype=torch.int32, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_mesh_triangles(ptr(vertex_index_d), ptr(cells_d), c_u32(gw), c_u32(gh), ptr(out) if cap else c_vp(0), c_u32(cap),
+                                        ptr(count), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    n = int(count.item())
+    return out[: min(n, cap)], n
+
+
+def mesh_normals(points_d, vertex_index_d, cells_d, out=None):
+    """Unit normals of a mesh's vertices from the triangles around them, facing the camera (ssrlcv_hip_mesh_normals; item 5).
+    points_d: (n, 3) float32 device tensor.  -> float32 (n, 3): zeros first, then the vertices of the map with an index below n;
+    into `out` (which is not cleared) when given.  Asynchronous on the current stream."""
+    gw, gh = _mesh_maps(vertex_index_d, cells_d)
+    p, n = _cloud(points_d)
+    nrm = torch.zeros((n, 3), dtype=torch.float32, device="cuda") if out is None else out
+    assert nrm.dtype == torch.float32 and nrm.is_cuda and nrm.is_contiguous() and nrm.numel() >= 3 * n
+    check(LIB.ssrlcv_hip_mesh_normals(ptr(p), c_u32(n), ptr(vertex_index_d), ptr(cells_d), c_u32(gw), c_u32(gh), ptr(nrm), stream_ptr()))
+    return nrm
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

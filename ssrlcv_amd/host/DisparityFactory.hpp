@@ -35,8 +35,15 @@
 //   factory.filterSpeckles(disparity, nullptr, 200, 1.0f);             // in place: components of at most 200 pixels become invalid
 //   disparity = factory.fillHoles(disparity, 0xFF, 32, 5, 0);          // a new map: holes take the smallest of >= 5 measured neighbours
 //
+// The surface of the final map (include/ssrlcv_hip.h "disparity mesh"), with the vertex numbering of generateMatches' records at
+// the same step, goes to a MeshFactory beside the cloud of those records:
+//
+//   GridMesh surface = factory.generateMesh(disparity, 1, 1.0f);       // triangles over the step-1 grid, cut at jumps above 1
+//   meshFactory.setPoints(cloud); meshFactory.setSurface(surface); meshFactory.computeSurfaceNormals();
+//
 // Pixels keep upstream's memory-state contract: forced onto the gpu for the call, restored to their origin state after it.
 #pragma once
+#include "GridMesh.hpp"
 #include "Image.hpp"
 #include "MatchFactory.hpp"
 
@@ -317,6 +324,35 @@ class DisparityFactory {
     HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
     if (origin != gpu) disparity->setMemoryState(origin);
     return out;
+  }
+
+  // the triangle mesh of a map over the grid of meshStep, generateMatches' setStep (include/ssrlcv_hip.h "disparity mesh" items 1-3; the map has the size
+  // of the last pair matched, or what setMapSize said): both maps in state gpu, the vertices numbered as generateMatches
+  // numbers its records for the same map; two nodes whose disparities differ by more than maxJump are not joined
+  GridMesh generateMesh(ptr::value<Unity<float>> disparity, unsigned int meshStep, float maxJump) {
+    const uint32_t w = mapSize.x, h = mapSize.y;
+    const ssrlcv_mesh_params params = {meshStep, maxJump};
+    if ((unsigned long)w * h != disparity->size()) {
+      logger.err << "ERROR: the mesh takes a map of the size of the last pair matched (setMapSize for any other)";
+      std::exit(-1);
+    }
+    const size_t wsBytes = ssrlcv_hip_disparity_mesh_workspace_bytes(w, h, &params);  // 0 for refused parameters: the call says so
+    MemoryState origin = disparity->getMemoryState();
+    if (origin != gpu) disparity->setMemoryState(gpu);
+    GridMesh mesh;
+    mesh.gw = meshStep && w ? (w - 1) / meshStep + 1 : 0;
+    mesh.gh = meshStep && h ? (h - 1) / meshStep + 1 : 0;
+    const unsigned long nodes = (unsigned long)mesh.gw * mesh.gh;
+    mesh.vertexIndex = ptr::value<Unity<unsigned int>>(nullptr, nodes ? nodes : 1ul, gpu);
+    mesh.cells = ptr::value<Unity<unsigned char>>(nullptr, mesh.numCells() ? mesh.numCells() : 1ul, gpu);
+    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+    ptr::device<uint32_t> countDev(1);
+    HipSafeCall(ssrlcv_hip_disparity_mesh(disparity->device.get(), w, h, &params, mesh.vertexIndex->device.get(), mesh.cells->device.get(),
+                                          countDev.get(), workspace.get(), wsBytes, nullptr));
+    HipCheckError();
+    HipSafeCall(ssrlcv_hip_memcpy(&mesh.vertexCount, countDev.get(), sizeof mesh.vertexCount, 1));  // synchronises: the workspace may go
+    if (origin != gpu) disparity->setMemoryState(origin);
+    return mesh;
   }
 
   // in place: generateMatches' records of a rectified pair, through Hl and Hr into source pixels; a record that does not

@@ -12,6 +12,7 @@ struct float3 { float x, y, z; };
 struct alignas(16) float4 { float x, y, z, w; };
 struct alignas(8) uint2 { unsigned int x, y; };
 struct alignas(8) int2 { int x, y; };
+struct uint3 { unsigned int x, y, z; };
 
 // the operators the hot path uses (src/cuda_vec_util.cu:136-138,559-563,1228-1250,1585-1605)
 inline bool operator==(const uint2& a, const uint2& b) { return a.x == b.x && a.y == b.y; }

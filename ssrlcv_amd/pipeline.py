@@ -258,6 +258,12 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None,
     matches are in source pixels with parent ids 0 (cam_l) and 1 (cam_r); the disparity map is the rectified left view's."""
     if "want_cost" in disparity_args:
         raise TypeError("stereo_cloud_cameras computes no cost map: call stereo_disparity for one")
+    return _cloud_cameras(left, right, cam_l, cam_r, step, sgm, post, disparity_args)
+
+
+def _cloud_cameras(left, right, cam_l, cam_r, step, sgm, post, disparity_args, on_records=None):
+    """stereo_cloud_cameras' chain.  on_records(disp, matches, n): stereo_mesh_cameras' look at the records mapped back into
+    source pixels, before the ones that did not map are compacted away"""
     left_r, right_r, rect = rectify_pair(left, right, cam_l, cam_r)
     disp = _dense_disparity(left_r, right_r, sgm, disparity_args)
     footprint = disparity_args.get("radius", 4 if sgm is None else 2) + disparity_args.get("census", 0)
@@ -267,6 +273,8 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None,
         capi.stereo_mask_rectified(disp, None, footprint, rect)   # the fill extrapolates past the mask's edge: the mask only removes, never adds
     matches, n = capi.stereo_matches(disp, step, 0, 1)
     capi.matches_apply_homography(matches, n, rect["Hl"], rect["Hr"])
+    if on_records is not None:
+        on_records(disp, matches, n)
     if n:
         n = capi.compact_matches(capi.OUT_MATCH, matches, n, capi.match_workspace(n, 1))   # a record that did not map back
         matches = matches[: 40 * n]
@@ -279,6 +287,71 @@ def stereo_cloud_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None,
         b_d, l_d = capi.generate_bundles(mm_d, kp_d, n, capi.to_dev(cameras), 2, 2 * n)
         pts = capi.triangulate(l_d, b_d, n, nview=False)[0].view(-1, 3)
     return pts, matches, n, disp, rect
+
+
+def disparity_mesh(disp, step=1, max_jump=None):
+    """The triangle mesh of a disparity map (float32 CUDA tensor (H, W); include/ssrlcv_hip.h "disparity mesh"): the nodes are
+    the pixels of the `step` grid, the vertices its valid nodes in stereo_matches' order, and every grid cell gives up to two
+    triangles, cut wherever two corners' disparities differ by more than max_jump (None: float(step), one disparity a pixel).
+    -> dict(vertex_index int32 (gh, gw), -1 where there is no vertex; cells uint8 (gh - 1, gw - 1): bit 0 / 1 = the cell's first /
+    second triangle exists, bit 2 = its diagonal runs b-c; n_vertices).  One synchronisation (the count)."""
+    vertex_index, cells, count = capi.disparity_mesh(disp, step, float(step) if max_jump is None else max_jump)
+    return {"vertex_index": vertex_index, "cells": cells, "n_vertices": int(count.item())}
+
+
+def mesh_select(mesh, kept_index):
+    """A mesh restricted to the vertices kept_index names (old vertex indices, strictly ascending: an integer device tensor,
+    e.g. filter_cloud's `index`): vertex kept_index[j] becomes j, a triangle that loses a corner goes, nothing is
+    re-triangulated.  -> a new mesh dict; `mesh` is left as it is."""
+    vertex_index, cells = mesh["vertex_index"].clone(), mesh["cells"].clone()
+    kept = kept_index.to(torch.int32).contiguous()
+    capi.mesh_select(vertex_index, cells, mesh["n_vertices"], kept)
+    return {"vertex_index": vertex_index, "cells": cells, "n_vertices": int(kept.numel())}
+
+
+def mesh_faces(mesh):
+    """The triangles of a mesh -> int32 (T, 3) device tensor of vertex indices, in cell raster order; every face winds so that
+    its normal (q - p) x (r - p) faces the camera."""
+    return capi.mesh_triangles(mesh["vertex_index"], mesh["cells"])[0]
+
+
+def mesh_normals(mesh, points):
+    """Unit normals of the vertices of a mesh at the positions `points` ((n, 3) float32 device tensor, row v = vertex v): the
+    normalised sum of the cross products of the triangles around each vertex, facing the camera; (0, 0, 0) for a vertex without
+    a triangle.  -> (n, 3) float32 device tensor.  Stream-ordered."""
+    return capi.mesh_normals(points, mesh["vertex_index"], mesh["cells"])
+
+
+def stereo_mesh(left, right, foc, baseline, doffset=0.0, cx=None, cy=None, step=1, left_id=0, right_id=1, sgm=None, post=None,
+                max_jump=None, **disparity_args):
+    """stereo_cloud with the surface: the same arguments (and the same points, matches, n and disparity), then disparity_mesh of
+    the map at the same step with max_jump, its faces and the normals of the cloud's points.  Normals face the camera where
+    every d + doffset is above 0 (min_disparity + doffset > 0).  -> dict(points, faces int32 (T, 3), normals, matches, n,
+    disparity, mesh)."""
+    pts, matches, n, disp = stereo_cloud(left, right, foc, baseline, doffset, cx, cy, step, left_id, right_id, sgm, post, **disparity_args)
+    mesh = disparity_mesh(disp, step, max_jump)
+    return {"points": pts, "faces": mesh_faces(mesh), "normals": mesh_normals(mesh, pts), "matches": matches, "n": n, "disparity": disp,
+            "mesh": mesh}
+
+
+def stereo_mesh_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None, max_jump=None, **disparity_args):
+    """stereo_cloud_cameras with the surface: the same arguments (and the same points, matches, n, disparity and rect).  The mesh
+    is taken from the disparity map the records come from, restricted to the records that map back into the sources (their
+    `invalid` byte, before the compaction), and only then come the faces and the normals over the world-frame points.
+    -> dict(points, faces, normals, matches, n, disparity, mesh, rect)."""
+    if "want_cost" in disparity_args:
+        raise TypeError("stereo_mesh_cameras computes no cost map: call stereo_disparity for one")
+    found = {}
+
+    def on_records(disp, matches, n):
+        mesh = disparity_mesh(disp, step, max_jump)
+        kept = torch.nonzero(matches[: 40 * n].view(-1, 40)[:, 0] == 0).view(-1)   # ascending
+        found["mesh"] = mesh_select(mesh, kept)
+
+    pts, matches, n, disp, rect = _cloud_cameras(left, right, cam_l, cam_r, step, sgm, post, disparity_args, on_records)
+    mesh = found["mesh"]
+    return {"points": pts, "faces": mesh_faces(mesh), "normals": mesh_normals(mesh, pts), "matches": matches, "n": n, "disparity": disp,
+            "mesh": mesh, "rect": rect}
 
 
 def exchange_features(local, num_images):
