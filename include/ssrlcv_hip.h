@@ -1044,6 +1044,90 @@ int ssrlcv_hip_mesh_triangles(const uint32_t* vertexIndex, const uint8_t* cells,
                               uint32_t* count_dev, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 int ssrlcv_hip_mesh_normals(const ssrlcv_float3* points, uint32_t n, const uint32_t* vertexIndex, const uint8_t* cells, uint32_t gw, uint32_t gh,
                             float* normals, ssrlcv_stream_t stream);
+/* The meshes of several pairs are merged through the next section: their clouds into one height map, and that map's mesh. */
+
+/* ---- surface model: a height map on a ground grid, fused over every pair that sees a cell.  The map has the form of a
+ * disparity map -- float[w h], pitch w, invalid = 0x7FC00000 -- so ssrlcv_hip_stereo_filter_median, _filter_speckles,
+ * _fill_holes and ssrlcv_hip_disparity_mesh take it unchanged: merging the meshes of several pairs is rasterising each pair's
+ * world-frame cloud into the same grid, fusing per cell, and meshing the result.  Everything is a selection or a fixed-order
+ * float32 expression, nothing contracted, the one division IEEE: the kernels of csrc/dsm.hip are held to a numpy restatement
+ * bit for bit (tests/dsm_ref.py, tests/test_gpu_dsm.py).
+ *   frame       ssrlcv_dsm_frame: cell (i, j) of the w x h grid covers origin + a ex + b ey, i cell <= a < (i + 1) cell,
+ *               j cell <= b < (j + 1) cell; ez is the direction heights are measured along.  It is an affine map and is NOT
+ *               checked for orthonormality.  Refused: a non-finite entry of origin, ex, ey or ez; a cell that is not finite or
+ *               not above 0.
+ *   validity    as everywhere in this file: a cell is valid iff its height's bit pattern is not 0x7FC00000.
+ *   key         k(f) = b >= 0 ? b : b ^ 0x7FFFFFFF of the bits b as an int32, the key of the median filter ("disparity
+ *               post-filters" item 4): a total order in which -0 lies below +0.
+ *   1 rasterize ssrlcv_hip_dsm_rasterize.  A point is skipped if any component is not finite, or if it is (0, 0, 0) with
+ *               either sign of zero, this file's "no result" point.  Otherwise, for point p of index t, in float32 in exactly
+ *               this order:
+ *                 q = p - origin  (component by component)
+ *                 a = ((q.x ex.x) + (q.y ex.y)) + (q.z ex.z),   b the same with ey,   z the same with ez
+ *                 u = a / cell,  v = b / cell,  fi = floorf(u),  fj = floorf(v)
+ *               The point lies in cell (i, j) = (fi, fj) iff fi >= 0 && fi < (float)w && fj >= 0 && fj < (float)h, compared
+ *               on floats before any conversion: a NaN and a huge value are outside, -0 is inside cell 0, u == w is outside.
+ *               A point whose z is not finite is skipped.  rule 0 = MAX (the top surface), 1 = MIN:
+ *                 height(i, j) = the z of greatest (least) key among the cell's points
+ *                 source(i, j) = that point's index; among points of equal key the smallest index
+ *                 count(i, j)  = the number of points in the cell
+ *               An empty cell holds 0x7FC00000, UINT32_MAX and 0.  Every entry of every given map is written and nothing
+ *               behind it; source and count may be NULL.
+ *   2 fuse      ssrlcv_hip_dsm_fuse: `maps` is a HOST array of m device pointers, 1 <= m <= 8, each a w x h map.  Per cell:
+ *               the valid entries among the m maps, n of them, ordered by key.  If n < minViews the cell is invalid.  If
+ *               !(hi - lo <= maxSpread) -- one float subtraction of the largest and the smallest entry; maxSpread = +inf is
+ *               legal, a NaN difference (inf - inf) fails -- the cell is invalid.  Otherwise out takes rank 0 (rule 0, MIN),
+ *               rank (n - 1) / 2 (rule 1, the lower MEDIAN) or rank n - 1 (rule 2, MAX): always one of the inputs.  views
+ *               (uint8, may be NULL) holds n, whether or not the cell survives.  The same map may be passed twice.
+ *   3 points    ssrlcv_hip_dsm_points writes the valid cells in raster order -- the numbering ssrlcv_hip_disparity_mesh gives
+ *               the same map at step 1 (its item 1) -- each as, in float32, z its height:
+ *                 a = ((float)i + 0.5f) cell,   b = ((float)j + 0.5f) cell
+ *                 P = ((origin + a ex) + b ey) + z ez      (component by component, in that order)
+ *               *count_dev (device) = the full count; only the first min(count, capacity) points are written and nothing
+ *               behind out[capacity) is touched; out may be NULL with capacity 0 (the truncation contract of
+ *               ssrlcv_hip_stereo_matches).
+ *   winding     with (ex, ey, -ez) right-handed -- x east, y south, height up: the image convention with the camera above --
+ *               the faces of ssrlcv_hip_disparity_mesh on the height map wind so that ssrlcv_hip_mesh_normals' normals of
+ *               these points face +ez.
+ * Refusals, decided on the host before any launch, the parameters before the sizes before the buffers:
+ *   rasterize   SSRLCV_ERR_INVALID_ARG for a NULL or refused frame, rule > 1, w h >= 2^31, n = UINT32_MAX; then
+ *               SSRLCV_ERR_UNSUPPORTED for w or h above 2^24, where (float)w stops being exact; an empty grid (w or h 0) is
+ *               then SSRLCV_OK and nothing is looked at; then SSRLCV_ERR_INVALID_ARG for a NULL height or workspace, or a NULL
+ *               points unless n is 0 (the maps are then all empty cells); then SSRLCV_ERR_WORKSPACE.
+ *   fuse        SSRLCV_ERR_INVALID_ARG for m 0 or above 8, minViews 0 or above m, maxSpread negative or a NaN
+ *               (!(maxSpread >= 0)), rule > 2, then w h >= 2^31; an empty map is then SSRLCV_OK; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL maps, maps[i] or out, or out equal to any input.
+ *   points      SSRLCV_ERR_INVALID_ARG for a NULL or refused frame or w h >= 2^31; SSRLCV_ERR_UNSUPPORTED for w or h above
+ *               2^24; SSRLCV_ERR_INVALID_ARG for a NULL count_dev; an empty grid then writes count 0 and is SSRLCV_OK; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL height or workspace, or a NULL out unless capacity is 0; then
+ *               SSRLCV_ERR_WORKSPACE.
+ * Workspace (host only; computed in size_t; 0 for a refused size), a256 and c as in "disparity mesh":
+ *     dsm_rasterize   a256(8 w h), one 64-bit accumulator per cell        dsm_points   c(w h)        dsm_fuse   none
+ * It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  dsm_rasterize uses global INTEGER
+ * atomics only -- a 64-bit max on (key << 32) | (0xFFFFFFFF - index), the key complemented for MIN, and a 32-bit add for the
+ * count, at most one of each per point: adjacent lanes of a wave that fall into one cell share theirs -- which commute: the maps
+ * do not depend on the order the points arrive in and are bit-equal run to run.
+ * dsm_fuse and dsm_points use no atomics.
+ * Out of scope: a mean or any float accumulation per cell; ortho-image colours (the source map reduces them to a gather); a
+ * ground frame fitted to the cloud; pushbroom pairs; more than 8 maps. */
+typedef struct {
+  float origin[3];  /* the world position of the corner of cell (0, 0) */
+  float ex[3];      /* the direction of growing i */
+  float ey[3];      /* the direction of growing j */
+  float ez[3];      /* the direction heights are measured along */
+  float cell;       /* > 0 and finite: the side of a cell */
+  uint32_t w, h;    /* the grid */
+} ssrlcv_dsm_frame; /* 60 bytes */
+size_t ssrlcv_hip_dsm_rasterize_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_rasterize(const ssrlcv_float3* points, uint32_t n, const ssrlcv_dsm_frame* frame, uint32_t rule, float* height,
+                             uint32_t* source /* may be NULL */, uint32_t* count /* may be NULL */, void* workspace, size_t workspaceBytes,
+                             ssrlcv_stream_t stream);
+int ssrlcv_hip_dsm_fuse(const float* const* maps, uint32_t m, uint32_t w, uint32_t h, uint32_t minViews, float maxSpread, uint32_t rule,
+                        float* out, uint8_t* views /* may be NULL */, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_dsm_points_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_points(const float* height, const ssrlcv_dsm_frame* frame, ssrlcv_float3* out, uint32_t capacity, uint32_t* count_dev,
+                          void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -882,6 +882,75 @@ def mesh_normals(points_d, vertex_index_d, cells_d, out=None):
     return nrm
 
 
+# ------------------------------------------------------------------ surface model
+class DsmFrame(ctypes.Structure):
+    """ssrlcv_dsm_frame: cell (i, j) covers origin + a ex + b ey, i cell <= a < (i + 1) cell, j cell <= b < (j + 1) cell; heights
+    are measured along ez"""
+    _fields_ = [("origin", c_f32 * 3), ("ex", c_f32 * 3), ("ey", c_f32 * 3), ("ez", c_f32 * 3), ("cell", c_f32), ("w", c_u32), ("h", c_u32)]
+
+    @classmethod
+    def make(cls, origin, ex, ey, ez, cell, w, h):
+        vec = lambda v: (c_f32 * 3)(*[float(x) for x in np.asarray(v, np.float32).reshape(3)])  # noqa: E731
+        return cls(vec(origin), vec(ex), vec(ey), vec(ez), float(np.float32(cell)), int(w), int(h))
+
+
+assert ctypes.sizeof(DsmFrame) == 60
+
+DSM_MAX, DSM_MIN = 0, 1                          # dsm_rasterize's rule
+DSM_FUSE_MIN, DSM_FUSE_MEDIAN, DSM_FUSE_MAX = 0, 1, 2   # dsm_fuse's rule
+
+
+def dsm_rasterize(points_d, frame, rule=DSM_MAX, want_source=True, want_count=True, workspace=None):
+    """A cloud into the height map of `frame` (ssrlcv_hip_dsm_rasterize; include/ssrlcv_hip.h "surface model" item 1): per cell
+    the greatest (rule DSM_MAX) or least (DSM_MIN) height of its points.  points_d: (n, 3) float32 device tensor.
+    -> (height float32 (h, w), 0x7FC00000 for an empty cell; source int32 (h, w) holding the uint32 bits: the winner's index, -1
+    for an empty cell; count int32 (h, w)); source and count are None unless asked for.  The workspace is reused if it is large
+    enough.  Asynchronous on the current stream."""
+    p, n = _cloud(points_d)
+    w, h = int(frame.w), int(frame.h)
+    ws = _filter_workspace(LIB.ssrlcv_hip_dsm_rasterize_workspace_bytes, w, h, workspace)
+    height = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    source = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_source else None
+    count = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_count else None
+    check(LIB.ssrlcv_hip_dsm_rasterize(ptr(p) if n else c_vp(0), c_u32(n), ctypes.byref(frame), c_u32(rule), ptr(height), ptr(source), ptr(count),
+                                       ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return height, source, count
+
+
+def dsm_fuse(maps, min_views=1, max_spread=float("inf"), rule=DSM_FUSE_MEDIAN, want_views=True):
+    """Up to 8 height maps of one grid fused per cell (ssrlcv_hip_dsm_fuse; item 2): a cell with at least min_views valid entries
+    whose largest and smallest differ by at most max_spread takes the smallest (DSM_FUSE_MIN), the lower median
+    (DSM_FUSE_MEDIAN) or the largest (DSM_FUSE_MAX) of them.  -> (a new float32 (h, w) tensor, views uint8 (h, w) or None: the
+    number of valid entries).  Asynchronous on the current stream."""
+    maps = list(maps)
+    assert maps, "at least one map"
+    h, w = _disparity_map(maps[0])
+    for m in maps:
+        assert _disparity_map(m) == (h, w), "the maps share one grid"
+    out = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    views = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_views else None
+    arr = (c_vp * len(maps))(*[m.data_ptr() for m in maps])
+    check(LIB.ssrlcv_hip_dsm_fuse(arr, c_u32(len(maps)), c_u32(w), c_u32(h), c_u32(min_views), c_f32(max_spread), c_u32(rule), ptr(out), ptr(views),
+                                  stream_ptr()))
+    return out, views
+
+
+def dsm_points(height_d, frame, capacity=None):
+    """The valid cells of a height map as world-frame points, in raster order: the vertex numbering disparity_mesh gives the same
+    map at step 1 (ssrlcv_hip_dsm_points; item 3).  -> (points float32 (min(count, capacity), 3), count).  capacity defaults to
+    the grid's size.  One synchronisation (the count)."""
+    h, w = _disparity_map(height_d)
+    assert (h, w) == (int(frame.h), int(frame.w)), "the map has the frame's grid"
+    cap = w * h if capacity is None else int(capacity)
+    ws = dev_bytes(int(LIB.ssrlcv_hip_dsm_points_workspace_bytes(c_u32(w), c_u32(h))))
+    out = torch.empty((cap, 3), dtype=torch.float32, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_dsm_points(ptr(height_d), ctypes.byref(frame), ptr(out) if cap else c_vp(0), c_u32(cap), ptr(count), ptr(ws),
+                                    c_sz(ws.numel()), stream_ptr()))
+    n = int(count.item())
+    return out[: min(n, cap)], n
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

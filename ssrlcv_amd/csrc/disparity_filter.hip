@@ -38,6 +38,7 @@
 #include "ssrlcv_hip.h"
 #include "align256.h"
 #include "device_math.h"
+#include "order_key.h"
 
 namespace {
 
@@ -236,39 +237,7 @@ __global__ __launch_bounds__(256) void k_speckle_apply(float* __restrict__ dispa
   }
 }
 
-// ---- median
-__device__ __forceinline__ int32_t order_key(uint32_t bits) {  // the float order as an integer order, total, -0 below +0
-  const int32_t b = (int32_t)bits;
-  return b >= 0 ? b : b ^ 0x7FFFFFFF;  // its own inverse
-}
-
-__device__ __forceinline__ void compare_exchange(int32_t& a, int32_t& b) {
-  const int32_t lo = min(a, b), hi = max(a, b);
-  a = lo;
-  b = hi;
-}
-
-// Batcher's odd-even merge sort of N = 2^k registers: every index is a compile-time constant once the loops are unrolled, and
-// the exchanges with the constant INT32_MAX entries behind the window's (2M + 1)^2 fold away
-template <int N>
-__device__ __forceinline__ void sort_network(int32_t (&a)[N]) {
-#pragma unroll
-  for (int lp = 0; (1 << lp) < N; ++lp) {
-    const int p = 1 << lp;
-#pragma unroll
-    for (int lk = lp; lk >= 0; --lk) {
-      const int k = 1 << lk;
-#pragma unroll
-      for (int j = k % p; j <= N - 1 - k; j += 2 * k) {
-#pragma unroll
-        for (int i = 0; i < k; ++i) {
-          if (i + j + k < N && (i + j) / (2 * p) == (i + j + k) / (2 * p)) compare_exchange(a[i + j], a[i + j + k]);
-        }
-      }
-    }
-  }
-}
-
+// ---- median (order_key and sort_network: csrc/order_key.h)
 template <int M>
 __global__ __launch_bounds__(256) void k_median(const float* __restrict__ in, float* __restrict__ out, uint32_t w, uint32_t h, uint32_t tilesX) {
   constexpr int kHaloW = kTileW + 2 * M, kHaloH = kTileH + 2 * M, kWindow = (2 * M + 1) * (2 * M + 1);

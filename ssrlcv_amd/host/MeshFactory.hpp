@@ -12,6 +12,7 @@
 #pragma once
 #include <cstdio>
 #include <string>
+#include <vector>
 #include "GridMesh.hpp"
 #include "Unity.hpp"
 #include "cuda_vec_types.hpp"
@@ -215,6 +216,91 @@ class MeshFactory {
       points->setMemoryState(cpu);
       normals->setMemoryState(cpu);
     }
+  }
+
+  // ---- the surface model (include/ssrlcv_hip.h "surface model"): the clouds of several pairs become one surface through a
+  // height map on a ground grid.  generateHeightMap per cloud, fuseHeightMaps over them (DisparityFactory's medianFilter,
+  // filterSpeckles and fillHoles take the result as it is: a height map has a disparity map's form), then
+  // setPointsFromHeightMap(height, frame) and setSurface(DisparityFactory::generateMesh(height, 1, maxJump)) with the factory's
+  // map size set to the grid; saveMesh then writes the fused surface.
+
+  // the height map of the points this factory holds: per cell of `frame` the greatest (rule 0) or least (rule 1) height; in
+  // state gpu, frame.w x frame.h, 0x7FC00000 in an empty cell; null for an empty grid or a refused frame
+  ptr::value<Unity<float>> generateHeightMap(const ssrlcv_dsm_frame& frame, unsigned int rule) {
+    const unsigned long cells = (unsigned long)frame.w * frame.h;
+    if (points == nullptr || cells == 0) {
+      logger.err << "MeshFactory::generateHeightMap: needs points and a grid with a cell";
+      return ptr::value<Unity<float>>();
+    }
+    MemoryState origin = points->getMemoryState();
+    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
+    const size_t wsb = ssrlcv_hip_dsm_rasterize_workspace_bytes(frame.w, frame.h);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::value<Unity<float>> height(nullptr, cells, gpu);
+    HipSafeCall(ssrlcv_hip_dsm_rasterize((const ssrlcv_float3*)points->device.get(), (uint32_t)points->size(), &frame, rule, height->device.get(),
+                                         nullptr, nullptr, ws.get(), wsb, nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    if (origin == cpu) points->setMemoryState(cpu);
+    return height;
+  }
+
+  // 1 to 8 height maps of one w x h grid fused per cell: at least minViews valid entries whose largest and smallest differ by
+  // at most maxSpread give their smallest (rule 0), lower median (1) or largest (2); in state gpu.  *views, when asked for,
+  // holds the number of valid entries of every cell.  The maps are left in the state they came in.
+  static ptr::value<Unity<float>> fuseHeightMaps(const std::vector<ptr::value<Unity<float>>>& maps, unsigned int w, unsigned int h,
+                                                 unsigned int minViews, float maxSpread, unsigned int rule,
+                                                 ptr::value<Unity<unsigned char>>* views = nullptr) {
+    const unsigned long cells = (unsigned long)w * h;
+    if (maps.empty() || maps.size() > 8 || cells == 0) {
+      logger.err << "MeshFactory::fuseHeightMaps: needs 1 to 8 maps of a grid with a cell";
+      return ptr::value<Unity<float>>();
+    }
+    std::vector<MemoryState> origin;
+    std::vector<const float*> dev;
+    for (auto& m : maps) {
+      if (m == nullptr || m->size() != cells) {
+        logger.err << "MeshFactory::fuseHeightMaps: every map has w h entries";
+        return ptr::value<Unity<float>>();
+      }
+      origin.push_back(m->getMemoryState());
+      if (origin.back() != gpu) m->setMemoryState(gpu);
+      dev.push_back(m->device.get());
+    }
+    ptr::value<Unity<float>> out(nullptr, cells, gpu);
+    if (views) *views = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
+    HipSafeCall(ssrlcv_hip_dsm_fuse(dev.data(), (uint32_t)maps.size(), w, h, minViews, maxSpread, rule, out->device.get(),
+                                    views ? (*views)->device.get() : nullptr, nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    for (size_t k = 0; k < maps.size(); ++k)
+      if (origin[k] != gpu) maps[k]->setMemoryState(origin[k]);
+    return out;
+  }
+
+  // the valid cells of a height map become this factory's points, in raster order: the vertex numbering of
+  // DisparityFactory::generateMesh(height, 1, maxJump), so that mesh is the surface of these points
+  void setPointsFromHeightMap(ptr::value<Unity<float>> height, const ssrlcv_dsm_frame& frame) {
+    const unsigned long cells = (unsigned long)frame.w * frame.h;
+    if (height == nullptr || cells == 0 || height->size() != cells) {
+      logger.err << "MeshFactory::setPointsFromHeightMap: the map has frame.w frame.h entries";
+      return;
+    }
+    MemoryState origin = height->getMemoryState();
+    if (origin != gpu) height->setMemoryState(gpu);
+    const size_t wsb = ssrlcv_hip_dsm_points_workspace_bytes(frame.w, frame.h);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::device<uint32_t> count(1);
+    HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, nullptr, 0, count.get(), ws.get(), wsb, nullptr));
+    uint32_t n = 0;
+    HipSafeCall(ssrlcv_hip_memcpy(&n, count.get(), sizeof n, 1));
+    if (n == 0) {
+      setPoints(ptr::value<Unity<float3>>());
+    } else {
+      ptr::value<Unity<float3>> pts(nullptr, (unsigned long)n, gpu);
+      HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, (ssrlcv_float3*)pts->device.get(), n, count.get(), ws.get(), wsb, nullptr));
+      HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+      setPoints(pts);
+    }
+    if (origin != gpu) height->setMemoryState(origin);
   }
 
   // ASCII PLY of the points (and their normals once computed) as <dir><filename>.ply

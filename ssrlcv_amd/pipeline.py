@@ -354,6 +354,77 @@ def stereo_mesh_cameras(left, right, cam_l, cam_r, step=1, sgm=None, post=None, 
             "mesh": mesh, "rect": rect}
 
 
+_DSM_RULES = {"max": capi.DSM_MAX, "min": capi.DSM_MIN}
+_DSM_FUSE_RULES = {"min": capi.DSM_FUSE_MIN, "median": capi.DSM_FUSE_MEDIAN, "max": capi.DSM_FUSE_MAX}
+
+
+def dsm_frame(points, up, cell, margin=0, ex=None):
+    """The ground grid of a cloud ((n, 3) float32 device tensor; include/ssrlcv_hip.h "surface model" frame): ez = `up`
+    normalised, ex perpendicular to it (the given `ex` made so, or the world axis furthest from `up`), ey such that
+    (ex, ey, -up) is right-handed -- x east, y south, height up -- and origin, w and h from the bounding box of the cloud's
+    usable points (finite, not (0, 0, 0)) in that frame, `margin` world units wider on every side.  The origin has no component
+    along ez, so a height is the point's own coordinate along `up`.  Host arithmetic on two torch reductions.
+    -> capi.DsmFrame."""
+    up = np.asarray(up, np.float64).reshape(3)
+    up = up / np.linalg.norm(up)
+    axis = np.eye(3)[int(np.argmin(np.abs(up)))] if ex is None else np.asarray(ex, np.float64).reshape(3)
+    ex = axis - np.dot(axis, up) * up
+    if not np.linalg.norm(ex) > 0:
+        raise ValueError("ex is parallel to up")
+    ex = ex / np.linalg.norm(ex)
+    ey = np.cross(-up, ex)
+    if not (np.isfinite(cell) and cell > 0 and np.isfinite(margin) and margin >= 0):
+        raise ValueError("cell is positive and margin is not negative")
+    p = points.view(-1, 3).to(torch.float64)
+    p = p[torch.isfinite(p).all(1) & (p != 0).any(1)]
+    if p.shape[0] == 0:
+        return capi.DsmFrame.make((0, 0, 0), ex, ey, up, cell, 0, 0)
+    ab = p @ torch.tensor(np.stack([ex, ey], 1), dtype=torch.float64, device=p.device)
+    lo, hi = ab.min(0).values.cpu().numpy() - margin, ab.max(0).values.cpu().numpy() + margin
+    w, h = (int(np.floor((hi[k] - lo[k]) / cell)) + 1 for k in range(2))
+    return capi.DsmFrame.make(lo[0] * ex + lo[1] * ey, ex, ey, up, cell, w, h)
+
+
+def surface_model(clouds, frame, rule="max", fuse=None, post=None):
+    """The surface model of several pairs' world-frame clouds (each (n, 3) float32 device tensor, e.g. stereo_cloud_cameras'
+    points) on the grid of `frame` (include/ssrlcv_hip.h "surface model"): every cloud is rasterised into its own height map
+    (rule "max": the top surface, or "min"), the maps are fused per cell -- fuse = dict(min_views=1, max_spread=inf,
+    rule="median"): a cell seen by at least min_views clouds whose heights agree within max_spread takes their "min", lower
+    "median" or "max" -- and post (stereo_cloud's dictionary: median, speckle_size, speckle_diff, fill) then runs on the fused
+    map unchanged, a height map being a disparity map in form.  -> dict(height float32 (h, w), 0x7FC00000 where there is none;
+    fused: the map before post; views uint8 (h, w): the clouds that saw the cell; maps, sources, counts: one (h, w) tensor a
+    cloud, sources holding the index of the winning point, -1 in an empty cell)."""
+    if rule not in _DSM_RULES:
+        raise ValueError("rule is 'max' or 'min', not %r" % (rule,))
+    fuse = dict(fuse or {})
+    if set(fuse) - {"min_views", "max_spread", "rule"}:
+        raise TypeError("fuse takes min_views, max_spread and rule")
+    if fuse.get("rule", "median") not in _DSM_FUSE_RULES:
+        raise ValueError("fuse's rule is 'min', 'median' or 'max', not %r" % (fuse["rule"],))
+    clouds = list(clouds)
+    if not 1 <= len(clouds) <= 8:
+        raise ValueError("1 to 8 clouds, not %d" % len(clouds))
+    maps, sources, counts, ws = [], [], [], None
+    for cloud in clouds:
+        if ws is None:
+            ws = capi.dev_bytes(int(capi.LIB.ssrlcv_hip_dsm_rasterize_workspace_bytes(capi.c_u32(frame.w), capi.c_u32(frame.h))))
+        height, source, count = capi.dsm_rasterize(cloud, frame, _DSM_RULES[rule], True, True, ws)
+        maps.append(height), sources.append(source), counts.append(count)
+    fused, views = capi.dsm_fuse(maps, fuse.get("min_views", 1), fuse.get("max_spread", float("inf")), _DSM_FUSE_RULES[fuse.get("rule", "median")])
+    return {"height": _post_filter(fused, post), "fused": fused, "views": views, "maps": maps, "sources": sources, "counts": counts}
+
+
+def surface_mesh(model, frame, max_jump):
+    """The surface of a surface model: the valid cells of model["height"] as world-frame vertices (capi.dsm_points), the mesh of
+    the height map at step 1 (two cells whose heights differ by more than max_jump are not joined), its faces and normals.
+    With (ex, ey, -ez) right-handed the normals face +ez.  -> dict(points float32 (n, 3), faces int32 (T, 3), normals, mesh)."""
+    height = model["height"]
+    pts, n = capi.dsm_points(height, frame)
+    mesh = disparity_mesh(height, 1, max_jump)
+    assert mesh["n_vertices"] == n
+    return {"points": pts, "faces": mesh_faces(mesh), "normals": mesh_normals(mesh, pts), "mesh": mesh}
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:
