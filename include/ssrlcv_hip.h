@@ -1109,8 +1109,8 @@ int ssrlcv_hip_mesh_normals(const ssrlcv_float3* points, uint32_t n, const uint3
  * count, at most one of each per point: adjacent lanes of a wave that fall into one cell share theirs -- which commute: the maps
  * do not depend on the order the points arrive in and are bit-equal run to run.
  * dsm_fuse and dsm_points use no atomics.
- * Out of scope: a mean or any float accumulation per cell; ortho-image colours (the source map reduces them to a gather); a
- * ground frame fitted to the cloud; pushbroom pairs; more than 8 maps. */
+ * Out of scope: a mean or any float accumulation per cell; a ground frame fitted to the cloud; pushbroom pairs; more than 8
+ * maps.  The picture on the surface is the next section, "ortho-image". */
 typedef struct {
   float origin[3];  /* the world position of the corner of cell (0, 0) */
   float ex[3];      /* the direction of growing i */
@@ -1128,6 +1128,73 @@ int ssrlcv_hip_dsm_fuse(const float* const* maps, uint32_t m, uint32_t w, uint32
 size_t ssrlcv_hip_dsm_points_workspace_bytes(uint32_t w, uint32_t h);
 int ssrlcv_hip_dsm_points(const float* height, const ssrlcv_dsm_frame* frame, ssrlcv_float3* out, uint32_t capacity, uint32_t* count_dev,
                           void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- ortho-image: the grey of every valid cell of a height map -- the fused, filled map of "surface model", cells that the fill
+ * or the median created included -- taken from up to 8 source images, each view tested for occlusion by a march over the height
+ * map towards its camera.  The heights and this raster are co-registered: cell for cell the same grid.  Everything is float32,
+ * every product, sum and division rounded on its own, nothing contracted: csrc/ortho.hip is held to a numpy restatement byte for
+ * byte (tests/ortho_ref.py, tests/test_gpu_ortho.py).
+ *   view        ssrlcv_ortho_view, made by ssrlcv_dsm_ortho_view_host from an Image::Camera record and the frame (host only, in
+ *               double, no device): f = foc / dpix with dpix = foc tan(fov.x / 2) / (size.x / 2) (step 1 of "rectification"'s
+ *               builder, NOT the stored dpix); R = Rz Ry Rx of cam_rot from double sin / cos of the float angles;
+ *               K = [[f, 0, size.x / 2], [0, f, size.y / 2], [0, 0, 1]]; M = K R^T; pos = cam_pos, where generateBundle's rays
+ *               start (ecef_offset is not added: ssrlcv_projection_matrix_host is another frame); eye = ((q . ex) / cell,
+ *               (q . ey) / cell, q . ez) with q = pos - origin; all rounded to float32 at the end; w, h = size; `image` is left as
+ *               it was.  SSRLCV_ERR_INVALID_ARG for a NULL, a refused frame (the rules of "surface model"), a zero side, foc or
+ *               fov.x not finite and positive, or a field of view at a pole of tan; `out` is untouched on error.
+ *   per cell    (i, j) of the w x h map, z its height.  If z is 0x7FC00000 or not finite: ortho = 0, seen = 0, which = 0xFF.
+ *               Otherwise, for every view k in the given order:
+ *     position    a = ((float)i + 0.5f) cell, b = ((float)j + 0.5f) cell, P = ((origin + a ex) + b ey) + z ez: item 3 of "surface
+ *                 model", so a vertex of ssrlcv_hip_dsm_points and its colour are the same point.
+ *     projection  d = P - pos; X = (M0 d.x + M1 d.y) + M2 d.z, Y with M3..5, W with M6..8; sx = X / W, sy = Y / W.  The view can
+ *                 see the cell only if W > 0, sx and sy are finite, 0 <= sx <= w_k - 1 and 0 <= sy <= h_k - 1 (MAPPED and INSIDE
+ *                 of "rectification").
+ *     visibility  in grid coordinates: ci = (float)i + 0.5f, cj = (float)j + 0.5f; du = eye0 - ci, dv = eye1 - cj, dz = eye2 - z.
+ *                 !(dz > 0): not seen (a camera at or below the cell).  L = max(|du|, |dv|); L < 1 or maxSteps == 0: visible.
+ *                 Otherwise su = du / L, sv = dv / L, sz = dz / L and for s = 1 .. maxSteps, fs = (float)s:
+ *                   fs > L: visible (the march has passed the camera)
+ *                   u = ci + fs su, v = cj + fs sv, zr = z + fs sz (one product and one sum each); fi = floorf(u), fj = floorf(v)
+ *                   !(fi >= 0 && fi < (float)w && fj >= 0 && fj < (float)h), on floats as in rasterize: visible
+ *                   hh = height(fi, fj); if its pattern is not 0x7FC00000 and hh > zr + bias: OCCLUDED (+inf occludes, another
+ *                   NaN never does)
+ *                 Out of steps: visible.  The march is exact geometry for an orthonormal frame (pipeline.dsm_frame makes one);
+ *                 for a skew frame it is still the defined result.  bias >= 0 (+inf is legal) absorbs the staircase of a
+ *                 sampled slope.
+ *     sample      the bilinear expression of ssrlcv_hip_warp_homography_u8 at (sx, sy), word for word (csrc/bilinear_u8.h).
+ *   choice      among the views that see the cell, n of them: rule 0 FIRST, the first in the given order (the caller lists the
+ *               best view first); rule 1 MEDIAN, the lower median of their bytes, rank (n - 1) / 2.  seen: bit k = view k sees
+ *               the cell.  which: the smallest k among the seeing views that has the chosen byte, 0xFF when n = 0.  ortho = 0
+ *               when n = 0.
+ * Every entry of every given output is written and nothing behind it; seen and which may be NULL; inputs are never written;
+ * views_host is a HOST array, copied into the launch.
+ * Refusals, decided on the host before any launch, the parameters before the sizes before the buffers: SSRLCV_ERR_INVALID_ARG
+ * for a NULL or refused frame, a NULL params or views_host, m 0 or above 8, rule > 1, !(bias >= 0), a view with a zero side, a
+ * side above 2^24, w h >= 2^31 or a non-finite entry of M, pos or eye, then a grid with w h >= 2^31; then SSRLCV_ERR_UNSUPPORTED
+ * for a grid side above 2^24; an empty grid is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL height, ortho, view image or
+ * workspace; then SSRLCV_ERR_WORKSPACE.
+ * Workspace (host only; 0 for a refused size or m): a256(4), the greatest height's order key.  It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no float atomics -- one integer atomicMax a wave for the greatest
+ * height that is not a NaN, which lets a march stop, visible, once zr + bias has reached it (zr never decreases with s): the
+ * outputs do not depend on it and are bit-equal run to run.
+ * Out of scope, not built: colour images; a mean or blend of views; seam smoothing; pushbroom views; sampling other than
+ * bilinear; more than 8 views. */
+typedef struct {
+  const uint8_t* image; /* DEVICE pointer, uint8, pitch = w */
+  uint32_t w, h;        /* the source image */
+  float M[9];           /* row-major K R^T: world direction from the camera -> homogeneous pixel */
+  float pos[3];         /* the camera's position in the clouds' world frame */
+  float eye[3];         /* the camera in grid coordinates: (a / cell, b / cell, height) */
+} ssrlcv_ortho_view; /* 80 bytes */
+typedef struct {
+  uint32_t maxSteps; /* the march's length in cells of the dominant axis; 0 = no occlusion test */
+  float bias;        /* >= 0: how far a height must stand above the line of sight to hide the cell */
+  uint32_t rule;     /* 0 FIRST, 1 MEDIAN */
+} ssrlcv_ortho_params;
+int ssrlcv_dsm_ortho_view_host(const ssrlcv_camera* cam, const ssrlcv_dsm_frame* frame, ssrlcv_ortho_view* out); /* host only */
+size_t ssrlcv_hip_dsm_ortho_workspace_bytes(uint32_t w, uint32_t h, uint32_t m);
+int ssrlcv_hip_dsm_ortho(const float* height, const ssrlcv_dsm_frame* frame, const ssrlcv_ortho_view* views_host, uint32_t m,
+                         const ssrlcv_ortho_params* params, uint8_t* ortho, uint8_t* seen /* may be NULL */, uint8_t* which /* may be NULL */,
+                         void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

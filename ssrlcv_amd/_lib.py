@@ -71,7 +71,8 @@ def load():
                      "ssrlcv_hip_disparity_components_workspace_bytes", "ssrlcv_hip_stereo_filter_speckles_workspace_bytes",
                      "ssrlcv_hip_stereo_fill_holes_workspace_bytes", "ssrlcv_hip_disparity_mesh_workspace_bytes",
                      "ssrlcv_hip_mesh_select_workspace_bytes", "ssrlcv_hip_mesh_triangles_workspace_bytes",
-                     "ssrlcv_hip_dsm_rasterize_workspace_bytes", "ssrlcv_hip_dsm_points_workspace_bytes"):
+                     "ssrlcv_hip_dsm_rasterize_workspace_bytes", "ssrlcv_hip_dsm_points_workspace_bytes",
+                     "ssrlcv_hip_dsm_ortho_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -124,4 +125,5 @@ EXPORTED = [
     "ssrlcv_hip_mesh_select", "ssrlcv_hip_mesh_triangles_workspace_bytes", "ssrlcv_hip_mesh_triangles", "ssrlcv_hip_mesh_normals",
     "ssrlcv_hip_dsm_rasterize_workspace_bytes", "ssrlcv_hip_dsm_rasterize", "ssrlcv_hip_dsm_fuse",
     "ssrlcv_hip_dsm_points_workspace_bytes", "ssrlcv_hip_dsm_points",
+    "ssrlcv_dsm_ortho_view_host", "ssrlcv_hip_dsm_ortho_workspace_bytes", "ssrlcv_hip_dsm_ortho",
 ]

@@ -951,6 +951,59 @@ def dsm_points(height_d, frame, capacity=None):
     return out[: min(n, cap)], n
 
 
+# ------------------------------------------------------------------ ortho-image
+class OrthoView(ctypes.Structure):
+    """ssrlcv_ortho_view: a source image and its camera as the ortho-image reads it (made by dsm_ortho_view)"""
+    _fields_ = [("image", c_vp), ("w", c_u32), ("h", c_u32), ("M", c_f32 * 9), ("pos", c_f32 * 3), ("eye", c_f32 * 3)]
+
+
+class OrthoParams(ctypes.Structure):
+    _fields_ = [("maxSteps", c_u32), ("bias", c_f32), ("rule", c_u32)]
+
+
+assert ctypes.sizeof(OrthoView) == 80 and ctypes.sizeof(OrthoParams) == 12
+
+ORTHO_FIRST, ORTHO_MEDIAN = 0, 1   # dsm_ortho's rule
+ORTHO_NO_VIEW = 0xFF               # which: no view sees the cell
+
+
+def dsm_ortho_view(cam, frame):
+    """ssrlcv_dsm_ortho_view_host of one Image::Camera record over the grid of `frame` (host arithmetic: needs no GPU) -> an
+    OrthoView whose image pointer is NULL."""
+    raw = camera_bytes(cam)
+    out = OrthoView()
+    check(LIB.ssrlcv_dsm_ortho_view_host(raw.ctypes.data_as(c_vp), ctypes.byref(frame), ctypes.byref(out)))
+    return out
+
+
+def dsm_ortho(height_d, frame, views, images, max_steps, bias, rule, want_seen=True, want_which=True, workspace=None):
+    """The ortho-image of a height map (ssrlcv_hip_dsm_ortho; include/ssrlcv_hip.h "ortho-image"): every valid cell's grey from the
+    first (ORTHO_FIRST) of `views` that sees it, or the lower median (ORTHO_MEDIAN) of those that do, a view seeing a cell if the
+    cell projects into its image and no height within max_steps cells towards the camera stands more than `bias` above the line
+    of sight.  views: 1 to 8 OrthoView; images: their uint8 (h, w) device tensors.  -> (ortho uint8 (h, w); seen uint8 (h, w), bit
+    k = view k sees the cell; which uint8 (h, w), the view the grey came from, ORTHO_NO_VIEW for none); seen and which are None
+    unless asked for.  The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    h, w = _disparity_map(height_d)
+    assert (h, w) == (int(frame.h), int(frame.w)), "the map has the frame's grid"
+    views, images = list(views), list(images)
+    assert len(views) == len(images), "one image a view"
+    arr = (OrthoView * max(len(views), 1))()
+    for k, (v, img) in enumerate(zip(views, images)):
+        assert img.dim() == 2 and img.dtype == torch.uint8 and img.is_cuda and img.is_contiguous()   # read with pitch w
+        assert tuple(img.shape) == (int(v.h), int(v.w)), "the image has the view's size"
+        ctypes.memmove(ctypes.byref(arr[k]), ctypes.byref(v), ctypes.sizeof(OrthoView))
+        arr[k].image = img.data_ptr()
+    need = int(LIB.ssrlcv_hip_dsm_ortho_workspace_bytes(c_u32(w), c_u32(h), c_u32(len(views))))
+    ws = workspace if workspace is not None and workspace.numel() >= need else dev_bytes(need)
+    params = OrthoParams(int(max_steps), float(bias), int(rule))
+    ortho = torch.empty((h, w), dtype=torch.uint8, device="cuda")
+    seen = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_seen else None
+    which = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_which else None
+    check(LIB.ssrlcv_hip_dsm_ortho(ptr(height_d), ctypes.byref(frame), arr, c_u32(len(views)), ctypes.byref(params), ptr(ortho), ptr(seen), ptr(which),
+                                   ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return ortho, seen, which
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -20,16 +20,19 @@
 #include "align256.h"
 #include "compact.h"
 #include "device_math.h"
+#include "dsm_frame.h"
 #include "order_key.h"
 
 namespace {
 
+using dsm::finite_bits;
+using dsm::frame_ok;
+using dsm::too_long_a_side;
+using dsm::too_many_cells;
+
 constexpr uint32_t kNaN = 0x7FC00000u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kPerThread = 16;  // compact.h: a wave owns a run of 1024 elements, a block 4096
-constexpr uint32_t kMaxSide = 1u << 24;  // (float)w is exact up to here
-
-__host__ __device__ __forceinline__ bool finite_bits(uint32_t bits) { return (bits & 0x7F800000u) != 0x7F800000u; }
 
 // a . e in the contract's order: ((q.x e.x) + (q.y e.y)) + (q.z e.z)
 __device__ __forceinline__ float along(float qx, float qy, float qz, const float (&e)[3]) { return ((qx * e[0]) + (qy * e[1])) + (qz * e[2]); }
@@ -157,21 +160,6 @@ struct DsmEmit {
 };
 
 // ---- host side
-bool finite_host(float v) {
-  uint32_t bits;
-  __builtin_memcpy(&bits, &v, 4);
-  return finite_bits(bits);
-}
-
-bool frame_ok(const ssrlcv_dsm_frame* f) {
-  if (!f) return false;
-  for (int k = 0; k < 3; ++k)
-    if (!finite_host(f->origin[k]) || !finite_host(f->ex[k]) || !finite_host(f->ey[k]) || !finite_host(f->ez[k])) return false;
-  return finite_host(f->cell) && f->cell > 0.0f;
-}
-
-bool too_many_cells(uint32_t w, uint32_t h) { return (unsigned long long)w * h >= (1ull << 31); }
-bool too_long_a_side(uint32_t w, uint32_t h) { return w > kMaxSide || h > kMaxSide; }
 size_t accumulator_bytes(uint32_t w, uint32_t h) { return align256((size_t)w * h * 8); }
 size_t compaction_bytes(uint32_t n) { return align256(svc::workspace_words<1, kPerThread>(n) * 4); }
 dim3 blocks_for(uint32_t n) { return dim3((n + 255u) / 256u); }

@@ -16,6 +16,8 @@
 #include <stdint.h>
 #include <string.h>
 #include "ssrlcv_hip.h"
+#include "bilinear_u8.h"
+#include "camera_host.h"
 #include "device_math.h"
 
 namespace {
@@ -47,18 +49,7 @@ __device__ __forceinline__ bool h_inside(const Homography& H, float x, float y, 
 __device__ __forceinline__ uint32_t warp_pixel(const uint8_t* __restrict__ src, int sw, int sh, const Homography& H, uint32_t x, uint32_t y) {
   float sx, sy;
   if (!h_mapped(H, (float)x, (float)y, sx, sy)) return 0u;
-  sx = fminf(fmaxf(sx, 0.0f), (float)(sw - 1));
-  sy = fminf(fmaxf(sy, 0.0f), (float)(sh - 1));
-  const int x0 = min((int)floorf(sx), max(sw - 2, 0)), x1 = min(x0 + 1, sw - 1);
-  const int y0 = min((int)floorf(sy), max(sh - 2, 0)), y1 = min(y0 + 1, sh - 1);
-  const float fx = sx - (float)x0, fy = sy - (float)y0;
-  const uint8_t* r0 = src + (size_t)y0 * sw;
-  const uint8_t* r1 = src + (size_t)y1 * sw;
-  const float a = (float)r0[x0], b = (float)r0[x1], c = (float)r1[x0], d = (float)r1[x1];
-  const float top = a + fx * (b - a);
-  const float bot = c + fx * (d - c);
-  const float v = top + fy * (bot - top);
-  return (uint32_t)floorf(v + 0.5f);  // 0 .. 255
+  return bilinear_u8(src, sw, sh, sx, sy);
 }
 
 // items = rows x lanesPerRow; item (y, 0) is the row's unaligned head (0 .. 3 pixels), item (y, j >= 1) its j-th aligned group
@@ -148,28 +139,12 @@ unsigned capped_blocks(uint32_t items) {
   return b > 2048u ? 2048u : b;
 }
 
-// 3 x 3 double matrices, row-major
-struct M3 {
-  double m[3][3];
-};
-M3 mul(const M3& a, const M3& b) {
-  M3 o;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) o.m[i][j] = a.m[i][0] * b.m[0][j] + a.m[i][1] * b.m[1][j] + a.m[i][2] * b.m[2][j];
-  return o;
-}
-M3 transpose(const M3& a) {
-  M3 o;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) o.m[i][j] = a.m[j][i];
-  return o;
-}
-// rotatePoint's matrix Rz(z) Ry(y) Rx(x)
-M3 euler_matrix(double x, double y, double z) {
-  const double cx = cos(x), sx = sin(x), cy = cos(y), sy = sin(y), cz = cos(z), sz = sin(z);
-  M3 o = {{{cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx}, {sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx}, {-sy, cy * sx, cy * cx}}};
-  return o;
-}
+using camera_host::euler_matrix;
+using camera_host::finite_positive;
+using camera_host::M3;
+using camera_host::mul;
+using camera_host::transpose;
+
 M3 adjugate(const M3& a) {  // the inverse up to the determinant, which the normalisation divides out
   M3 o;
   o.m[0][0] = a.m[1][1] * a.m[2][2] - a.m[1][2] * a.m[2][1];
@@ -187,8 +162,6 @@ double det(const M3& a) {
   return a.m[0][0] * (a.m[1][1] * a.m[2][2] - a.m[1][2] * a.m[2][1]) - a.m[0][1] * (a.m[1][0] * a.m[2][2] - a.m[1][2] * a.m[2][0]) +
          a.m[0][2] * (a.m[1][0] * a.m[2][1] - a.m[1][1] * a.m[2][0]);
 }
-bool finite_positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
-
 // K(fi) M K(fl)^-1 T(t, ty), its last entry 1.  K^-1 is applied by columns -- col0 / fl, col1 / fl, col2 - col0' cx - col1' cy --
 // so that M = identity with fi = fl gives the identity exactly
 bool compose(const M3& M, double fi, double fl, double cx, double cy, double t, double ty, M3& H) {
@@ -237,9 +210,7 @@ int ssrlcv_rectify_cameras_host(const ssrlcv_camera* left, const ssrlcv_camera* 
   double f[2];
   M3 R[2];
   for (int i = 0; i < 2; ++i) {
-    const double foc = (double)cams[i]->foc;
-    const double dpix = foc * tan((double)cams[i]->fov.x / 2.0) / ((double)cams[i]->size.x / 2.0);
-    f[i] = foc / dpix;
+    f[i] = camera_host::focal_pixels((double)cams[i]->foc, (double)cams[i]->fov.x, (double)cams[i]->size.x);
     if (!finite_positive(f[i])) return SSRLCV_ERR_INVALID_ARG;  // a field of view at a pole of tan
     R[i] = euler_matrix((double)cams[i]->cam_rot.x, (double)cams[i]->cam_rot.y, (double)cams[i]->cam_rot.z);
   }

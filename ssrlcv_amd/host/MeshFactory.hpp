@@ -11,6 +11,7 @@
 // (filtered points, normals, mean distances) are left in the state the points were in.
 #pragma once
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "GridMesh.hpp"
@@ -79,6 +80,7 @@ class MeshFactory {
  public:
   ptr::value<Unity<float3>> points;
   ptr::value<Unity<float3>> normals;  // null until computeNormals; kept row for row with points by the filter
+  ptr::value<Unity<unsigned char>> colors;  // null until setVertexColors: one grey a point; dropped by setPoints and by the filter
   double filterStats[3] = {0, 0, 0};  // {mu, std, threshold} of the last filterByNeighborDistance
   GridMesh surface;                   // set by setSurface: vertex v is points[v]; its own copy of the maps, in state gpu
   bool hasSurface = false;
@@ -90,6 +92,7 @@ class MeshFactory {
   void setPoints(ptr::value<Unity<float3>> pts) {
     points = pts;
     normals = ptr::value<Unity<float3>>();
+    colors = ptr::value<Unity<unsigned char>>();
     clearSurface();
   }
 
@@ -180,6 +183,7 @@ class MeshFactory {
     ptr::device<ssrlcv_float3> kept(n);
     ptr::device<float> keptNormals(withNormals ? 3 * n : 1);
     const uint32_t c = filter(k, sigma, kept, withNormals ? &keptNormals : nullptr, nullptr, hasSurface);
+    colors = ptr::value<Unity<unsigned char>>();  // set for the points as they were
     logger.info.printf("MeshFactory::filterByNeighborDistance: %u of %lu points kept (mu %.6g, std %.6g, threshold %.6g)",
                        c, n, filterStats[0], filterStats[1], filterStats[2]);
     if (c == 0) {
@@ -303,6 +307,83 @@ class MeshFactory {
     if (origin != gpu) height->setMemoryState(origin);
   }
 
+  // ---- the ortho-image (include/ssrlcv_hip.h "ortho-image"): the picture on the surface model.  generateOrthoImage on the fused,
+  // filled height map, then setVertexColors(ortho, height) behind setPointsFromHeightMap(height, frame): saveMesh writes the greys.
+
+  // the grey of every valid cell of `height` from 1 to 8 source images (uint8, cameras[k].size) and their cameras, each view tested
+  // for occlusion by a march over the map; in state gpu, frame.w x frame.h, 0 where no view sees the cell; null when refused.
+  // *seen and *which, when asked for, hold the views that see a cell as bits and the view its grey came from (0xFF: none).
+  // The map and the images are left in the state they came in.
+  static ptr::value<Unity<unsigned char>> generateOrthoImage(ptr::value<Unity<float>> height, const ssrlcv_dsm_frame& frame,
+                                                             const std::vector<ptr::value<Unity<unsigned char>>>& images,
+                                                             const std::vector<ssrlcv_camera>& cameras, const ssrlcv_ortho_params& params,
+                                                             ptr::value<Unity<unsigned char>>* seen = nullptr,
+                                                             ptr::value<Unity<unsigned char>>* which = nullptr) {
+    const unsigned long cells = (unsigned long)frame.w * frame.h;
+    if (height == nullptr || cells == 0 || height->size() != cells || images.empty() || images.size() > 8 || images.size() != cameras.size()) {
+      logger.err << "MeshFactory::generateOrthoImage: needs a map of frame.w frame.h entries and 1 to 8 images with their cameras";
+      return ptr::value<Unity<unsigned char>>();
+    }
+    std::vector<ssrlcv_ortho_view> views(images.size());
+    std::vector<MemoryState> origin;
+    for (size_t k = 0; k < images.size(); ++k) {
+      views[k].image = nullptr;
+      if (ssrlcv_dsm_ortho_view_host(&cameras[k], &frame, &views[k]) != SSRLCV_OK || images[k] == nullptr ||
+          images[k]->size() != (unsigned long)views[k].w * views[k].h) {
+        logger.err.printf("MeshFactory::generateOrthoImage: view %lu: a refused camera, or an image that has not its size", (unsigned long)k);
+        for (size_t i = 0; i < origin.size(); ++i)
+          if (origin[i] != gpu) images[i]->setMemoryState(origin[i]);
+        return ptr::value<Unity<unsigned char>>();
+      }
+      origin.push_back(images[k]->getMemoryState());
+      if (origin.back() != gpu) images[k]->setMemoryState(gpu);
+      views[k].image = images[k]->device.get();
+    }
+    MemoryState originH = height->getMemoryState();
+    if (originH != gpu) height->setMemoryState(gpu);
+    const size_t wsb = ssrlcv_hip_dsm_ortho_workspace_bytes(frame.w, frame.h, (uint32_t)views.size());
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::value<Unity<unsigned char>> ortho(nullptr, cells, gpu);
+    if (seen) *seen = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
+    if (which) *which = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
+    HipSafeCall(ssrlcv_hip_dsm_ortho(height->device.get(), &frame, views.data(), (uint32_t)views.size(), &params, ortho->device.get(),
+                                     seen ? (*seen)->device.get() : nullptr, which ? (*which)->device.get() : nullptr, ws.get(), wsb, nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    if (originH != gpu) height->setMemoryState(originH);
+    for (size_t k = 0; k < images.size(); ++k)
+      if (origin[k] != gpu) images[k]->setMemoryState(origin[k]);
+    return ortho;
+  }
+
+  // one grey a point: the ortho-image's bytes of the valid cells of `height` in raster order, the order setPointsFromHeightMap
+  // gave the points of the same map.  In state cpu; both maps come back to the state they came in.
+  void setVertexColors(ptr::value<Unity<unsigned char>> ortho, ptr::value<Unity<float>> height) {
+    if (points == nullptr || ortho == nullptr || height == nullptr || ortho->size() != height->size()) {
+      logger.err << "MeshFactory::setVertexColors: needs points, and an ortho-image and a height map of one grid";
+      return;
+    }
+    MemoryState originO = ortho->getMemoryState(), originH = height->getMemoryState();
+    if (originO == gpu || ortho->getFore() == gpu) ortho->transferMemoryTo(cpu);
+    if (originH == gpu || height->getFore() == gpu) height->transferMemoryTo(cpu);
+    const unsigned char* grey = ortho->host.get();
+    const float* z = height->host.get();
+    std::vector<unsigned char> kept;
+    for (unsigned long c = 0; c < height->size(); ++c) {
+      uint32_t bits;
+      std::memcpy(&bits, z + c, 4);
+      if (bits != 0x7FC00000u) kept.push_back(grey[c]);
+    }
+    if (originO == gpu) ortho->setMemoryState(gpu);
+    if (originH == gpu) height->setMemoryState(gpu);
+    if (kept.size() != points->size()) {
+      logger.err.printf("MeshFactory::setVertexColors: the map has %lu valid cells, the cloud %lu points", (unsigned long)kept.size(), points->size());
+      return;
+    }
+    ptr::host<unsigned char> values((long)kept.size(), true);
+    std::memcpy(values.get(), kept.data(), kept.size());
+    colors = ptr::value<Unity<unsigned char>>(values, (unsigned long)kept.size(), cpu, true);
+  }
+
   // ASCII PLY of the points (and their normals once computed) as <dir><filename>.ply
   void savePoints(std::string filename, std::string dir = "out/") {
     if (points == nullptr) return;
@@ -310,11 +391,15 @@ class MeshFactory {
     else writePLY(filename, points, dir);
   }
 
-  // ASCII PLY of the points, their normals once computed, and the surface's triangles as <dir><filename>.ply
+  // ASCII PLY of the points, their normals once computed, their greys once set (uchar red green blue, the grey three times), and
+  // the surface's triangles as <dir><filename>.ply
   void saveMesh(std::string filename, std::string dir = "out/") {
     if (points == nullptr) return;
     const bool withNormals = normals != nullptr && normals->size() == points->size();
-    writePLY(filename, points, withNormals ? normals : ptr::value<Unity<float3>>(), faces(), dir);
+    if (colors != nullptr && colors->size() == points->size())
+      writePLY(filename, points, withNormals ? normals : ptr::value<Unity<float3>>(), colors, faces(), dir);
+    else
+      writePLY(filename, points, withNormals ? normals : ptr::value<Unity<float3>>(), faces(), dir);
   }
 };
 

@@ -96,4 +96,50 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
   if (withNormals && originN == gpu) normals->setMemoryState(gpu);
   if (numFaces && originF == gpu) faces->setMemoryState(gpu);
 }
+
+// The same writer with a grey per vertex behind the normals (property uchar red / green / blue, the grey three times;
+// MeshFactory::saveMesh once setVertexColors has run).  `colors` is read in host memory.
+inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr::value<Unity<float3>> normals,
+                     ptr::value<Unity<unsigned char>> colors, ptr::value<Unity<uint3>> faces, std::string dir = "out/") {
+  const bool withNormals = normals != nullptr;
+  if ((withNormals && normals->size() != points->size()) || colors == nullptr || colors->size() != points->size()) {
+    logger.err.printf("writePLY: %lu normals and %lu colours for %lu points", withNormals ? normals->size() : 0ul,
+                      colors == nullptr ? 0ul : colors->size(), points->size());
+    return;
+  }
+  const unsigned long numFaces = faces != nullptr ? faces->size() : 0ul;
+  MemoryState origin = points->getMemoryState(), originN = withNormals ? normals->getMemoryState() : cpu;
+  MemoryState originF = numFaces ? faces->getMemoryState() : cpu, originC = colors->getMemoryState();
+  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
+  if (withNormals && (originN == gpu || normals->getFore() == gpu)) normals->transferMemoryTo(cpu);
+  if (numFaces && (originF == gpu || faces->getFore() == gpu)) faces->transferMemoryTo(cpu);
+  if (originC == gpu || colors->getFore() == gpu) colors->transferMemoryTo(cpu);
+  std::ofstream of;
+  of.open(dir + filename + ".ply");
+  of.precision(9);
+  of << "ply\nformat ascii 1.0\n";
+  of << "comment author: SSRLCV simple PLY writer (MI355X build)\n";
+  of << "element vertex " << points->size() << "\n";
+  of << "property float x\nproperty float y\nproperty float z\n";
+  if (withNormals) of << "property float nx\nproperty float ny\nproperty float nz\n";
+  of << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  of << "element face " << numFaces << "\n";
+  of << "property list uchar int vertex_indices\n";
+  of << "end_header\n";
+  const float3* p = points->host.get();
+  const float3* n = withNormals ? normals->host.get() : nullptr;
+  const unsigned char* g = colors->host.get();
+  for (unsigned long i = 0; i < points->size(); i++) {
+    of << p[i].x << " " << p[i].y << " " << p[i].z;
+    if (n) of << " " << n[i].x << " " << n[i].y << " " << n[i].z;
+    of << " " << (unsigned)g[i] << " " << (unsigned)g[i] << " " << (unsigned)g[i] << "\n";
+  }
+  const uint3* f = numFaces ? faces->host.get() : nullptr;
+  for (unsigned long i = 0; i < numFaces; i++) of << "3 " << f[i].x << " " << f[i].y << " " << f[i].z << "\n";
+  of.close();
+  if (origin == gpu) points->setMemoryState(gpu);
+  if (withNormals && originN == gpu) normals->setMemoryState(gpu);
+  if (numFaces && originF == gpu) faces->setMemoryState(gpu);
+  if (originC == gpu) colors->setMemoryState(gpu);
+}
 }  // namespace ssrlcv

@@ -425,6 +425,35 @@ def surface_mesh(model, frame, max_jump):
     return {"points": pts, "faces": mesh_faces(mesh), "normals": mesh_normals(mesh, pts), "mesh": mesh}
 
 
+_ORTHO_RULES = {"first": capi.ORTHO_FIRST, "median": capi.ORTHO_MEDIAN}
+
+
+def surface_ortho(model_or_height, frame, images, cameras, max_steps=256, bias=None, rule="first"):
+    """The ortho-image of a surface model (surface_model's dictionary, or its height map alone) from 1 to 8 source images (uint8
+    (h, w) device tensors) and their Image::Camera records (include/ssrlcv_hip.h "ortho-image"): every valid cell of the
+    filled map -- cells the fill or the median created included -- takes the grey of the "first" view, in the order given, that
+    sees it, or the lower "median" of the views that do.  A view sees a cell if the cell projects into its image and no height
+    within max_steps cells towards the camera stands more than `bias` above the line of sight (None: half a cell).
+    -> dict(ortho uint8 (h, w), 0 where no view sees the cell; seen uint8 (h, w): bit k = view k sees it; which uint8 (h, w): the
+    view the grey came from, 0xFF for none)."""
+    if rule not in _ORTHO_RULES:
+        raise ValueError("rule is 'first' or 'median', not %r" % (rule,))
+    images, cameras = list(images), list(cameras)
+    if not 1 <= len(images) <= 8 or len(images) != len(cameras):
+        raise ValueError("1 to 8 images and as many cameras, not %d and %d" % (len(images), len(cameras)))
+    height = model_or_height["height"] if isinstance(model_or_height, dict) else model_or_height
+    views = [capi.dsm_ortho_view(cam, frame) for cam in cameras]
+    ortho, seen, which = capi.dsm_ortho(height, frame, views, images, max_steps, 0.5 * float(frame.cell) if bias is None else bias, _ORTHO_RULES[rule])
+    return {"ortho": ortho, "seen": seen, "which": which}
+
+
+def surface_colors(ortho, height):
+    """The ortho-image's bytes of the valid cells of `height` in raster order: one grey a vertex of capi.dsm_points and of
+    surface_mesh (the mesh's numbering at step 1).  -> uint8 (n,) device tensor."""
+    assert ortho.shape == height.shape and ortho.dtype == torch.uint8 and height.dtype == torch.float32
+    return ortho[height.view(torch.int32) != capi.STEREO_INVALID_BITS]
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:
