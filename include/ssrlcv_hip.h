@@ -53,7 +53,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      stereo_sgm_census_u8;
  *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median;
  *      hole filling: stereo_fill_holes (+ its workspace query);
- *      disparity mesh: disparity_mesh, mesh_select, mesh_triangles (+ their workspace queries), mesh_normals */
+ *      disparity mesh: disparity_mesh, mesh_select, mesh_triangles (+ their workspace queries), mesh_normals;
+ *      surface accuracy: dsm_difference, difference_stats (+ its workspace query) */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1195,6 +1196,82 @@ size_t ssrlcv_hip_dsm_ortho_workspace_bytes(uint32_t w, uint32_t h, uint32_t m);
 int ssrlcv_hip_dsm_ortho(const float* height, const ssrlcv_dsm_frame* frame, const ssrlcv_ortho_view* views_host, uint32_t m,
                          const ssrlcv_ortho_params* params, uint8_t* ortho, uint8_t* seen /* may be NULL */, uint8_t* which /* may be NULL */,
                          void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- surface accuracy: how far a cloud lies from a reference surface, and exact robust statistics of such differences --
+ * MeshFactory's calculatePerPointDifference / calculateAverageDifference upstream.  The reference is a height map in a frame of
+ * "surface model", triangulated by "disparity mesh": one definition of the surface, the mesh's.  Everything is a selection or a
+ * fixed-order expression, nothing contracted: csrc/accuracy.hip is held to a numpy restatement bit for bit
+ * (tests/accuracy_ref.py, tests/test_gpu_accuracy.py).
+ *   1 difference ssrlcv_hip_dsm_difference: `height` is the reference map of `frame` (float[w h], pitch w, invalid = 0x7FC00000).
+ *               Per point of index t, in float32: the skip rules and q, a, b, z, u, v of "surface model" item 1, word for word.  A
+ *               skipped point, or one whose z is not finite, gives 0x7FC00000.  Then
+ *     CELL        (cells NULL): fi = floorf(u), fj = floorf(v); inside iff fi >= 0 && fi < (float)w && fj >= 0 && fj < (float)h, on
+ *                 floats as in rasterize; r = height(fi, fj); an r that is 0x7FC00000 or not finite, or a point outside, gives
+ *                 0x7FC00000; otherwise diff = z - r.
+ *     MESH        (cells given): `cells` is what ssrlcv_hip_disparity_mesh wrote for the same map at step 1 (its item 3: bit 0 / 1 =
+ *                 T0 / T1 emitted, bit 2 = the diagonal is b-c; its maxJump cuts are in it), pitch w - 1.  The mesh's vertices sit
+ *                 at cell centres: uu = u - 0.5f, vv = v - 0.5f, fi = floorf(uu), fj = floorf(vv); inside iff fi >= 0 &&
+ *                 fi < (float)(w - 1) && fj >= 0 && fj < (float)(h - 1) -- a grid with w or h below 2 has no inside, and a point
+ *                 within half a cell of the border is inside in CELL mode and outside here.  s = uu - fi, t = vv - fj; the corners
+ *                 a, b, c, d of cell (fi, fj) as in "disparity mesh" item 3, za .. zd their heights:
+ *                   diagonal a-d   T0 iff t >= s:      r = za + ((t (zc - za)) + (s (zd - zc)))
+ *                                  otherwise T1:       r = za + ((s (zb - za)) + (t (zd - zb)))
+ *                   diagonal b-c   T0 iff s + t <= 1:  r = za + ((s (zb - za)) + (t (zc - za)))
+ *                                  otherwise T1:       r = zd + (((1 - s) (zc - zd)) + ((1 - t) (zb - zd)))
+ *                 A triangle whose bit is clear gives 0x7FC00000, and so does an r that is not finite; otherwise diff = z - r:
+ *                 positive means above the reference along ez.  Only the corners of the chosen triangle are read.
+ *               Every entry of diff[n] is written and nothing behind it; inputs are never written.
+ *   2 stats     ssrlcv_hip_difference_stats over values[n], e.g. item 1's output:
+ *     validity    an entry is valid iff its bits are not 0x7FC00000; `valid` counts them.
+ *     value       a valid entry x becomes y = x - center, one float subtraction, and with absolute = 1 fabsf of that.
+ *     selection   only entries whose y is finite take part: `finite` = m of them.
+ *     min, max    the y of least and greatest key ("surface model" key: -0 below +0); 0x7FC00000 when m is 0.
+ *     quantile    params.quantile[k], k < numQuantiles, is in parts per 10000; result slot k holds the y of rank
+ *                 (uint64)q (m - 1) / 10000 in key order: exact, always one of the inputs; 5000 is the lower median, 0 the min,
+ *                 10000 the max.  Slots k >= numQuantiles, and every slot when m is 0, hold 0x7FC00000; the parameter's entries
+ *                 k >= numQuantiles are not looked at.
+ *     sum, sumSq  float64 sums of (double)y and (double)y (double)y (the square is exact) in a fixed shape: tiles of 4096
+ *                 consecutive entries, excluded and padding entries adding +0.0; lane l of 256 adds entries l + 256 r, r = 0 .. 15,
+ *                 in that order, starting from +0.0; the 256 lane sums fold by acc[l] += acc[l + half] for l < half, half = 128,
+ *                 64, .., 1; the tile sums are reduced by the same shape again until one is left.  The mean and the RMS are the
+ *                 binders' business, in host float64.
+ *     record      ssrlcv_diff_stats in DEVICE memory: n, valid, finite, reserved = 0, sum, sumSq, min, max, quantile[8].  The
+ *                 empty record (n = 0): zeros, +0.0 sums, 0x7FC00000 in min, max and every slot.
+ * Refusals, decided on the host before any launch, in this order:
+ *   difference  SSRLCV_ERR_INVALID_ARG for a NULL or refused frame (the rules of "surface model"), then w h >= 2^31; then
+ *               SSRLCV_ERR_UNSUPPORTED for w or h above 2^24; n = 0 is then SSRLCV_OK and nothing is looked at; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL points, height or diff.  An empty grid is legal: no point is inside it.
+ *   stats       SSRLCV_ERR_INVALID_ARG for a NULL params; numQuantiles > 8, a used quantile above 10000, a center that is not
+ *               finite, absolute > 1; then a NULL out_dev; n = 0 then writes the empty record and is SSRLCV_OK; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL values or workspace; then SSRLCV_ERR_WORKSPACE.
+ * Workspace of stats (host only; computed in size_t; 0 for refused params), a256 as in "disparity mesh", T(n) = ceil(n / 4096):
+ *     256 + 196608 + a256(16 T(n)) + a256(16 T(T(n)))
+ *   the control words, 3 passes x 8 histograms x 2048 bins x 4 bytes, and the partial sums of two levels.  It may hold anything on
+ *   entry.  The difference needs none.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  The difference uses no atomics.  The
+ * quantiles are a radix select over the keys, digits of 11, 11 and 10 bits from the top: histograms by INTEGER atomics (LDS, then global; the
+ * lanes of a wave that share the first lane's digit add once), a one-block step a pass that narrows every quantile's prefix and
+ * rank, all quantiles in the same passes, equal prefixes sharing a histogram.  Counts, min and max are integer atomics, one a
+ * block.  Integer atomics commute and the sums have a fixed shape: the record is bit-equal run to run and to the restatement.
+ * Out of scope, not built: differences along a direction other than the frame's ez; ray casts against unorganised meshes;
+ * registration or a shift search; float atomics; weighted statistics. */
+typedef struct {
+  float center;          /* finite: subtracted from every valid entry */
+  uint32_t absolute;     /* 0 or 1: fabsf of the difference to center */
+  uint32_t numQuantiles; /* 0 .. 8 */
+  uint32_t quantile[8];  /* parts per 10000, 0 .. 10000 */
+} ssrlcv_diff_stats_params; /* 44 bytes */
+typedef struct {
+  uint32_t n, valid, finite, reserved;
+  double sum, sumSq;
+  float min, max;
+  float quantile[8];
+} ssrlcv_diff_stats; /* 72 bytes */
+int ssrlcv_hip_dsm_difference(const ssrlcv_float3* points, uint32_t n, const float* height, const ssrlcv_dsm_frame* frame,
+                              const uint8_t* cells /* may be NULL */, float* diff, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_difference_stats_workspace_bytes(uint32_t n, const ssrlcv_diff_stats_params* params);
+int ssrlcv_hip_difference_stats(const float* values, uint32_t n, const ssrlcv_diff_stats_params* params, ssrlcv_diff_stats* out_dev,
+                                void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

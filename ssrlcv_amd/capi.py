@@ -1004,6 +1004,59 @@ def dsm_ortho(height_d, frame, views, images, max_steps, bias, rule, want_seen=T
     return ortho, seen, which
 
 
+# ------------------------------------------------------------------ surface accuracy
+class DiffStatsParams(ctypes.Structure):
+    """ssrlcv_diff_stats_params: y = x - center (fabsf of it with absolute), quantiles in parts per 10000"""
+    _fields_ = [("center", c_f32), ("absolute", c_u32), ("numQuantiles", c_u32), ("quantile", c_u32 * 8)]
+
+
+class DiffStats(ctypes.Structure):
+    """ssrlcv_diff_stats: the record ssrlcv_hip_difference_stats writes"""
+    _fields_ = [("n", c_u32), ("valid", c_u32), ("finite", c_u32), ("reserved", c_u32), ("sum", ctypes.c_double), ("sumSq", ctypes.c_double),
+                ("min", c_f32), ("max", c_f32), ("quantile", c_f32 * 8)]
+
+
+assert ctypes.sizeof(DiffStatsParams) == 44 and ctypes.sizeof(DiffStats) == 72
+
+
+def dsm_difference(points_d, height_d, frame, cells_d=None, out=None):
+    """The signed height difference of every point of a cloud to a reference height map (ssrlcv_hip_dsm_difference;
+    include/ssrlcv_hip.h "surface accuracy" item 1): to the height of the cell under the point (cells_d None), or to the triangle
+    of the reference's mesh under it (cells_d: disparity_mesh's `cells` of height_d at step 1).  points_d: (n, 3) float32 device
+    tensor.  -> float32 (n,), 0x7FC00000 where there is no difference; into `out` when given.  Asynchronous on the current
+    stream."""
+    p, n = _cloud(points_d)
+    h, w = _disparity_map(height_d)
+    assert (h, w) == (int(frame.h), int(frame.w)), "the map has the frame's grid"
+    if cells_d is not None:
+        assert cells_d.dtype == torch.uint8 and cells_d.is_cuda and cells_d.is_contiguous()
+        assert tuple(cells_d.shape) == (max(h - 1, 0), max(w - 1, 0)), "the cells of the same map at step 1"
+        if cells_d.numel() == 0:
+            cells_d = dev_bytes(1)   # a grid without a cell is still MESH mode (no point is inside): the pointer must not be NULL
+    diff = torch.empty((n,), dtype=torch.float32, device="cuda") if out is None else out
+    assert diff.dtype == torch.float32 and diff.is_cuda and diff.is_contiguous() and diff.numel() >= n
+    check(LIB.ssrlcv_hip_dsm_difference(ptr(p) if n else c_vp(0), c_u32(n), ptr(height_d), ctypes.byref(frame), ptr(cells_d), ptr(diff), stream_ptr()))
+    return diff
+
+
+def difference_stats(values_d, center=0.0, absolute=False, quantiles=(), workspace=None):
+    """Exact statistics of a float32 device tensor of differences (ssrlcv_hip_difference_stats; "surface accuracy" item 2): the
+    valid entries (bits not 0x7FC00000) become y = x - center, |y| with `absolute`; over the finite y: count, float64 sum and sum of
+    squares, min, max and up to 8 quantiles (parts per 10000, each one of the inputs).  -> a DiffStats record on the host.  The
+    workspace is reused if it is large enough.  One synchronisation (the record)."""
+    assert values_d.dtype == torch.float32 and values_d.is_cuda and values_d.is_contiguous()
+    n = values_d.numel()
+    quantiles = [int(q) for q in quantiles]
+    assert len(quantiles) <= 8 and all(0 <= q <= 0xFFFFFFFF for q in quantiles)   # c_u32 would wrap them
+    params = DiffStatsParams(float(center), int(bool(absolute)), len(quantiles), (c_u32 * 8)(*quantiles))
+    need = int(LIB.ssrlcv_hip_difference_stats_workspace_bytes(c_u32(n), ctypes.byref(params)))
+    ws = workspace if workspace is not None and workspace.numel() >= need else dev_bytes(need)
+    out = torch.empty(ctypes.sizeof(DiffStats), dtype=torch.uint8, device="cuda")
+    check(LIB.ssrlcv_hip_difference_stats(ptr(values_d) if n else c_vp(0), c_u32(n), ctypes.byref(params), ptr(out), ptr(ws), c_sz(ws.numel()),
+                                          stream_ptr()))
+    return DiffStats.from_buffer_copy(out.cpu().numpy().tobytes())
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

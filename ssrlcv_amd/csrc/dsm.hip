@@ -34,18 +34,11 @@ constexpr uint32_t kNaN = 0x7FC00000u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kPerThread = 16;  // compact.h: a wave owns a run of 1024 elements, a block 4096
 
-// a . e in the contract's order: ((q.x e.x) + (q.y e.y)) + (q.z e.z)
-__device__ __forceinline__ float along(float qx, float qy, float qz, const float (&e)[3]) { return ((qx * e[0]) + (qy * e[1])) + (qz * e[2]); }
-
 // the cell of a point and its height above the frame's plane; false for a point that is skipped or outside
 __device__ __forceinline__ bool point_cell(const ssrlcv_float3& p, const ssrlcv_dsm_frame& f, uint32_t& cell, float& z) {
-  const uint32_t bx = __float_as_uint(p.x), by = __float_as_uint(p.y), bz = __float_as_uint(p.z);
-  if (!finite_bits(bx) || !finite_bits(by) || !finite_bits(bz)) return false;
-  if (((bx | by | bz) & 0x7FFFFFFFu) == 0u) return false;  // (0, 0, 0), either sign: "no result"
-  const float qx = p.x - f.origin[0], qy = p.y - f.origin[1], qz = p.z - f.origin[2];
-  const float a = along(qx, qy, qz, f.ex), b = along(qx, qy, qz, f.ey);
-  z = along(qx, qy, qz, f.ez);
-  const float fi = floorf(__fdiv_rn(a, f.cell)), fj = floorf(__fdiv_rn(b, f.cell));
+  float u, v;
+  if (!dsm::point_uvz(p, f, u, v, z)) return false;
+  const float fi = floorf(u), fj = floorf(v);
   // on floats, before any conversion: a NaN and a huge value are outside, -0 is cell 0
   if (!(fi >= 0.0f && fi < (float)f.w && fj >= 0.0f && fj < (float)f.h)) return false;
   if (!finite_bits(__float_as_uint(z))) return false;

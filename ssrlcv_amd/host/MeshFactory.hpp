@@ -5,13 +5,16 @@
 // reconstruction from an unorganised cloud and the Octree / Quadtree classes are not mirrored.  The surface of a DENSE STEREO
 // cloud is: its disparity map's grid gives the triangles (DisparityFactory::generateMesh, include/ssrlcv_hip.h "disparity
 // mesh"); setSurface takes them, computeSurfaceNormals, faces and saveMesh work on them, and filterByNeighborDistance keeps
-// them in step with the points it keeps.
+// them in step with the points it keeps.  How far a cloud lies from a reference surface -- upstream's
+// calculatePerPointDifference / calculateAverageDifference -- is measured against a height map (setReferenceSurface).
 //
 // Memory state: `points` goes to the gpu for a call and comes back to its origin state; Unitys this class creates
 // (filtered points, normals, mean distances) are left in the state the points were in.
 #pragma once
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 #include "GridMesh.hpp"
@@ -383,6 +386,121 @@ class MeshFactory {
     std::memcpy(values.get(), kept.data(), kept.size());
     colors = ptr::value<Unity<unsigned char>>(values, (unsigned long)kept.size(), cpu, true);
   }
+
+  // ---- surface accuracy (include/ssrlcv_hip.h "surface accuracy"): how far a cloud lies from a reference surface -- upstream's
+  // calculatePerPointDifference / calculateAverageDifference.  The reference is a height map on a ground grid, triangulated as
+  // DisparityFactory::generateMesh(height, 1, maxJump) triangulates it; differences are measured along the frame's ez.
+
+  struct AccuracyReport {
+    unsigned long n = 0;  // the points
+    double coverage = 0, bias = 0, nmad = 0, mean = 0, rms = 0, le68 = 0, le90 = 0, le95 = 0, min = 0, max = 0;  // NaN where there is no value
+  };
+
+  // the surface the differences are taken to: its own copy of the map, in state gpu, and the cells of its mesh at step 1
+  void setReferenceSurface(ptr::value<Unity<float>> height, const ssrlcv_dsm_frame& frame, float maxJump = std::numeric_limits<float>::infinity()) {
+    const unsigned long cells = (unsigned long)frame.w * frame.h;
+    hasReference = false;
+    if (height == nullptr || cells == 0 || height->size() != cells || !(maxJump >= 0.0f)) {
+      logger.err << "MeshFactory::setReferenceSurface: the map has frame.w frame.h entries and maxJump is not negative";
+      return;
+    }
+    referenceHeight = copyToGpu(height);
+    referenceFrame = frame;
+    const unsigned long meshCells = (unsigned long)(frame.w - 1) * (frame.h - 1);
+    referenceCells = ptr::value<Unity<unsigned char>>(nullptr, meshCells ? meshCells : 1, gpu);  // never NULL: NULL would mean CELL mode
+    ssrlcv_mesh_params params = {1u, maxJump};
+    const size_t wsb = ssrlcv_hip_disparity_mesh_workspace_bytes(frame.w, frame.h, &params);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::device<uint32_t> vertexIndex(cells), count(1);
+    HipSafeCall(ssrlcv_hip_disparity_mesh(referenceHeight->device.get(), frame.w, frame.h, &params, vertexIndex.get(), referenceCells->device.get(),
+                                          count.get(), ws.get(), wsb, nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    hasReference = true;
+  }
+
+  // the signed difference of every point of `cloud` to the reference surface along planeNormal, which must be the reference
+  // frame's ez (after normalising both in float, a dot product below 0.999999f is refused; another direction is out of scope);
+  // in state gpu, 0x7FC00000 where there is no difference; null when refused.  The cloud is left in the state it came in.
+  ptr::value<Unity<float>> calculatePerPointDifference(ptr::value<Unity<float3>> cloud, float3 planeNormal) {
+    if (!hasReference || cloud == nullptr || cloud->size() == 0 || cloud->size() > 0xFFFFFFFFul) {
+      logger.err << "MeshFactory::calculatePerPointDifference: needs a reference surface (setReferenceSurface) and points";
+      return ptr::value<Unity<float>>();
+    }
+    const float* ez = referenceFrame.ez;
+    const float ln = std::sqrt(planeNormal.x * planeNormal.x + planeNormal.y * planeNormal.y + planeNormal.z * planeNormal.z);
+    const float le = std::sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
+    const float dot = (planeNormal.x / ln) * (ez[0] / le) + (planeNormal.y / ln) * (ez[1] / le) + (planeNormal.z / ln) * (ez[2] / le);
+    if (!(dot >= 0.999999f)) {  // false for a NaN: a zero vector
+      logger.err.printf("MeshFactory::calculatePerPointDifference: planeNormal is not the reference frame's ez (dot %g)", (double)dot);
+      return ptr::value<Unity<float>>();
+    }
+    MemoryState origin = cloud->getMemoryState();
+    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
+    ptr::value<Unity<float>> diff(nullptr, cloud->size(), gpu);
+    HipSafeCall(ssrlcv_hip_dsm_difference((const ssrlcv_float3*)cloud->device.get(), (uint32_t)cloud->size(), referenceHeight->device.get(),
+                                          &referenceFrame, referenceCells->device.get(), diff->device.get(), nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    if (origin == cpu) cloud->setMemoryState(cpu);
+    return diff;
+  }
+
+  // the mean of the finite differences, in host float64 from the device's fixed-shape sums; NaN when there is none or when refused
+  double calculateAverageDifference(ptr::value<Unity<float3>> cloud, float3 planeNormal) {
+    auto diff = calculatePerPointDifference(cloud, planeNormal);
+    if (diff == nullptr) return std::numeric_limits<double>::quiet_NaN();
+    const ssrlcv_diff_stats s = differenceStats(diff, 0.0f, false, {});
+    return s.finite ? s.sum / (double)s.finite : std::numeric_limits<double>::quiet_NaN();
+  }
+
+  // ssrlcv_hip_difference_stats of a Unity of differences -> the record on the host; the values come back to the state they came in
+  static ssrlcv_diff_stats differenceStats(ptr::value<Unity<float>> values, float center, bool absolute, const std::vector<uint32_t>& quantiles) {
+    ssrlcv_diff_stats_params params = {center, absolute ? 1u : 0u, (uint32_t)quantiles.size(), {0, 0, 0, 0, 0, 0, 0, 0}};
+    for (size_t k = 0; k < quantiles.size() && k < 8; ++k) params.quantile[k] = quantiles[k];
+    MemoryState origin = values->getMemoryState();
+    if (origin != gpu) values->setMemoryState(gpu);
+    const size_t wsb = ssrlcv_hip_difference_stats_workspace_bytes((uint32_t)values->size(), &params);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::device<ssrlcv_diff_stats> record(1);
+    HipSafeCall(ssrlcv_hip_difference_stats(values->device.get(), (uint32_t)values->size(), &params, record.get(), ws.get(), wsb, nullptr));
+    ssrlcv_diff_stats host;
+    HipSafeCall(ssrlcv_hip_memcpy(&host, record.get(), sizeof host, 1));  // synchronises: the workspace may go out of scope
+    if (origin != gpu) values->setMemoryState(origin);
+    return host;
+  }
+
+  // pipeline.surface_accuracy's fields for `cloud` against the reference surface: three statistics calls on the differences
+  AccuracyReport accuracyReport(ptr::value<Unity<float3>> cloud, ptr::value<Unity<float>>* differences = nullptr) {
+    AccuracyReport r;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    r.coverage = r.bias = r.nmad = r.mean = r.rms = r.le68 = r.le90 = r.le95 = r.min = r.max = nan;
+    if (!hasReference) {
+      logger.err << "MeshFactory::accuracyReport: needs a reference surface (setReferenceSurface)";
+      return r;
+    }
+    auto diff = calculatePerPointDifference(cloud, {referenceFrame.ez[0], referenceFrame.ez[1], referenceFrame.ez[2]});
+    if (diff == nullptr) return r;
+    if (differences) *differences = diff;
+    const ssrlcv_diff_stats s = differenceStats(diff, 0.0f, false, {5000u});
+    r.n = s.n;
+    r.coverage = (double)s.finite / (double)s.n;
+    if (s.finite == 0) return r;
+    r.bias = s.quantile[0];
+    r.mean = s.sum / (double)s.finite;
+    r.rms = std::sqrt(s.sumSq / (double)s.finite);
+    r.min = s.min;
+    r.max = s.max;
+    r.nmad = 1.4826 * (double)differenceStats(diff, s.quantile[0], true, {5000u}).quantile[0];
+    const ssrlcv_diff_stats a = differenceStats(diff, 0.0f, true, {6827u, 9000u, 9500u});
+    r.le68 = a.quantile[0];
+    r.le90 = a.quantile[1];
+    r.le95 = a.quantile[2];
+    return r;
+  }
+
+  ptr::value<Unity<float>> referenceHeight;           // set by setReferenceSurface, in state gpu
+  ptr::value<Unity<unsigned char>> referenceCells;
+  ssrlcv_dsm_frame referenceFrame = {};
+  bool hasReference = false;
 
   // ASCII PLY of the points (and their normals once computed) as <dir><filename>.ply
   void savePoints(std::string filename, std::string dir = "out/") {

@@ -454,6 +454,63 @@ def surface_colors(ortho, height):
     return ortho[height.view(torch.int32) != capi.STEREO_INVALID_BITS]
 
 
+def surface_difference(points, reference, frame, mesh=True, max_jump=None):
+    """The signed height difference of every point of a cloud ((n, 3) float32 device tensor) to a reference height map (float32
+    (h, w) device tensor in `frame`; include/ssrlcv_hip.h "surface accuracy" item 1), positive above the reference along the
+    frame's ez.  With `mesh` the reference is the triangle mesh of the map at step 1, cut where two cells differ by more than
+    max_jump (None: nowhere); without, the height of the cell under the point.  -> float32 (n,) device tensor, 0x7FC00000 where
+    there is no difference."""
+    cells = capi.disparity_mesh(reference, 1, float("inf") if max_jump is None else max_jump)[1] if mesh else None
+    return capi.dsm_difference(points, reference, frame, cells)
+
+
+def difference_stats(diff, center=0.0, absolute=False, quantiles=(5000,)):
+    """Exact statistics of a tensor of differences ("surface accuracy" item 2): the valid entries become y = x - center (|y| with
+    `absolute`), and over the finite y -> dict(n, valid, finite, sum, sum_sq, min, max, quantiles: one float a quantile, in parts
+    per 10000, each one of the inputs; mean and rms in host float64 from sum, sum_sq and finite, nan when finite is 0)."""
+    quantiles = tuple(quantiles)
+    rec = capi.difference_stats(diff, center, absolute, quantiles)
+    m = int(rec.finite)
+    mean = float(np.float64(rec.sum) / np.float64(m)) if m else float("nan")
+    rms = float(np.sqrt(np.float64(rec.sumSq) / np.float64(m))) if m else float("nan")
+    return {"n": int(rec.n), "valid": int(rec.valid), "finite": m, "sum": float(rec.sum), "sum_sq": float(rec.sumSq), "min": float(rec.min),
+            "max": float(rec.max), "quantiles": [float(rec.quantile[k]) for k in range(len(quantiles))], "mean": mean, "rms": rms}
+
+
+def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=False, **kw):
+    """How far a surface lies from a reference height map (`reference` in `frame`): `subject` is a cloud ((n, 3) float32 device
+    tensor) or a height map (float32 (h, w): any tensor when subject_frame is given, one of the grid of `frame` without), which
+    goes through capi.dsm_points of its own frame.  kw is surface_difference's (mesh, max_jump).  Three statistics calls on the differences: the signed ones with
+    the median; the absolute ones about the median; the absolute ones with three quantiles.
+    -> dict(n; coverage = finite / n; bias: the median; nmad = 1.4826 x the median absolute deviation about it, host float64;
+    mean, rms; le68, le90, le95: the 6827 / 9000 / 9500 quantiles of |diff|; min, max; diff: the differences).  With want_map and a
+    height-map subject also error_map: the differences scattered back into the subject's grid by its validity mask, a map in
+    the form of every map here."""
+    sub_frame = frame if subject_frame is None else subject_frame
+    is_map = subject_frame is not None or (subject.dim() == 2 and tuple(subject.shape) == (int(frame.h), int(frame.w)))
+    if want_map and not is_map:
+        raise ValueError("want_map needs a height-map subject")
+    points = capi.dsm_points(subject, sub_frame)[0] if is_map else subject
+    diff = surface_difference(points, reference, frame, **kw)
+    signed = difference_stats(diff, quantiles=(5000,))
+    nan = float("nan")
+    if signed["finite"]:
+        bias = signed["quantiles"][0]
+        mad = difference_stats(diff, center=bias, absolute=True, quantiles=(5000,))["quantiles"][0]
+        le = difference_stats(diff, absolute=True, quantiles=(6827, 9000, 9500))["quantiles"]
+    else:
+        bias, mad, le = nan, nan, [nan, nan, nan]
+    n = signed["n"]
+    out = {"n": n, "coverage": signed["finite"] / n if n else nan, "bias": bias, "nmad": float(np.float64(1.4826) * np.float64(mad)),
+           "mean": signed["mean"], "rms": signed["rms"], "le68": le[0], "le90": le[1], "le95": le[2], "min": signed["min"], "max": signed["max"],
+           "diff": diff}
+    if want_map:
+        error_map = torch.full(subject.shape, capi.STEREO_INVALID_BITS, dtype=torch.int32, device=subject.device)
+        error_map[subject.view(torch.int32) != capi.STEREO_INVALID_BITS] = diff.view(torch.int32)   # dsm_points numbers the valid cells in raster order
+        out["error_map"] = error_map.view(torch.float32)
+    return out
+
+
 def exchange_features(local, num_images):
     world, _ = _world()
     if world == 1:
