@@ -54,7 +54,9 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      disparity post-filters: disparity_components, stereo_filter_speckles (+ their workspace queries), stereo_filter_median;
  *      hole filling: stereo_fill_holes (+ its workspace query);
  *      disparity mesh: disparity_mesh, mesh_select, mesh_triangles (+ their workspace queries), mesh_normals;
- *      surface accuracy: dsm_difference, difference_stats (+ its workspace query) */
+ *      surface accuracy: dsm_difference, difference_stats (+ its workspace query);
+ *      surface registration: register_terms (+ its workspace query), transform_points, register_step_host,
+ *      register_compose_host */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1254,7 +1256,8 @@ int ssrlcv_hip_dsm_ortho(const float* height, const ssrlcv_dsm_frame* frame, con
  * rank, all quantiles in the same passes, equal prefixes sharing a histogram.  Counts, min and max are integer atomics, one a
  * block.  Integer atomics commute and the sums have a fixed shape: the record is bit-equal run to run and to the restatement.
  * Out of scope, not built: differences along a direction other than the frame's ez; ray casts against unorganised meshes;
- * registration or a shift search; float atomics; weighted statistics. */
+ * a shift search; float atomics; weighted statistics.  Registration -- a cloud that lies off in x / y shows every slope of the
+ * terrain as height error -- is the next section, "surface registration". */
 typedef struct {
   float center;          /* finite: subtracted from every valid entry */
   uint32_t absolute;     /* 0 or 1: fabsf of the difference to center */
@@ -1272,6 +1275,96 @@ int ssrlcv_hip_dsm_difference(const ssrlcv_float3* points, uint32_t n, const flo
 size_t ssrlcv_hip_difference_stats_workspace_bytes(uint32_t n, const ssrlcv_diff_stats_params* params);
 int ssrlcv_hip_difference_stats(const float* values, uint32_t n, const ssrlcv_diff_stats_params* params, ssrlcv_diff_stats* out_dev,
                                 void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- surface registration: the point-to-plane alignment of a cloud to the reference surface of "surface accuracy" -- what
+ * PointCloudFactory's scalePointCloud / translatePointCloud / rotatePointCloud do by hand upstream before
+ * calculateAverageDifference.  One GPU call accumulates the normal equations of a Gauss-Newton step over seven unknowns --
+ * translation, rotation, scale --, two host calls solve and compose the step, one GPU call applies a pose to a cloud; the binders
+ * iterate.  Fixed-order float32 per point, nothing contracted, the divisions and the square root IEEE; products that are exact in
+ * float64; float64 sums in the fixed shape of "surface accuracy"; integer atomics only: csrc/register.hip is held to a numpy
+ * restatement bit for bit (tests/register_ref.py, tests/test_gpu_register.py).
+ *   pose        ssrlcv_register_pose: p' = M p + T, m the 3 x 4 matrix [M | T] row-major; pivot: the point steps rotate and scale
+ *               about.  The pivot only conditions the system: it changes no p'.
+ *   1 terms     ssrlcv_hip_register_terms.  The reference is MESH mode only: `cells` is required, the bytes of
+ *               ssrlcv_hip_disparity_mesh of `height` at step 1 with its maxJump cuts.  Per point p of index t, in float32 in
+ *               exactly this order:
+ *     skip        p is skipped by the rasterize rule ("surface model" item 1): a component that is not finite, or (0, 0, 0) with
+ *                 either sign of zero.
+ *     pose        for the rows r = 0, 1, 2:  p'.r = (((m[4r] p.x) + (m[4r+1] p.y)) + (m[4r+2] p.z)) + m[4r+3]
+ *     lookup      p' goes through "surface accuracy" item 1, MESH, word for word, its own skip rules included (csrc/mesh_lookup.h
+ *                 is the one definition of both): d, or no difference.  `inside` counts the points that have a d.
+ *     slopes      of the chosen triangle in s and t, from the corner heights MESH mode read:
+ *                   diagonal a-d   T0: rs = zd - zc, rt = zc - za        T1: rs = zb - za, rt = zd - zb
+ *                   diagonal b-c   T0: rs = zb - za, rt = zc - za        T1: rs = zd - zc, rt = zd - zb
+ *                 gu = rs / cell, gv = rt / cell.
+ *     gradient    of d in world coordinates, for any affine frame:  G.k = (ez.k - (gu ex.k)) - (gv ey.k),
+ *                 len = sqrtf(((G.x G.x) + (G.y G.y)) + (G.z G.z)),  N = G / len component by component,  e = d / len.
+ *     row         L = p' - pivot;  J0..2 = N;  J3..5 = L x N as (L.y N.z) - (L.z N.y), (L.z N.x) - (L.x N.z),
+ *                 (L.x N.y) - (L.y N.x);  J6 = ((L.x N.x) + (L.y N.y)) + (L.z N.z).
+ *     used        iff d exists, fabsf(d - center) <= gate (one subtraction; false for a NaN) and J0..6 and e are all finite.
+ *                 `used` counts these points.
+ *     sums        over the used points, of exact float64 products: jtj = sum (double)Ji (double)Jj for rows i = 0..6 and within
+ *                 a row j = i..6; jte = sum (double)Ji (double)e; ee = sum (double)e (double)e.  Unused and padding entries add
+ *                 +0.0.  Each of the 36 sums has the shape of `sum` in "surface accuracy": tiles of 4096, lane l of 256 adds
+ *                 entries l + 256 r, r = 0 .. 15, in that order from +0.0, the lanes fold by acc[l] += acc[l + half], half = 128
+ *                 .. 1, and the tile sums are reduced by the same shape again until one is left.
+ *     record      ssrlcv_register_terms in DEVICE memory: n, inside, used, reserved = 0, jtj[28], jte[7], ee.  The empty record
+ *                 (n = 0): zeros and +0.0 sums.
+ *   2 transform ssrlcv_hip_transform_points: out[t] = p' by the row expression of item 1; a point skipped by item 1's rule is
+ *               copied bit for bit, so the "no result" point stays one.  out == points is legal.  Every entry of out[n] is
+ *               written and nothing behind it.
+ *   3 step      ssrlcv_register_step_host (host only, in double, no device): dofMask bits 0..6 = tx, ty, tz, rx, ry, rz, scale.
+ *               H = jtj with H_ii <- H_ii (1 + lambda); H delta = -jte over the masked unknowns by Cholesky in its root-free form
+ *               L D L^T (one masked unknown is one division); the unmasked entries of delta[7] are 0.  SSRLCV_ERR_UNSUPPORTED,
+ *               not a wrong answer, when used = 0, when a pivot D_k is not above 2^-30 times the diagonal entry H_kk it started
+ *               as, or when the solution is not finite.  SSRLCV_ERR_INVALID_ARG for a NULL, a mask of 0 or above 0x7F, a lambda
+ *               that is negative or not finite.  delta is untouched on error.
+ *   4 compose   ssrlcv_register_compose_host (host only, in double): the step is
+ *                 p'' = pivot + (1 + ds) R(dw) (p' - pivot) + dt
+ *               with R the exact rotation of the rotation vector dw (Rodrigues; below |dw| = 2^-26 the limits 1 and 1/2 of its two
+ *               coefficients), so M <- (1 + ds) R M and T <- pivot + (1 + ds) R (T - pivot) + dt, computed in double and rounded
+ *               once to float; the pivot is carried over.  out may be pose.  SSRLCV_ERR_INVALID_ARG for a NULL, a refused pose or
+ *               a delta that is not finite; SSRLCV_ERR_UNSUPPORTED if an entry of the result is not a finite float; `out` is
+ *               untouched on error.
+ * Refusals of the device calls, decided on the host before any launch, the parameters before the sizes before the buffers:
+ *   terms       SSRLCV_ERR_INVALID_ARG for a NULL or refused frame (the rules of "surface model") or w h >= 2^31; then for a
+ *               NULL pose or params, an entry of m or pivot that is not finite, a center that is not finite, a gate that is
+ *               negative or a NaN (+inf is legal); then SSRLCV_ERR_UNSUPPORTED for w or h above 2^24; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL out_dev; n = 0 then writes the empty record and is SSRLCV_OK; then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL points, height, cells or workspace; then SSRLCV_ERR_WORKSPACE.  A grid with a
+ *               side below 2 is legal: no point is inside.
+ *   transform   SSRLCV_ERR_INVALID_ARG for a NULL or refused pose; n = 0 is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a
+ *               NULL points or out, or an out that overlaps points without being equal to it.
+ * Workspace of terms (host only; computed in size_t), a256 as in "disparity mesh", T(n) = ceil(n / 4096):
+ *     a256(288 T(n)) + a256(288 T(T(n)))
+ *   the 36 partial sums of two levels.  It may hold anything on entry.  The transform needs none.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  The counts are INTEGER atomics, one
+ * a block; the sums have a fixed shape; there are no float atomics: the record is bit-equal run to run and to the restatement.
+ * The transform uses no atomics.
+ * Out of scope, not built: a coarse shift search over many cells (the caller passes an initial pose); robust weights other than
+ * the gate; cloud-to-cloud ICP; pushbroom geometry; re-running stereo. */
+typedef struct {
+  float m[12];    /* [M | T], 3 x 4 row-major: p' = M p + T */
+  float pivot[3]; /* the point steps rotate and scale about */
+} ssrlcv_register_pose; /* 60 bytes */
+typedef struct {
+  float center; /* finite: a point is used iff fabsf(d - center) <= gate */
+  float gate;   /* >= 0; +inf: every point that has a difference */
+} ssrlcv_register_params; /* 8 bytes */
+typedef struct {
+  uint32_t n, inside, used, reserved;
+  double jtj[28]; /* rows i = 0..6, within a row j = i..6 */
+  double jte[7];
+  double ee;
+} ssrlcv_register_terms; /* 304 bytes */
+size_t ssrlcv_hip_register_terms_workspace_bytes(uint32_t n);
+int ssrlcv_hip_register_terms(const ssrlcv_float3* points, uint32_t n, const ssrlcv_register_pose* pose, const float* height,
+                              const ssrlcv_dsm_frame* frame, const uint8_t* cells, const ssrlcv_register_params* params,
+                              ssrlcv_register_terms* out_dev, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+int ssrlcv_hip_transform_points(const ssrlcv_float3* points, uint32_t n, const ssrlcv_register_pose* pose, ssrlcv_float3* out,
+                                ssrlcv_stream_t stream);
+int ssrlcv_register_step_host(const ssrlcv_register_terms* record, uint32_t dofMask, double lambda, double* delta /* [7] */); /* host only */
+int ssrlcv_register_compose_host(const ssrlcv_register_pose* pose, const double* delta /* [7] */, ssrlcv_register_pose* out); /* host only */
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

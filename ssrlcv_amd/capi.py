@@ -1057,6 +1057,89 @@ def difference_stats(values_d, center=0.0, absolute=False, quantiles=(), workspa
     return DiffStats.from_buffer_copy(out.cpu().numpy().tobytes())
 
 
+# ------------------------------------------------------------------ surface registration
+class RegisterPose(ctypes.Structure):
+    """ssrlcv_register_pose: p' = M p + T, m = [M | T] 3 x 4 row-major; pivot: the point steps rotate and scale about"""
+    _fields_ = [("m", c_f32 * 12), ("pivot", c_f32 * 3)]
+
+    @classmethod
+    def make(cls, matrix=None, translation=(0, 0, 0), pivot=(0, 0, 0)):
+        m = np.zeros((3, 4), np.float32)
+        m[:, :3] = np.eye(3) if matrix is None else np.asarray(matrix, np.float64).reshape(3, 3)
+        m[:, 3] = np.asarray(translation, np.float64).reshape(3)
+        return cls((c_f32 * 12)(*m.reshape(12).tolist()), (c_f32 * 3)(*[float(np.float32(x)) for x in pivot]))
+
+
+class RegisterParams(ctypes.Structure):
+    """ssrlcv_register_params: a point is used iff fabsf(d - center) <= gate"""
+    _fields_ = [("center", c_f32), ("gate", c_f32)]
+
+
+class RegisterTerms(ctypes.Structure):
+    """ssrlcv_register_terms: the record ssrlcv_hip_register_terms writes"""
+    _fields_ = [("n", c_u32), ("inside", c_u32), ("used", c_u32), ("reserved", c_u32), ("jtj", ctypes.c_double * 28), ("jte", ctypes.c_double * 7),
+                ("ee", ctypes.c_double)]
+
+
+assert ctypes.sizeof(RegisterPose) == 60 and ctypes.sizeof(RegisterParams) == 8 and ctypes.sizeof(RegisterTerms) == 304
+
+REGISTER_SHIFT, REGISTER_RIGID, REGISTER_SIMILARITY = 0x07, 0x3F, 0x7F   # register_step's dof masks: bits tx, ty, tz, rx, ry, rz, scale
+
+
+def register_terms(points_d, pose, height_d, frame, cells_d, center=0.0, gate=float("inf"), workspace=None):
+    """The normal equations of one point-to-plane step of a cloud under `pose` towards a reference height map
+    (ssrlcv_hip_register_terms; include/ssrlcv_hip.h "surface registration" item 1).  points_d: (n, 3) float32 device tensor;
+    cells_d: disparity_mesh's `cells` of height_d at step 1 (required: the reference is its mesh); a point takes part iff it has
+    a difference d to the mesh and |d - center| <= gate.  -> a RegisterTerms record on the host.  The workspace is reused if it
+    is large enough.  One synchronisation (the record)."""
+    p, n = _cloud(points_d)
+    h, w = _disparity_map(height_d)
+    assert (h, w) == (int(frame.h), int(frame.w)), "the map has the frame's grid"
+    assert cells_d is not None and cells_d.dtype == torch.uint8 and cells_d.is_cuda and cells_d.is_contiguous()
+    assert tuple(cells_d.shape) == (max(h - 1, 0), max(w - 1, 0)), "the cells of the same map at step 1"
+    if cells_d.numel() == 0:
+        cells_d = dev_bytes(1)   # a grid without a cell: no point is inside, and the pointer must not be NULL
+    params = RegisterParams(float(center), float(gate))
+    need = int(LIB.ssrlcv_hip_register_terms_workspace_bytes(c_u32(n)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(max(need, 1))
+    out = torch.empty(ctypes.sizeof(RegisterTerms), dtype=torch.uint8, device="cuda")
+    check(LIB.ssrlcv_hip_register_terms(ptr(p) if n else c_vp(0), c_u32(n), ctypes.byref(pose), ptr(height_d), ctypes.byref(frame), ptr(cells_d),
+                                        ctypes.byref(params), ptr(out), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return RegisterTerms.from_buffer_copy(out.cpu().numpy().tobytes())
+
+
+def transform_points(points_d, pose, out=None):
+    """A pose applied to a cloud (ssrlcv_hip_transform_points; "surface registration" item 2): p' = M p + T; a "no result" point
+    ((0, 0, 0) or a non-finite component) is copied bit for bit.  -> float32 (n, 3); into `out` when given, which may be
+    points_d itself.  Asynchronous on the current stream."""
+    p, n = _cloud(points_d)
+    res = torch.empty((n, 3), dtype=torch.float32, device="cuda") if out is None else out
+    assert res.dtype == torch.float32 and res.is_cuda and res.is_contiguous() and res.numel() >= 3 * n
+    check(LIB.ssrlcv_hip_transform_points(ptr(p) if n else c_vp(0), c_u32(n), ctypes.byref(pose), ptr(res) if n else c_vp(0), stream_ptr()))
+    return res
+
+
+def register_step(terms, dof_mask=REGISTER_RIGID, damping=0.0):
+    """ssrlcv_register_step_host (host arithmetic: needs no GPU): H delta = -jte over the masked unknowns, H = jtj with its
+    diagonal times (1 + damping).  -> delta, float64 (7,) (tx, ty, tz, rx, ry, rz, scale; 0 where unmasked), or None where the
+    system has no answer (no point used, or a direction the points do not hold)."""
+    delta = (ctypes.c_double * 7)()
+    rc = LIB.ssrlcv_register_step_host(ctypes.byref(terms), c_u32(int(dof_mask)), ctypes.c_double(float(damping)), delta)
+    if rc == -4:   # SSRLCV_ERR_UNSUPPORTED
+        return None
+    check(rc)
+    return np.array(list(delta), np.float64)
+
+
+def register_compose(pose, delta):
+    """ssrlcv_register_compose_host (host arithmetic): the pose after the step p'' = pivot + (1 + ds) R(dw) (p' - pivot) + dt.
+    -> a new RegisterPose with the same pivot."""
+    d = (ctypes.c_double * 7)(*[float(x) for x in delta])
+    out = RegisterPose()
+    check(LIB.ssrlcv_register_compose_host(ctypes.byref(pose), d, ctypes.byref(out)))
+    return out
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -4,7 +4,8 @@
 //
 //   k_dsm_difference  a thread per point: the point in the frame by the expression of the surface model (dsm_frame.h), then the
 //                     reference's height under it -- the cell's own height (CELL), or the plane of the triangle of the reference's
-//                     mesh it lies in, from the `cells` bytes of ssrlcv_hip_disparity_mesh (MESH) -- in fixed-order float32
+//                     mesh it lies in, from the `cells` bytes of ssrlcv_hip_disparity_mesh (MESH: mesh_lookup.h, the definition
+//                     register.hip shares) -- in fixed-order float32
 //   k_stats_tiles     a block walks tiles of 4096 values: the float64 sums of y and y y in the contract's shape (lane l adds entries
 //                     l + 256 r in order, the lanes fold by halves), one partial a tile; the counts, the least and the greatest key
 //                     in registers and one integer atomic each a block; the histogram of the keys' first digit in LDS, flushed by
@@ -24,6 +25,7 @@
 #include "align256.h"
 #include "device_math.h"
 #include "dsm_frame.h"
+#include "mesh_lookup.h"
 #include "order_key.h"
 
 namespace {
@@ -61,39 +63,9 @@ __global__ __launch_bounds__(256) void k_dsm_difference(const ssrlcv_float3* __r
         const float r = height[(uint32_t)fj * f.w + (uint32_t)fi];  // below w h < 2^31
         if (__float_as_uint(r) != kNaN && finite_f(r)) out = __float_as_uint(z - r);
       }
-    } else if (f.w >= 2u && f.h >= 2u) {  // MESH: the mesh's vertices sit at cell centres
-      const float uu = u - 0.5f, vv = v - 0.5f;
-      const float fi = floorf(uu), fj = floorf(vv);
-      if (fi >= 0.0f && fi < (float)(f.w - 1u) && fj >= 0.0f && fj < (float)(f.h - 1u)) {
-        const uint32_t i = (uint32_t)fi, j = (uint32_t)fj;  // i <= w - 2, j <= h - 2: all four corners are cells of the map
-        const float s = uu - fi, tt = vv - fj;
-        const uint32_t byte = cells[j * (f.w - 1u) + i];
-        const float* corner = height + (j * f.w + i);
-        const float za = corner[0], zd = corner[f.w + 1u];  // a corner no emitted triangle names may be invalid: it is not used
-        float r;
-        bool emitted;
-        if (!(byte & 4u)) {  // diagonal a-d: T0 = (a, c, d), T1 = (a, d, b)
-          if (tt >= s) {
-            const float zc = corner[f.w];
-            emitted = byte & 1u;
-            r = za + ((tt * (zc - za)) + (s * (zd - zc)));
-          } else {
-            const float zb = corner[1];
-            emitted = byte & 2u;
-            r = za + ((s * (zb - za)) + (tt * (zd - zb)));
-          }
-        } else {  // diagonal b-c: T0 = (a, c, b), T1 = (b, c, d)
-          const float zb = corner[1], zc = corner[f.w];
-          if (s + tt <= 1.0f) {
-            emitted = byte & 1u;
-            r = za + ((s * (zb - za)) + (tt * (zc - za)));
-          } else {
-            emitted = byte & 2u;
-            r = zd + (((1.0f - s) * (zc - zd)) + ((1.0f - tt) * (zb - zd)));
-          }
-        }
-        if (emitted && finite_f(r)) out = __float_as_uint(z - r);
-      }
+    } else {  // MESH: the triangle of the reference's mesh under the point (mesh_lookup.h)
+      float d, rs, rt;
+      if (dsm::mesh_difference(u, v, z, height, cells, f.w, f.h, d, rs, rt)) out = __float_as_uint(d);
     }
   }
   diff[t] = out;

@@ -1,6 +1,6 @@
 // ssrlcv_amd/csrc/dsm_frame.h -- what the calls on a ground grid share on the host (include/ssrlcv_hip.h "surface model" frame and
-// refusals): dsm.hip, ortho.hip and accuracy.hip refuse the same frames and the same sizes, and dsm.hip and accuracy.hip place a
-// point in the frame with the same expression.
+// refusals): dsm.hip, ortho.hip, accuracy.hip and register.hip refuse the same frames and the same sizes, and dsm.hip,
+// accuracy.hip and register.hip place a point in the frame with the same expression.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

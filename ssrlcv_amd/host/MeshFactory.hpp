@@ -11,6 +11,7 @@
 // Memory state: `points` goes to the gpu for a call and comes back to its origin state; Unitys this class creates
 // (filtered points, normals, mean distances) are left in the state the points were in.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -495,6 +496,112 @@ class MeshFactory {
     r.le90 = a.quantile[1];
     r.le95 = a.quantile[2];
     return r;
+  }
+
+  // ---- surface registration (include/ssrlcv_hip.h "surface registration"): the pose that aligns a cloud to the reference surface
+  // by point-to-plane steps -- pipeline.surface_register's loop, call for call.  dofMask bits 0..6 = tx, ty, tz, rx, ry, rz, scale
+  // (0x07 a shift, 0x3F rigid, 0x7F a similarity); gateFactor > 0: only points within gateFactor x NMAD of the median difference
+  // take part, otherwise all that have one.  The cloud is not moved (PointCloudFactory::transformPointCloud does that) and is
+  // left in the state it came in.
+  struct RegistrationStep {
+    uint32_t used = 0, inside = 0;
+    double rms = 0, center = 0, gate = 0;
+    double delta[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool stepped = false;  // false: the step was refused and delta holds nothing
+  };
+  struct Registration {
+    ssrlcv_register_pose pose = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, {0, 0, 0}};
+    bool converged = false;
+    std::vector<RegistrationStep> history;
+  };
+
+  Registration registerToReference(ptr::value<Unity<float3>> cloud, uint32_t dofMask = 0x3Fu, unsigned iterations = 8, float gateFactor = 3.0f,
+                                   double damping = 0.0) {
+    Registration reg;
+    if (!hasReference || cloud == nullptr || cloud->size() == 0 || cloud->size() > 0xFFFFFFFFul) {
+      logger.err << "MeshFactory::registerToReference: needs a reference surface (setReferenceSurface) and points";
+      return reg;
+    }
+    const uint32_t n = (uint32_t)cloud->size();
+    MemoryState origin = cloud->getMemoryState();
+    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
+    const ssrlcv_float3* points = (const ssrlcv_float3*)cloud->device.get();
+    ptr::value<Unity<float3>> posed(nullptr, n, gpu);
+    ptr::value<Unity<float>> diff(nullptr, n, gpu);
+    auto difference = [&]() {
+      HipSafeCall(ssrlcv_hip_transform_points(points, n, &reg.pose, (ssrlcv_float3*)posed->device.get(), nullptr));
+      HipSafeCall(ssrlcv_hip_dsm_difference((const ssrlcv_float3*)posed->device.get(), n, referenceHeight->device.get(), &referenceFrame,
+                                            referenceCells->device.get(), diff->device.get(), nullptr));
+      HipSafeCall(ssrlcv_hip_device_synchronize());
+    };
+    // the pivot: the float64 mean of the points that have a difference under the initial pose; the corners of the cloud's box
+    difference();
+    std::vector<float3> posedHost(n), cloudHost(n);
+    std::vector<uint32_t> diffBits(n);
+    HipSafeCall(ssrlcv_hip_memcpy(posedHost.data(), posed->device.get(), (size_t)n * sizeof(float3), 1));
+    HipSafeCall(ssrlcv_hip_memcpy(cloudHost.data(), points, (size_t)n * sizeof(float3), 1));
+    HipSafeCall(ssrlcv_hip_memcpy(diffBits.data(), diff->device.get(), (size_t)n * sizeof(float), 1));
+    double sum[3] = {0, 0, 0}, lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    unsigned long has = 0, kept = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      const float c[3] = {cloudHost[k].x, cloudHost[k].y, cloudHost[k].z};
+      if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || (c[0] == 0.0f && c[1] == 0.0f && c[2] == 0.0f)) continue;
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = kept ? std::min(lo[a], (double)c[a]) : (double)c[a];
+        hi[a] = kept ? std::max(hi[a], (double)c[a]) : (double)c[a];
+      }
+      ++kept;
+      if (diffBits[k] == 0x7FC00000u) continue;
+      sum[0] += (double)posedHost[k].x, sum[1] += (double)posedHost[k].y, sum[2] += (double)posedHost[k].z;
+      ++has;
+    }
+    for (int a = 0; a < 3; ++a) reg.pose.pivot[a] = has ? (float)(sum[a] / (double)has) : 0.0f;
+    const size_t wsb = ssrlcv_hip_register_terms_workspace_bytes(n);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::device<ssrlcv_register_terms> record(1);
+    const double inf = std::numeric_limits<double>::infinity();
+    for (unsigned it = 0; it < iterations; ++it) {
+      ssrlcv_register_params params = {0.0f, (float)inf};
+      if (gateFactor > 0.0f) {
+        difference();
+        const ssrlcv_diff_stats s = differenceStats(diff, 0.0f, false, {5000u});
+        if (s.finite == 0) break;
+        params.center = s.quantile[0];
+        params.gate = (float)((double)gateFactor * (1.4826 * (double)differenceStats(diff, params.center, true, {5000u}).quantile[0]));
+      }
+      HipSafeCall(ssrlcv_hip_register_terms(points, n, &reg.pose, referenceHeight->device.get(), &referenceFrame, referenceCells->device.get(), &params,
+                                            record.get(), ws.get(), wsb, nullptr));
+      ssrlcv_register_terms terms;
+      HipSafeCall(ssrlcv_hip_memcpy(&terms, record.get(), sizeof terms, 1));
+      RegistrationStep step;
+      step.used = terms.used, step.inside = terms.inside;
+      step.rms = terms.used ? std::sqrt(terms.ee / (double)terms.used) : std::numeric_limits<double>::quiet_NaN();
+      step.center = params.center, step.gate = params.gate;
+      step.stepped = ssrlcv_register_step_host(&terms, dofMask, damping, step.delta) == SSRLCV_OK;
+      reg.history.push_back(step);
+      if (!step.stepped) break;
+      ssrlcv_register_pose next;
+      if (ssrlcv_register_compose_host(&reg.pose, step.delta, &next) != SSRLCV_OK) break;
+      double moved = 0.0;  // the largest displacement of a corner of the cloud's box
+      for (int k = 0; k < 8 && kept; ++k) {
+        const double c[3] = {(k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], (k & 4) ? hi[2] : lo[2]};
+        double d2 = 0.0;
+        for (int r = 0; r < 3; ++r) {
+          const float *a = reg.pose.m + 4 * r, *b = next.m + 4 * r;
+          const double before = (c[0] * (double)a[0] + c[1] * (double)a[1] + c[2] * (double)a[2]) + (double)a[3];
+          const double after = (c[0] * (double)b[0] + c[1] * (double)b[1] + c[2] * (double)b[2]) + (double)b[3];
+          d2 += (after - before) * (after - before);
+        }
+        moved = std::max(moved, std::sqrt(d2));
+      }
+      reg.pose = next;
+      if (moved <= 1e-3 * (double)referenceFrame.cell) {
+        reg.converged = true;
+        break;
+      }
+    }
+    if (origin == cpu) cloud->setMemoryState(cpu);
+    return reg;
   }
 
   ptr::value<Unity<float>> referenceHeight;           // set by setReferenceSurface, in state gpu

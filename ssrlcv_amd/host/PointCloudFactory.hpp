@@ -477,6 +477,51 @@ class PointCloudFactory {
     bundleTemp = generateBundles(matchSet, images);
     return twoViewTriangulate(bundleTemp, &localError);
   }
+
+  // ---- a pose applied to a cloud (include/ssrlcv_hip.h "surface registration" item 2): p' = M p + T in place, on the device;
+  // a "no result" point -- (0, 0, 0) or a non-finite component -- stays what it is.  The cloud is left in the state it came in.
+  // MeshFactory::registerToReference finds such a pose.
+  void transformPointCloud(ptr::value<Unity<float3>> cloud, const ssrlcv_register_pose& pose) {
+    if (cloud == nullptr || cloud->size() == 0 || cloud->size() > 0xFFFFFFFFul) return;
+    MemoryState origin = cloud->getMemoryState();
+    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
+    ssrlcv_float3* p = (ssrlcv_float3*)cloud->device.get();
+    HipSafeCall(ssrlcv_hip_transform_points(p, (uint32_t)cloud->size(), &pose, p, nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    if (cloud->getFore() != gpu) cloud->setFore(gpu);  // the device holds the moved points
+    if (origin == cpu) cloud->setMemoryState(cpu);     // brings them back
+    else if (origin == both) cloud->transferMemoryTo(cpu);
+  }
+
+  // Upstream's scalePointCloud / translatePointCloud / rotatePointCloud: a pose built on the host, then transformPointCloud.
+  // Scaling and rotating are about the origin.  rotatePointCloud turns about the x axis, then y, then z -- R = Rz Ry Rx of the
+  // angles in radians, the order of cam_rot everywhere in this mirror; SURVEY.md and INTEGRATION.md do not record upstream's
+  // order for this call, so that one is assumed.
+  static ssrlcv_register_pose poseOf(const double (&M)[3][3], float3 t) {
+    ssrlcv_register_pose g = {};
+    const float tv[3] = {t.x, t.y, t.z};
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) g.m[4 * r + c] = (float)M[r][c];
+      g.m[4 * r + 3] = tv[r];
+    }
+    return g;
+  }
+  void scalePointCloud(float scale, ptr::value<Unity<float3>> cloud) {
+    const double M[3][3] = {{scale, 0, 0}, {0, scale, 0}, {0, 0, scale}};
+    transformPointCloud(cloud, poseOf(M, {0.0f, 0.0f, 0.0f}));
+  }
+  void translatePointCloud(float3 translate, ptr::value<Unity<float3>> cloud) {
+    const double M[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    transformPointCloud(cloud, poseOf(M, translate));
+  }
+  void rotatePointCloud(float3 rotate, ptr::value<Unity<float3>> cloud) {
+    const double cx = std::cos((double)rotate.x), sx = std::sin((double)rotate.x), cy = std::cos((double)rotate.y), sy = std::sin((double)rotate.y),
+                 cz = std::cos((double)rotate.z), sz = std::sin((double)rotate.z);
+    const double M[3][3] = {{cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx},
+                            {sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx},
+                            {-sy, cy * sx, cy * cx}};
+    transformPointCloud(cloud, poseOf(M, {0.0f, 0.0f, 0.0f}));
+  }
 };
 
 }  // namespace ssrlcv

@@ -16,6 +16,7 @@ With world size 1 (no process group) every exchange is the identity.  Python her
 torch.distributed); all compute is libssrlcv_hip.so.  A `Workspace` keeps the per-rank plans, matcher workspaces and
 seed descriptors between calls: creating and freeing them per pair / per image was a third of a step.
 """
+import ctypes
 import os
 import sys
 import time
@@ -477,7 +478,87 @@ def difference_stats(diff, center=0.0, absolute=False, quantiles=(5000,)):
             "max": float(rec.max), "quantiles": [float(rec.quantile[k]) for k in range(len(quantiles))], "mean": mean, "rms": rms}
 
 
-def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=False, **kw):
+_REGISTER_DOF = {"shift": capi.REGISTER_SHIFT, "rigid": capi.REGISTER_RIGID, "similarity": capi.REGISTER_SIMILARITY}
+
+
+def transform_cloud(points, pose):
+    """A pose (capi.RegisterPose: p' = M p + T) applied to a cloud ((n, 3) float32 device tensor; include/ssrlcv_hip.h "surface
+    registration" item 2).  "No result" points stay what they are.  -> a new (n, 3) float32 device tensor."""
+    return capi.transform_points(points, pose)
+
+
+def _pose64(pose):
+    m = np.array(list(pose.m), np.float64).reshape(3, 4)
+    return m[:, :3], m[:, 3]
+
+
+def surface_register(points, reference, frame, max_jump=None, dof="rigid", iterations=8, gate=3.0, initial=None, damping=0.0):
+    """The pose that aligns a cloud ((n, 3) float32 device tensor) to a reference height map (float32 (h, w) device tensor in
+    `frame`) by point-to-plane Gauss-Newton steps (include/ssrlcv_hip.h "surface registration").  The reference is the triangle
+    mesh of the map at step 1, cut where two cells differ by more than max_jump (None: nowhere).  dof: "shift" (translation),
+    "rigid" (and rotation), "similarity" (and scale), or a mask of capi.register_step's bits.  initial: a capi.RegisterPose to
+    start from (None: the identity); a coarse search over many cells is the caller's.  The pivot is the float64 mean of the points
+    that have a difference under the initial pose, rounded to float.  Every iteration: with a gate (None: without), one
+    surface_difference of the posed cloud and two statistics calls give center = the median and width = gate x NMAD, and only
+    points with |d - center| <= width take part; then one capi.register_terms (one 304-byte read-back), capi.register_step with
+    `damping`, capi.register_compose.  The loop ends early when a step is refused, or -- converged -- when a step moves no corner
+    of the cloud's bounding box by more than 1e-3 cell.  -> dict(pose: capi.RegisterPose; converged; history: per iteration
+    dict(used, inside, rms = sqrt(ee / used), center, gate, delta: the step or None when it was refused, terms: the record)).
+    Deterministic: the same inputs give the same bytes."""
+    mask = _REGISTER_DOF[dof] if isinstance(dof, str) else int(dof)
+    inf = float("inf")
+    cells = capi.disparity_mesh(reference, 1, inf if max_jump is None else max_jump)[1]
+    pose = capi.RegisterPose()
+    ctypes.memmove(ctypes.byref(pose), ctypes.byref(capi.RegisterPose.make() if initial is None else initial), ctypes.sizeof(capi.RegisterPose))
+    pts = points.reshape(-1, 3)
+    kept = torch.isfinite(pts).all(1) & ~(pts == 0).all(1)       # the points the skip rule keeps
+    posed = capi.transform_points(points, pose)
+    has = (capi.dsm_difference(posed, reference, frame, cells).view(torch.int32) != capi.STEREO_INVALID_BITS) & kept
+    # masked reductions, no compaction: one read-back of the pivot's sums, the two counts and the box
+    inf32 = torch.tensor(inf, dtype=torch.float32, device=pts.device)
+    head = torch.cat([torch.where(has[:, None], posed.reshape(-1, 3), torch.zeros_like(inf32)).double().sum(0),
+                      torch.stack([has.sum(), kept.sum()]).double(),
+                      torch.where(kept[:, None], pts, inf32).min(0).values.double() if pts.shape[0] else torch.zeros(3, dtype=torch.float64, device=pts.device),
+                      torch.where(kept[:, None], pts, -inf32).max(0).values.double() if pts.shape[0] else torch.zeros(3, dtype=torch.float64, device=pts.device)]).cpu().numpy()
+    count = int(head[3])
+    pivot = head[:3] / count if count else np.zeros(3)
+    pose.pivot[:] = [float(np.float32(x)) for x in pivot]
+    if int(head[4]):
+        lo, hi = head[5:8], head[8:11]
+        corners = np.array([[(lo, hi)[(k >> a) & 1][a] for a in range(3)] for k in range(8)], np.float64)
+    else:
+        corners = np.zeros((0, 3))
+    history, converged, ws = [], False, None
+    for _ in range(int(iterations)):
+        center, width = 0.0, inf
+        if gate is not None:
+            diff = capi.dsm_difference(capi.transform_points(points, pose, out=posed), reference, frame, cells)
+            signed = capi.difference_stats(diff, quantiles=(5000,))
+            if signed.finite == 0:
+                break
+            center = float(signed.quantile[0])
+            mad = capi.difference_stats(diff, center=center, absolute=True, quantiles=(5000,)).quantile[0]
+            width = float(np.float32(np.float64(gate) * (np.float64(1.4826) * np.float64(mad))))
+        if ws is None:
+            ws = capi.dev_bytes(int(capi.LIB.ssrlcv_hip_register_terms_workspace_bytes(capi.c_u32(pts.shape[0]))))
+        terms = capi.register_terms(points, pose, reference, frame, cells, center, width, ws)
+        delta = capi.register_step(terms, mask, damping)
+        used = int(terms.used)
+        history.append({"used": used, "inside": int(terms.inside), "rms": float(np.sqrt(np.float64(terms.ee) / used)) if used else float("nan"),
+                        "center": center, "gate": width, "delta": None if delta is None else delta.tolist(), "terms": terms})
+        if delta is None:
+            break
+        nxt = capi.register_compose(pose, delta)
+        (m0, t0), (m1, t1) = _pose64(pose), _pose64(nxt)
+        step = (corners @ m1.T + t1) - (corners @ m0.T + t0)
+        pose = nxt
+        if len(corners) == 0 or float(np.sqrt((step ** 2).sum(1)).max()) <= 1e-3 * float(frame.cell):
+            converged = True
+            break
+    return {"pose": pose, "converged": converged, "history": history}
+
+
+def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=False, register=None, **kw):
     """How far a surface lies from a reference height map (`reference` in `frame`): `subject` is a cloud ((n, 3) float32 device
     tensor) or a height map (float32 (h, w): any tensor when subject_frame is given, one of the grid of `frame` without), which
     goes through capi.dsm_points of its own frame.  kw is surface_difference's (mesh, max_jump).  Three statistics calls on the differences: the signed ones with
@@ -485,12 +566,20 @@ def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=Fal
     -> dict(n; coverage = finite / n; bias: the median; nmad = 1.4826 x the median absolute deviation about it, host float64;
     mean, rms; le68, le90, le95: the 6827 / 9000 / 9500 quantiles of |diff|; min, max; diff: the differences).  With want_map and a
     height-map subject also error_map: the differences scattered back into the subject's grid by its validity mask, a map in
-    the form of every map here."""
+    the form of every map here.  With register = a dict of surface_register's arguments (dof, iterations, gate, initial, damping;
+    max_jump is kw's) the subject's points are registered to the reference first and the differences are those of the registered
+    points: the report gains pose and registration (surface_register's dictionary)."""
     sub_frame = frame if subject_frame is None else subject_frame
     is_map = subject_frame is not None or (subject.dim() == 2 and tuple(subject.shape) == (int(frame.h), int(frame.w)))
     if want_map and not is_map:
         raise ValueError("want_map needs a height-map subject")
     points = capi.dsm_points(subject, sub_frame)[0] if is_map else subject
+    registration = None
+    if register is not None:
+        if not kw.get("mesh", True):
+            raise ValueError("register needs the mesh of the reference (mesh=True)")
+        registration = surface_register(points, reference, frame, max_jump=kw.get("max_jump"), **dict(register))
+        points = transform_cloud(points, registration["pose"])
     diff = surface_difference(points, reference, frame, **kw)
     signed = difference_stats(diff, quantiles=(5000,))
     nan = float("nan")
@@ -508,6 +597,8 @@ def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=Fal
         error_map = torch.full(subject.shape, capi.STEREO_INVALID_BITS, dtype=torch.int32, device=subject.device)
         error_map[subject.view(torch.int32) != capi.STEREO_INVALID_BITS] = diff.view(torch.int32)   # dsm_points numbers the valid cells in raster order
         out["error_map"] = error_map.view(torch.float32)
+    if registration is not None:
+        out["pose"], out["registration"] = registration["pose"], registration
     return out
 
 
