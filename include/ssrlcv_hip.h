@@ -56,7 +56,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      disparity mesh: disparity_mesh, mesh_select, mesh_triangles (+ their workspace queries), mesh_normals;
  *      surface accuracy: dsm_difference, difference_stats (+ its workspace query);
  *      surface registration: register_terms (+ its workspace query), transform_points, register_step_host,
- *      register_compose_host */
+ *      register_compose_host;
+ *      mesh render: mesh_render (+ its workspace query), image_residual */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1365,6 +1366,84 @@ int ssrlcv_hip_transform_points(const ssrlcv_float3* points, uint32_t n, const s
                                 ssrlcv_stream_t stream);
 int ssrlcv_register_step_host(const ssrlcv_register_terms* record, uint32_t dofMask, double lambda, double* delta /* [7] */); /* host only */
 int ssrlcv_register_compose_host(const ssrlcv_register_pose* pose, const double* delta /* [7] */, ssrlcv_register_pose* out); /* host only */
+
+/* ---- mesh render: the grid mesh drawn into a pinhole view -- a z-buffered rasterisation that gives the depth map of the model in
+ * that view, the triangle under every pixel, and the vertices' greys carried into the image.  Compared with the view's own
+ * pixels (item 2) it is an accuracy measure that needs no reference surface: a wrong height shifts the texture, a wrong camera
+ * shifts all of it, and a view held out of the ortho-image is an independent check.  Everything is a selection, an int32
+ * expression or a fixed-order float32 expression, every product, sum and division rounded on its own, nothing contracted:
+ * csrc/render.hip is held to a numpy restatement byte for byte (tests/render_ref.py, tests/test_gpu_render.py).
+ *   inputs      a grid mesh as ssrlcv_hip_disparity_mesh leaves it (vertexIndex[gw gh], cells[(gw - 1) (gh - 1)], after
+ *               ssrlcv_hip_mesh_select too); points[n] the vertices' world positions, e.g. ssrlcv_hip_dsm_points'; grey[n] (uint8 a
+ *               vertex, e.g. the ortho-image's bytes of the valid cells; NULL: every grey counts as 0); one ssrlcv_ortho_view on the
+ *               HOST, of which M, pos, w and h are read -- `image` and `eye` are ignored.
+ *   1 render    ssrlcv_hip_mesh_render.
+ *     vertex      for vertex t, in float32, the projection of "ortho-image" word for word: d = P - pos; X = (M0 d.x + M1 d.y) +
+ *                 M2 d.z, Y with M3..5, W with M6..8; sx = X / W, sy = Y / W; iw = 1.0f / W.  The vertex is USABLE iff P's
+ *                 components are finite, W > 0, W <= 2^60, sx and sy are finite, fabsf(sx) <= 1048576 and fabsf(sy) <= 1048576,
+ *                 and iw is finite (a W so small that 1 / W overflows is as unusable as one that is not above 0).  Its position
+ *                 in 1/256 pixel is fx = (int32)rintf(sx * 256.0f), fy likewise (ties to even); pixel (x, y) has its centre at
+ *                 (256 x, 256 y), the sampling convention of the ortho-image: sx = x is the centre of pixel x.
+ *     triangle    every emitted triangle of `cells` (bit 0 / 1 = T0 / T1, bit 2 = the diagonal is b-c), corners (p, q, r) in the
+ *                 order of "disparity mesh" item 3; its id is 2 cellIndex + t, cellIndex = cj (gw - 1) + ci.  With
+ *                 E(a, b; c) = (b.x - a.x) (c.y - a.y) - (b.y - a.y) (c.x - a.x) in int32 over (fx, fy), in this order:
+ *                   a corner whose vertexIndex entry is not below n (UINT32_MAX, or stale for `points`: nothing is read or
+ *                   written out of bounds, as in mesh_normals), or whose vertex is not usable: skipped, counts[2]
+ *                   a bounding box wider or higher than 256 maxExtent (max - min > 256 maxExtent): skipped, counts[1]; with the
+ *                   box inside that bound every edge value below is under 2^29 in magnitude
+ *                   A = E(p, q; r) = 0: skipped, counts[2]
+ *                   x0 = max(ceil(minx / 256), 0), x1 = min(floor(maxx / 256), w - 1), y0 and y1 likewise, the divisions
+ *                   rounding towards -inf and +inf for negative coordinates too; x0 > x1 or y0 > y1 -- no pixel centre of the
+ *                   image inside the box, a triangle wholly off the image among them --: neither drawn nor counted
+ *                   otherwise DRAWN, counts[0], whether or not a centre turns out to be covered.
+ *                 There is no face culling: where A < 0 the three edge values and A are negated.
+ *     coverage    the centre c of pixel (x, y), x0 <= x <= x1, y0 <= y <= y1, is covered iff Ep = E(q, r; c), Eq = E(r, p; c) and
+ *                 Er = E(p, q; c) are all >= 0 (after the negation).  Edges are inclusive; a centre on a shared edge is covered
+ *                 twice and the depth test decides, so there is no fill rule.
+ *     per pixel   lp = (float)Ep / (float)A, lq and lr likewise; v = ((lp iwp) + (lq iwq)) + (lr iwr): the inverse depth,
+ *                 interpolated in the image.  v is positive and never subnormal or a NaN (the weights are in [0, 1], one is at
+ *                 least 1/3, iw >= 2^-60 and finite), so its bits order it.  The winner of a pixel is the covering triangle of
+ *                 greatest v, among equal v of smallest id.
+ *     outputs     each w x h of the view, pitch w; every entry of every given output is written and nothing behind it; any but
+ *                 depth may be NULL.  With the pixel's winner, its weights formed again by the expressions above:
+ *                   depth     float: 1.0f / v;  0x7FC00000 where nothing was drawn (the form of every map in this file)
+ *                   triangle  uint32: the id;  UINT32_MAX where nothing was drawn
+ *                   shade     uint8: floorf((((lp gp) + (lq gq)) + (lr gr)) + 0.5f) clamped to 0 .. 255, g the corners' greys as
+ *                             floats;  0 where nothing was drawn
+ *                   counts_dev[3]  uint32 (device): triangles drawn, skipped as too large, skipped for a corner or a zero area
+ *   2 residual  ssrlcv_hip_image_residual: image, shade (uint8) and depth of one w x h view, pitch w.  out = (float)image -
+ *               (float)shade, one subtraction, where depth's bits are not 0x7FC00000; 0x7FC00000 elsewhere: the entries that
+ *               ssrlcv_hip_difference_stats ("surface accuracy" item 2, validity) leaves out, so the map goes to it as it is.
+ * Refusals, decided on the host before any launch, the parameters before the sizes before the buffers:
+ *   render      SSRLCV_ERR_INVALID_ARG for a NULL params, maxExtent 0 or above 64, a NULL view, a non-finite entry of its M or
+ *               pos; then for a view with w h >= 2^31, then a grid with gw gh >= 2^31.  No size is unsupported.  An empty view
+ *               (w or h 0) then writes three zeros to counts_dev, if given, looks at nothing else and is SSRLCV_OK.  Then
+ *               SSRLCV_ERR_INVALID_ARG for a NULL depth or workspace, or -- unless n is 0 or the grid has no cell (gw or gh
+ *               below 2), where nothing is drawn and every output holds its "nothing drawn" value -- a NULL points,
+ *               vertexIndex or cells; then SSRLCV_ERR_WORKSPACE.
+ *   residual    SSRLCV_ERR_INVALID_ARG for w h >= 2^31; an empty view is then SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL
+ *               image, shade, depth or out.
+ * Workspace of render (host only; computed in size_t; 0 for a view with w h >= 2^31), a256 as in "disparity mesh":
+ *     256 + a256(8 w h) + a256(16 n)
+ *   the counters, one 64-bit accumulator a pixel, the projected vertices.  It may hold anything on entry.  The residual needs
+ *   none.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  Three passes -- a thread a vertex,
+ * a thread a cell (T0, then T1, at most (maxExtent + 1)^2 pixel centres each), a thread a pixel -- and global INTEGER atomics
+ * only, a 64-bit max on (bits(v) << 32) | (0xFFFFFFFF - id) a covered centre and 32-bit adds for the counts, which commute: the
+ * outputs do not depend on the order the triangles arrive in and are bit-equal run to run.  The residual uses no atomics.
+ * Out of scope, not built: perspective-correct shading (the greys are interpolated in the image, like v); near-plane clipping (a
+ * triangle with a corner at W <= 0 is dropped whole); triangles above 64 pixels; anti-aliasing; colour; pushbroom views;
+ * triangle soups that are not a grid mesh; predicted disparities. */
+typedef struct {
+  uint32_t maxExtent; /* 1 .. 64: a triangle whose bounding box is wider or higher than this many pixels is skipped */
+} ssrlcv_render_params; /* 4 bytes */
+size_t ssrlcv_hip_mesh_render_workspace_bytes(uint32_t n, uint32_t w, uint32_t h);
+int ssrlcv_hip_mesh_render(const ssrlcv_float3* points, uint32_t n, const uint8_t* grey /* may be NULL */, const uint32_t* vertexIndex,
+                           const uint8_t* cells, uint32_t gw, uint32_t gh, const ssrlcv_ortho_view* view, const ssrlcv_render_params* params,
+                           float* depth, uint32_t* triangle /* may be NULL */, uint8_t* shade /* may be NULL */,
+                           uint32_t* counts_dev /* may be NULL */, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+int ssrlcv_hip_image_residual(const uint8_t* image, const uint8_t* shade, const float* depth, uint32_t w, uint32_t h, float* out,
+                              ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -1140,6 +1140,57 @@ def register_compose(pose, delta):
     return out
 
 
+# ------------------------------------------------------------------ mesh render
+class RenderParams(ctypes.Structure):
+    """ssrlcv_render_params: a triangle whose bounding box is wider or higher than maxExtent pixels is skipped"""
+    _fields_ = [("maxExtent", c_u32)]
+
+
+assert ctypes.sizeof(RenderParams) == 4
+
+RENDER_NO_TRIANGLE = 0xFFFFFFFF   # triangle: nothing was drawn at the pixel
+
+
+def mesh_render(points_d, vertex_index_d, cells_d, view, grey_d=None, max_extent=8, want_triangle=True, want_shade=True, workspace=None):
+    """A grid mesh drawn into a pinhole view (ssrlcv_hip_mesh_render; include/ssrlcv_hip.h "mesh render" item 1).  points_d: (n, 3)
+    float32 device tensor, the vertices' world positions; vertex_index_d, cells_d: the maps of disparity_mesh (after mesh_select
+    too); view: an OrthoView (dsm_ortho_view's), of which M, pos, w and h are read; grey_d: uint8 (n,) device tensor, one grey a
+    vertex, or None (every grey 0).  -> (depth float32 (h, w), 0x7FC00000 where nothing was drawn; triangle int32 (h, w) holding
+    the uint32 bits: 2 cell + t, -1 (RENDER_NO_TRIANGLE) for none; shade uint8 (h, w); counts int32 [3] device tensor: triangles
+    drawn, skipped as larger than max_extent pixels, skipped for an unusable corner or a zero area); triangle and shade are None
+    unless asked for.  The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    gw, gh = _mesh_maps(vertex_index_d, cells_d)
+    p, n = _cloud(points_d)
+    if grey_d is not None:
+        assert grey_d.dtype == torch.uint8 and grey_d.is_cuda and grey_d.is_contiguous() and grey_d.numel() == n, "one grey a vertex"
+    assert isinstance(max_extent, int) and not isinstance(max_extent, bool) and 0 <= max_extent <= 0xFFFFFFFF   # c_u32 would wrap it
+    w, h = int(view.w), int(view.h)
+    need = int(LIB.ssrlcv_hip_mesh_render_workspace_bytes(c_u32(n), c_u32(w), c_u32(h)))
+    ws = workspace if workspace is not None and workspace.numel() >= max(need, 1) else dev_bytes(need)
+    params = RenderParams(max_extent)
+    depth = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    triangle = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_triangle else None
+    shade = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_shade else None
+    counts = torch.zeros(3, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_mesh_render(ptr(p) if n else c_vp(0), c_u32(n), ptr(grey_d) if n else c_vp(0), ptr(vertex_index_d) if gw * gh else c_vp(0),
+                                     ptr(cells_d) if cells_d.numel() else c_vp(0), c_u32(gw), c_u32(gh), ctypes.byref(view), ctypes.byref(params),
+                                     ptr(depth), ptr(triangle), ptr(shade), ptr(counts), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return depth, triangle, shade, counts
+
+
+def image_residual(image_d, shade_d, depth_d, out=None):
+    """A view's own pixels minus the rendered ones (ssrlcv_hip_image_residual; "mesh render" item 2): float32 (h, w),
+    (float)image - (float)shade where depth is valid and 0x7FC00000 elsewhere -- the form difference_stats takes.  image_d,
+    shade_d: uint8 (h, w) device tensors; depth_d: mesh_render's.  Into `out` when given.  Asynchronous on the current stream."""
+    h, w = _disparity_map(depth_d)
+    for t in (image_d, shade_d):
+        assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (h, w), "the image, the shade and the depth share one view"
+    res = torch.empty((h, w), dtype=torch.float32, device="cuda") if out is None else out
+    assert res.dtype == torch.float32 and res.is_cuda and res.is_contiguous() and res.numel() >= w * h
+    check(LIB.ssrlcv_hip_image_residual(ptr(image_d), ptr(shade_d), ptr(depth_d), c_u32(w), c_u32(h), ptr(res), stream_ptr()))
+    return res
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -21,6 +21,7 @@
 #include "align256.h"
 #include "compact.h"
 #include "device_math.h"
+#include "mesh_corners.h"
 
 namespace {
 
@@ -38,29 +39,6 @@ struct Grid {
 };
 
 __device__ __forceinline__ bool joined(float p, float q, float maxJump) { return fabsf(p - q) <= maxJump; }  // false for a NaN
-
-// The corners of triangle t of a cell whose diagonal is b-c (bc) or a-d, as offsets (di, dj) from corner a packed two bits a
-// corner: a = 0, b = 1, c = 2, d = 3, so di = corner & 1, dj = corner >> 1.
-//   a-d: T0 = (a, c, d), T1 = (a, d, b);   b-c: T0 = (a, c, b), T1 = (b, c, d)
-__device__ __forceinline__ void triangle_corners(bool bc, int t, uint32_t (&corner)[3]) {
-  if (!bc) {
-    corner[0] = 0u;
-    corner[1] = t == 0 ? 2u : 3u;
-    corner[2] = t == 0 ? 3u : 1u;
-  } else {
-    corner[0] = t == 0 ? 0u : 1u;
-    corner[1] = 2u;
-    corner[2] = t == 0 ? 1u : 3u;
-  }
-}
-
-// the nodes of triangle t of cell (ci, cj)
-__device__ __forceinline__ void triangle_nodes(const Grid& g, uint32_t ci, uint32_t cj, bool bc, int t, uint32_t (&node)[3]) {
-  uint32_t corner[3];
-  triangle_corners(bc, t, corner);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) node[k] = (cj + (corner[k] >> 1)) * g.gw + ci + (corner[k] & 1u);
-}
 
 __global__ __launch_bounds__(256) void k_mesh_cells(const float* __restrict__ disparity, uint32_t w, uint32_t step, Grid g, float maxJump,
                                                     uint32_t* __restrict__ vertexIndex, uint8_t* __restrict__ cells) {
@@ -125,7 +103,7 @@ struct TriEmit {
     if (dst >= capacity) return;
     const uint32_t cell = slot >> 1, cj = cell / (g.gw - 1), ci = cell - cj * (g.gw - 1);
     uint32_t node[3];
-    triangle_nodes(g, ci, cj, (cells[cell] & 4u) != 0u, (int)(slot & 1u), node);
+    triangle_nodes(g.gw, ci, cj, (cells[cell] & 4u) != 0u, (int)(slot & 1u), node);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)dst * 3 + k] = vertexIndex[node[k]];
   }
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(256) void k_mesh_normals(const ssrlcv_float3* __res
     for (int t = 0; t < 2; ++t) {
       if (!((byte >> t) & 1u)) continue;
       uint32_t tri[3];
-      triangle_nodes(g, ci, cj, (byte & 4u) != 0u, t, tri);
+      triangle_nodes(g.gw, ci, cj, (byte & 4u) != 0u, t, tri);
       if (tri[0] != node && tri[1] != node && tri[2] != node) continue;
       const uint32_t ip = vertexIndex[tri[0]], iq = vertexIndex[tri[1]], ir = vertexIndex[tri[2]];
       if (ip >= n || iq >= n || ir >= n) continue;
@@ -200,7 +178,7 @@ __global__ __launch_bounds__(256) void k_select_cells(const uint32_t* __restrict
   for (int t = 0; t < 2; ++t) {
     if (!((byte >> t) & 1u)) continue;
     uint32_t tri[3];
-    triangle_nodes(g, ci, cj, (byte & 4u) != 0u, t, tri);
+    triangle_nodes(g.gw, ci, cj, (byte & 4u) != 0u, t, tri);
 #pragma unroll
     for (int k = 0; k < 3; ++k)
       if (!select_keeps(map, nVertices, vertexIndex[tri[k]])) keep &= ~(1u << t);

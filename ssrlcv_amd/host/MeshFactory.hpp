@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "GridMesh.hpp"
+#include "Image.hpp"
 #include "Unity.hpp"
 #include "cuda_vec_types.hpp"
 #include "io_util.hpp"
@@ -602,6 +603,89 @@ class MeshFactory {
     }
     if (origin == cpu) cloud->setMemoryState(cpu);
     return reg;
+  }
+
+  // ---- mesh render (include/ssrlcv_hip.h "mesh render"): the surface drawn into a camera, and compared with that camera's own
+  // picture -- an accuracy measure that needs no reference surface.  Needs points with a surface (setPointsFromHeightMap, then
+  // setSurface(DisparityFactory::generateMesh(height, 1, maxJump))); the greys are `colors` (setVertexColors), 0 without.
+  struct RenderedView {
+    unsigned int w = 0, h = 0;                   // the camera's image
+    ptr::value<Unity<float>> depth;              // in state gpu: the distance along the optical axis, 0x7FC00000 where nothing was drawn
+    ptr::value<Unity<unsigned int>> triangle;    // 2 cell + t of the surface's grid, UINT32_MAX for none
+    ptr::value<Unity<unsigned char>> shade;      // the vertices' greys, interpolated; 0 where nothing was drawn
+    uint32_t drawn = 0, tooLarge = 0, unusable = 0;  // triangles drawn, skipped as above maxExtent pixels, skipped for a corner or no area
+  };
+  struct PhotoConsistency {
+    double coverage = 0, median = 0, nmad = 0, rms = 0;  // of image minus model, in grey levels; NaN where there is no value
+    RenderedView view;
+    ptr::value<Unity<float>> residual;           // in state gpu, 0x7FC00000 where nothing was drawn
+  };
+
+  // pipeline.surface_render's maps; depth is null when refused.  The points and the colours are left in the state they came in.
+  RenderedView renderView(const Image::Camera& camera, const ssrlcv_dsm_frame& frame, uint32_t maxExtent = 8) {
+    RenderedView r;
+    ssrlcv_ortho_view view;
+    view.image = nullptr;
+    const bool colored = colors != nullptr && points != nullptr && colors->size() == points->size();
+    if (!hasSurface || points == nullptr || surface.vertexCount != points->size() || points->size() > 0xFFFFFFFFul ||
+        ssrlcv_dsm_ortho_view_host((const ssrlcv_camera*)&camera, &frame, &view) != SSRLCV_OK) {
+      logger.err << "MeshFactory::renderView: needs a surface of these points (setSurface) and a camera the ortho-image takes";
+      return r;
+    }
+    MemoryState origin = points->getMemoryState(), originC = colored ? colors->getMemoryState() : gpu;
+    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
+    if (colored && (originC == cpu || colors->getFore() == cpu)) colors->transferMemoryTo(gpu);
+    const uint32_t n = (uint32_t)points->size();
+    const unsigned long pixels = (unsigned long)view.w * view.h;
+    const ssrlcv_render_params params = {maxExtent};
+    const size_t wsb = ssrlcv_hip_mesh_render_workspace_bytes(n, view.w, view.h);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::device<uint32_t> counts(3);
+    r.w = view.w, r.h = view.h;
+    r.depth = ptr::value<Unity<float>>(nullptr, pixels, gpu);
+    r.triangle = ptr::value<Unity<unsigned int>>(nullptr, pixels, gpu);
+    r.shade = ptr::value<Unity<unsigned char>>(nullptr, pixels, gpu);
+    const int status = ssrlcv_hip_mesh_render((const ssrlcv_float3*)points->device.get(), n, colored ? colors->device.get() : nullptr,
+                                              surface.vertexIndex->device.get(), surface.cells->device.get(), surface.gw, surface.gh, &view, &params,
+                                              r.depth->device.get(), r.triangle->device.get(), r.shade->device.get(), counts.get(), ws.get(), wsb, nullptr);
+    if (status == SSRLCV_OK) {
+      uint32_t c[3] = {0, 0, 0};
+      HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), sizeof c, 1));  // synchronises: the workspace may go out of scope
+      r.drawn = c[0], r.tooLarge = c[1], r.unusable = c[2];
+    } else {
+      logger.err.printf("MeshFactory::renderView: refused (%s)", ssrlcv_hip_status_string(status));
+      r = RenderedView();
+    }
+    if (origin == cpu) points->setMemoryState(cpu);
+    if (colored && originC == cpu) colors->setMemoryState(cpu);
+    return r;
+  }
+
+  // pipeline.surface_photo_check's figures for `image` (uint8, the camera's size), the picture `camera` took: the surface with its
+  // colours drawn into the camera, subtracted from the image, through the statistics as it is.  The image is left in its state.
+  PhotoConsistency photoConsistency(ptr::value<Unity<unsigned char>> image, const Image::Camera& camera, const ssrlcv_dsm_frame& frame,
+                                    uint32_t maxExtent = 8) {
+    PhotoConsistency p;
+    p.coverage = p.median = p.nmad = p.rms = std::numeric_limits<double>::quiet_NaN();
+    p.view = renderView(camera, frame, maxExtent);
+    if (p.view.depth == nullptr || image == nullptr || image->size() != (unsigned long)p.view.w * p.view.h) {
+      logger.err << "MeshFactory::photoConsistency: needs a view that renders and an image of the camera's size";
+      return p;
+    }
+    MemoryState origin = image->getMemoryState();
+    if (origin == cpu || image->getFore() == cpu) image->transferMemoryTo(gpu);
+    p.residual = ptr::value<Unity<float>>(nullptr, image->size(), gpu);
+    HipSafeCall(ssrlcv_hip_image_residual(image->device.get(), p.view.shade->device.get(), p.view.depth->device.get(), p.view.w, p.view.h,
+                                          p.residual->device.get(), nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    if (origin == cpu) image->setMemoryState(cpu);
+    const ssrlcv_diff_stats s = differenceStats(p.residual, 0.0f, false, {5000u});
+    p.coverage = (double)s.finite / (double)s.n;
+    if (s.finite == 0) return p;
+    p.median = s.quantile[0];
+    p.rms = std::sqrt(s.sumSq / (double)s.finite);
+    p.nmad = 1.4826 * (double)differenceStats(p.residual, s.quantile[0], true, {5000u}).quantile[0];
+    return p;
   }
 
   ptr::value<Unity<float>> referenceHeight;           // set by setReferenceSurface, in state gpu

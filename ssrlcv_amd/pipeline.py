@@ -455,6 +455,43 @@ def surface_colors(ortho, height):
     return ortho[height.view(torch.int32) != capi.STEREO_INVALID_BITS]
 
 
+def surface_render(model_or_height, frame, camera, colors=None, max_jump=None, max_extent=8):
+    """The surface of a surface model (surface_model's dictionary, or its height map alone) drawn into the view of an Image::Camera
+    record (include/ssrlcv_hip.h "mesh render"): the valid cells as vertices (capi.dsm_points), the mesh of the map at step 1, cut
+    where two cells differ by more than max_jump (None: nowhere), z-buffered into the camera's image.  colors: one grey a vertex
+    (surface_colors'), or None.  A triangle above max_extent pixels is skipped and counted.
+    -> dict(depth float32 (h, w): the distance along the optical axis, 0x7FC00000 where nothing was drawn; triangle int32 (h, w):
+    2 cell + t of the grid's cell raster, -1 for none; shade uint8 (h, w); counts: dict(drawn, too_large, unusable))."""
+    height = model_or_height["height"] if isinstance(model_or_height, dict) else model_or_height
+    pts, n = capi.dsm_points(height, frame)
+    vertex_index, cells, _ = capi.disparity_mesh(height, 1, float("inf") if max_jump is None else max_jump)
+    depth, triangle, shade, counts = capi.mesh_render(pts, vertex_index, cells, capi.dsm_ortho_view(camera, frame), colors, max_extent)
+    drawn, too_large, unusable = (int(c) for c in counts.cpu().tolist())
+    return {"depth": depth, "triangle": triangle, "shade": shade, "counts": {"drawn": drawn, "too_large": too_large, "unusable": unusable}}
+
+
+def surface_photo_check(model, frame, ortho, image, camera, max_jump=None, max_extent=8, want_map=False):
+    """How well a textured surface model predicts a view's own pixels -- an accuracy measure that needs no reference surface: the
+    model's mesh takes the greys of its ortho-image (surface_colors of surface_ortho's `ortho`), is drawn into `camera`
+    (surface_render) and subtracted from `image` (uint8 (h, w) device tensor, the camera's picture: a view held out of the
+    ortho-image is an independent check); the residuals go through difference_stats as they are.
+    -> dict(coverage: the share of the image's pixels the model covers; median: of the residuals, image minus model, in grey
+    levels; nmad = 1.4826 x the median absolute deviation about it, host float64; rms; counts: surface_render's); with want_map
+    also residual: float32 (h, w), 0x7FC00000 where nothing was drawn."""
+    height = model["height"] if isinstance(model, dict) else model
+    drawn = surface_render(height, frame, camera, surface_colors(ortho, height), max_jump, max_extent)
+    residual = capi.image_residual(image, drawn["shade"], drawn["depth"])
+    signed = difference_stats(residual, quantiles=(5000,))
+    nan = float("nan")
+    median = signed["quantiles"][0] if signed["finite"] else nan
+    mad = difference_stats(residual, center=median, absolute=True, quantiles=(5000,))["quantiles"][0] if signed["finite"] else nan
+    out = {"coverage": signed["finite"] / signed["n"] if signed["n"] else nan, "median": median, "nmad": float(np.float64(1.4826) * np.float64(mad)),
+           "rms": signed["rms"], "counts": drawn["counts"]}
+    if want_map:
+        out["residual"] = residual
+    return out
+
+
 def surface_difference(points, reference, frame, mesh=True, max_jump=None):
     """The signed height difference of every point of a cloud ((n, 3) float32 device tensor) to a reference height map (float32
     (h, w) device tensor in `frame`; include/ssrlcv_hip.h "surface accuracy" item 1), positive above the reference along the
