@@ -57,7 +57,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      surface accuracy: dsm_difference, difference_stats (+ its workspace query);
  *      surface registration: register_terms (+ its workspace query), transform_points, register_step_host,
  *      register_compose_host;
- *      mesh render: mesh_render (+ its workspace query), image_residual */
+ *      mesh render: mesh_render (+ its workspace query), image_residual;
+ *      surface simplification: dsm_simplify_errors, dsm_simplify_mesh (+ its workspace query) */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1030,7 +1031,7 @@ int ssrlcv_hip_stereo_fill_holes(const float* in, float* out, uint8_t* filled /*
  *     mesh_triangles   c(2 (gw - 1) (gh - 1)), c(0) when gw or gh is below 2
  * It may hold anything on entry.
  * Execution: asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.
- * Out of scope: vertex welding or decimation, closing holes in the mesh, triangle-quality tests in 3-D (a sliver between a
+ * Out of scope: vertex welding or decimation (a height map's mesh is thinned by "surface simplification"), closing holes in the mesh, triangle-quality tests in 3-D (a sliver between a
  * near and a far surface is cut by maxJump alone), texture coordinates, Poisson or any other reconstruction from unorganised
  * clouds, merging the meshes of several pairs. */
 typedef struct {
@@ -1444,6 +1445,88 @@ int ssrlcv_hip_mesh_render(const ssrlcv_float3* points, uint32_t n, const uint8_
                            uint32_t* counts_dev /* may be NULL */, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
 int ssrlcv_hip_image_residual(const uint8_t* image, const uint8_t* shade, const float* depth, uint32_t w, uint32_t h, float* out,
                               ssrlcv_stream_t stream);
+
+/* ---- surface simplification: the grid mesh of a height map holds two triangles a cell wherever the map is valid, on a plain as on
+ * a cliff.  This section selects a subset of its nodes and a conforming triangulation of them: a hierarchical right-triangle mesh
+ * (RTIN / restricted quadtree, Lindstrom-Pajarola) that keeps full resolution where the map is rough and at hole boundaries and
+ * collapses to large triangles where it is flat.  It is a pure selection over the existing nodes -- no vertex is created -- and its
+ * only float work is one fixed-order float32 expression a node plus max, which commutes: csrc/simplify.hip is held to a numpy
+ * restatement bit for bit (tests/simplify_ref.py, tests/test_gpu_simplify.py).  The error map is computed once; a mesh at any
+ * tolerance is then one extraction.
+ *   input       a height map height[w h], float, pitch w, the form of every map in this file: a node is valid iff its bits are
+ *               not 0x7FC00000; other NaNs, the infinities and -0 are valid values.
+ *   domain      L is the smallest integer with 2^L >= max(w - 1, h - 1, 1), S = 2^L; the domain is the node square [0, S]^2.  A
+ *               node is PRESENT iff it lies inside the grid (x < w, y < h) and is valid.  tz(v) = the number of trailing zero bits
+ *               of v, tz(0) = infinity; k(x, y) = min(tz(x), tz(y)); a node of the domain is a SPLIT NODE iff k < L: every node but
+ *               the domain's four corners.  u = 2^k.
+ *     D-node      tz(x) == tz(y): the centre of a block of side 2u, level t = 2 (L - k - 1).  With I = (x - u) / (2u) and
+ *                 J = (y - u) / (2u) the hypotenuse is the main diagonal iff I + J is even: a = (x - u, y - u), b = (x + u, y + u),
+ *                 apexes (x + u, y - u) and (x - u, y + u); otherwise a = (x + u, y - u), b = (x - u, y + u), apexes
+ *                 (x - u, y - u) and (x + u, y + u).  Children: (x +- u, y) and (x, y +- u).
+ *     A-node      tz(x) != tz(y): the midpoint of a block edge, level t = 2 (L - k - 1) + 1.  If tz(x) < tz(y): a = (x - u, y),
+ *                 b = (x + u, y), apexes (x, y - u) and (x, y + u); otherwise a = (x, y - u), b = (x, y + u), apexes (x - u, y) and
+ *                 (x + u, y).  An apex outside the domain does not exist: the edge lies on the domain's border.  Children: the
+ *                 four nodes (x +- u/2, y +- u/2) that lie in the domain; none when k = 0.
+ *   1 errors    ssrlcv_hip_dsm_simplify_errors.  e(m) = +inf unless m, a, b and every existing apex of m are present; otherwise,
+ *               in float32 with nothing contracted, mid = (h(a) + h(b)) * 0.5f, d = fabsf(h(m) - mid), e(m) = d if d < +inf, else
+ *               +inf (a NaN becomes +inf).  E(m) = max(e(m), E of m's children); a split node of the domain outside the grid has
+ *               E = +inf.  error[w h] (float) holds E for every split node of the grid and +inf for the at most four corners of
+ *               the domain inside the grid.  Every entry lies in [+0, +inf], never a NaN and never -0, so its bits order it.
+ *               Every entry is written and nothing behind the map.
+ *   2 triangles ssrlcv_hip_dsm_simplify_mesh at a `tolerance` that is a finite float; a negative one is legal and gives the
+ *               full-resolution mesh.  `error` is item 1's map of the same height map.
+ *     split nodes for a split node m inside the grid and an existing apex c of it, the triangle with hypotenuse a-b and apex c is
+ *                 emitted iff E(m) <= tol and (t(m) == 0 or !(E(c) <= tol)).  E(m) <= tol makes c present, so E(c) is an entry of
+ *                 the map.
+ *     leaves      cell (i, j), 0 <= i < w - 1, 0 <= j < h - 1, has its diagonal main iff i + j is even: a = (i, j),
+ *                 b = (i + 1, j + 1), apexes (i + 1, j) and (i, j + 1); otherwise a = (i + 1, j), b = (i, j + 1), apexes (i, j)
+ *                 and (i + 1, j + 1).  A leaf is emitted iff a, b and c are present and (L == 0 or !(E(c) <= tol)).
+ *     record      (p, q, r) = (c, a, b) if (a.x - c.x) (b.y - c.y) - (a.y - c.y) (b.x - c.x) < 0 in integers, else (c, b, a): the
+ *                 winding of "disparity mesh" item 3, so on a frame with the `winding` of "surface model" the faces look along
+ *                 +ez.
+ *     order       ascending (2 m.y, 2 m.x), the midpoint of the hypotenuse in doubled coordinates -- a leaf of cell (i, j) has
+ *                 (2j + 1, 2i + 1) --, triangles that share a midpoint by apex (c.y, c.x).
+ *     output      the three uint32 of a record are the corners' new vertex indices (item 3).  *triCount_dev (device) = the full
+ *                 count; only the first min(count, capacity) records are written and nothing behind out[3 capacity) is touched;
+ *                 out may be NULL with capacity 0 (the truncation contract of ssrlcv_hip_mesh_triangles).
+ *   3 vertices  a node is KEPT iff it is a corner of an emitted triangle, whether or not that triangle fit into `capacity`.
+ *               vertexIndex[w h] (uint32) holds a kept node's rank among the kept nodes in raster order and UINT32_MAX elsewhere;
+ *               *vertexCount_dev (device) = their number.  kept[min(count, keptCapacity)] holds, per new vertex in order, the
+ *               node's entry of nodeIndex[w h] if nodeIndex is given, else its raster index j w + i.  With the vertexIndex that
+ *               ssrlcv_hip_disparity_mesh gives the same map at step 1 as nodeIndex, `kept` is strictly ascending in the
+ *               numbering of ssrlcv_hip_dsm_points -- the form of keptIndex in ssrlcv_hip_mesh_select -- and a caller gathers
+ *               points, normals and greys through it.
+ *   bound       for an emitted triangle of level t every node inside it is the midpoint of one of its descendants, all of which
+ *               have E <= tol: refining down to the node the piecewise-linear surface moves at most tol a level, so the vertical
+ *               distance of any covered node from the triangle's plane is at most (2L - t) tol in exact arithmetic; the two
+ *               float32 roundings of e add at most 2^-22 max|h| a level.  This is the only accuracy promise.
+ *   border      a grid whose sides are not 2^L + 1 pays full refinement along the sides that cut the domain (an apex outside the
+ *               grid is not present): a plane at tolerance 0 gives 2 triangles on 33 x 33, 147 on 20 x 34 and 46 on 17 x 12.
+ *               The cost is a perimeter term and is accepted.
+ * Refusals, decided on the host before any launch, in this order: SSRLCV_ERR_INVALID_ARG for a tolerance that is not finite (mesh)
+ * and for w h >= 2^31; SSRLCV_ERR_UNSUPPORTED for w h > 2^29 -- the candidate numbering 2 w (2h - 1) must fit 32 bits --; mesh:
+ * SSRLCV_ERR_INVALID_ARG for a NULL triCount_dev or vertexCount_dev; an empty map (w or h 0) then writes both counts 0 (errors:
+ * nothing), looks at nothing else and is SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL buffer that has an element to hold
+ * (height and error; mesh: vertexIndex and the workspace too, out unless capacity is 0, kept unless keptCapacity is 0; nodeIndex
+ * may always be NULL); then SSRLCV_ERR_WORKSPACE.
+ * Workspace of mesh (host only; computed in size_t; 0 for a refused or empty size), a256 and c as in "disparity mesh":
+ *     c(2 w (2h - 1)) + c(w h)
+ *   the tables of the compaction over the triangle candidates and of the one over the nodes.  It may hold anything on entry.
+ *   The errors need none.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  errors: a level is two launches, its
+ * A-nodes then its D-nodes, a thread a node of the level's lattice; the levels whose lattice has at most 4096 nodes run in one
+ * block: 2L launches at most.  Every entry has one writer.  mesh: two ordered compactions (csrc/compact.h); the kept marks are
+ * stores of one value.  No atomics at all: bit-equal run to run.
+ * Out of scope: maxJump cuts (a cliff keeps full resolution through its error instead); errors measured in 3-D or along the normal;
+ * edge-collapse or quadric decimation; rendering the simplified mesh with ssrlcv_hip_mesh_render, which takes grid meshes only;
+ * normals recomputed on the simplified faces (gather the full-resolution ones); texture coordinates; tiling the domain so that a
+ * grid with w - 1 not a power of two avoids border refinement. */
+int ssrlcv_hip_dsm_simplify_errors(const float* height, uint32_t w, uint32_t h, float* error, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_dsm_simplify_mesh_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_simplify_mesh(const float* height, const float* error, uint32_t w, uint32_t h, float tolerance,
+                                 const uint32_t* nodeIndex /* may be NULL */, uint32_t* vertexIndex, uint32_t* out, uint32_t capacity,
+                                 uint32_t* triCount_dev, uint32_t* kept, uint32_t keptCapacity, uint32_t* vertexCount_dev, void* workspace,
+                                 size_t workspaceBytes, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

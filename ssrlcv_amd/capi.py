@@ -1191,6 +1191,43 @@ def image_residual(image_d, shade_d, depth_d, out=None):
     return res
 
 
+# ------------------------------------------------------------------ surface simplification
+def dsm_simplify_errors(height_d, out=None):
+    """The error map of a height map's right-triangle hierarchy (ssrlcv_hip_dsm_simplify_errors; include/ssrlcv_hip.h "surface
+    simplification" item 1): float32 (h, w), per split node the largest midpoint error in its subtree, +inf where a triangle
+    cannot be formed.  Computed once; dsm_simplify_mesh extracts a mesh at any tolerance from it.  Into `out` when given.
+    Asynchronous on the current stream."""
+    h, w = _disparity_map(height_d)
+    err = torch.empty((h, w), dtype=torch.float32, device="cuda") if out is None else out
+    assert err.dtype == torch.float32 and err.is_cuda and err.is_contiguous() and err.numel() >= w * h
+    check(LIB.ssrlcv_hip_dsm_simplify_errors(ptr(height_d), c_u32(w), c_u32(h), ptr(err), stream_ptr()))
+    return err
+
+
+def dsm_simplify_mesh(height_d, error_d, tolerance, node_index_d=None, capacity=None, kept_capacity=None, workspace=None):
+    """The simplified mesh of a height map at `tolerance` (ssrlcv_hip_dsm_simplify_mesh; items 2 and 3).  error_d:
+    dsm_simplify_errors' map of height_d.  node_index_d: int32 (h, w) or None; `kept` then holds raster indices.
+    -> (faces int32 (min(count, capacity), 3): new vertex indices; n_faces; kept int32 (min(n_vertices, kept_capacity),): per new
+    vertex its node's entry of node_index_d; n_vertices; vertex_index int32 (h, w) holding the uint32 bits: a kept node's new index,
+    -1 elsewhere).  capacity defaults to the full-resolution mesh, kept_capacity to the grid.  One synchronisation (the counts)."""
+    h, w = _disparity_map(height_d)
+    assert _disparity_map(error_d) == (h, w), "the error map has the height map's grid"
+    if node_index_d is not None:
+        assert node_index_d.dtype == torch.int32 and node_index_d.is_cuda and node_index_d.is_contiguous() and tuple(node_index_d.shape) == (h, w)
+    cap = 2 * max(w - 1, 0) * max(h - 1, 0) if capacity is None else int(capacity)
+    kcap = w * h if kept_capacity is None else int(kept_capacity)
+    ws = _filter_workspace(LIB.ssrlcv_hip_dsm_simplify_mesh_workspace_bytes, w, h, workspace)
+    faces = torch.empty((cap, 3), dtype=torch.int32, device="cuda")
+    kept = torch.empty(kcap, dtype=torch.int32, device="cuda")
+    vertex_index = torch.empty((h, w), dtype=torch.int32, device="cuda")
+    counts = torch.zeros(2, dtype=torch.int32, device="cuda")
+    check(LIB.ssrlcv_hip_dsm_simplify_mesh(ptr(height_d), ptr(error_d), c_u32(w), c_u32(h), c_f32(tolerance), ptr(node_index_d), ptr(vertex_index),
+                                           ptr(faces) if cap else c_vp(0), c_u32(cap), c_vp(counts.data_ptr()), ptr(kept) if kcap else c_vp(0),
+                                           c_u32(kcap), c_vp(counts.data_ptr() + 4), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    nt, nv = (int(c) for c in counts.cpu().tolist())
+    return faces[: min(nt, cap)], nt, kept[: min(nv, kcap)], nv, vertex_index
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -7,6 +7,8 @@
 // mesh"); setSurface takes them, computeSurfaceNormals, faces and saveMesh work on them, and filterByNeighborDistance keeps
 // them in step with the points it keeps.  How far a cloud lies from a reference surface -- upstream's
 // calculatePerPointDifference / calculateAverageDifference -- is measured against a height map (setReferenceSurface).
+// The surface of a height map is thinned to an error-bounded right-triangle mesh by simplifySurface (include/ssrlcv_hip.h
+// "surface simplification"); it is then a triangle list and no grid mesh.
 //
 // Memory state: `points` goes to the gpu for a call and comes back to its origin state; Unitys this class creates
 // (filtered points, normals, mean distances) are left in the state the points were in.
@@ -74,6 +76,20 @@ class MeshFactory {
                                   from->size() * sizeof(T), onGpu ? 2 : 0));
     return to;
   }
+  // rows `rows` (ascending) of `from`, in the state `from` is in
+  template <typename T>
+  static ptr::value<Unity<T>> gathered(ptr::value<Unity<T>> from, const std::vector<uint32_t>& rows) {
+    MemoryState origin = from->getMemoryState();
+    if (origin == gpu || from->getFore() == gpu) from->transferMemoryTo(cpu);
+    ptr::host<T> values((long)rows.size(), true);
+    for (size_t k = 0; k < rows.size(); ++k) values.get()[k] = from->host.get()[rows[k]];
+    ptr::value<Unity<T>> out(values, (unsigned long)rows.size(), cpu, true);
+    if (origin == gpu) {
+      from->setMemoryState(gpu);
+      out->setMemoryState(gpu);
+    }
+    return out;
+  }
   bool usable(int k, const char* what) const {
     if (points == nullptr || k < 1 || k > SSRLCV_KNN_MAX_K || points->size() < (unsigned long)k + 1) {
       logger.err.printf("MeshFactory::%s: needs 1 <= k <= %d and more than k points", what, SSRLCV_KNN_MAX_K);
@@ -89,6 +105,10 @@ class MeshFactory {
   double filterStats[3] = {0, 0, 0};  // {mu, std, threshold} of the last filterByNeighborDistance
   GridMesh surface;                   // set by setSurface: vertex v is points[v]; its own copy of the maps, in state gpu
   bool hasSurface = false;
+  ptr::value<Unity<float>> surfaceHeight;  // set by setPointsFromHeightMap: its own copy of the map the points came from, in state gpu
+  ssrlcv_dsm_frame surfaceFrame = {};
+  ptr::value<Unity<uint3>> simplifiedFaces;  // set by simplifySurface: the surface is then this triangle list, no GridMesh
+  bool hasSimplified = false;
 
   MeshFactory() {}
   explicit MeshFactory(ptr::value<Unity<float3>> points) : points(points) {}
@@ -99,6 +119,7 @@ class MeshFactory {
     normals = ptr::value<Unity<float3>>();
     colors = ptr::value<Unity<unsigned char>>();
     clearSurface();
+    surfaceHeight = ptr::value<Unity<float>>();
   }
 
   // the triangles of the points' disparity map (DisparityFactory::generateMesh for the map and step the points' records were
@@ -117,10 +138,19 @@ class MeshFactory {
   void clearSurface() {
     surface = GridMesh();
     hasSurface = false;
+    simplifiedFaces = ptr::value<Unity<uint3>>();
+    hasSimplified = false;
+  }
+  // a simplified surface is a triangle list: the calls that read a GridMesh say so and leave it alone
+  bool refusesSimplified(const char* what) const {
+    if (!hasSimplified) return false;
+    logger.err.printf("MeshFactory::%s: the surface was simplified (simplifySurface) and is a triangle list, not a grid mesh", what);
+    return true;
   }
 
   // unit normals from the surface's triangles, facing the camera of the disparity map; (0, 0, 0) for a vertex without one
   void computeSurfaceNormals() {
+    if (refusesSimplified("computeSurfaceNormals")) return;
     if (!hasSurface || points == nullptr || surface.vertexCount != points->size()) {
       logger.err << "MeshFactory::computeSurfaceNormals: needs a surface of these points (setSurface)";
       return;
@@ -141,6 +171,7 @@ class MeshFactory {
 
   // the surface's triangles as vertex index triples, in state gpu; null without a surface or without a triangle
   ptr::value<Unity<uint3>> faces() {
+    if (hasSimplified) return simplifiedFaces;
     if (!hasSurface) return ptr::value<Unity<uint3>>();
     const size_t wsb = ssrlcv_hip_mesh_triangles_workspace_bytes(surface.gw, surface.gh);
     ptr::device<unsigned char> ws(wsb ? wsb : 1);
@@ -179,6 +210,10 @@ class MeshFactory {
   // corner goes, nothing is re-triangulated).  Input order is kept.
   void filterByNeighborDistance(int k, float sigma) {
     if (!usable(k, "filterByNeighborDistance")) return;
+    if (hasSimplified) {  // the triangle list indexes the points as they are: it does not follow a filter
+      logger.err << "MeshFactory::filterByNeighborDistance: drops the simplified surface (filter before simplifySurface)";
+      clearSurface();
+    }
     MemoryState origin = points->getMemoryState();
     if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
     const unsigned long n = points->size();
@@ -308,8 +343,74 @@ class MeshFactory {
       HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, (ssrlcv_float3*)pts->device.get(), n, count.get(), ws.get(), wsb, nullptr));
       HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
       setPoints(pts);
+      surfaceHeight = copyToGpu(height);  // simplifySurface works on the map the points came from
+      surfaceFrame = frame;
     }
     if (origin != gpu) height->setMemoryState(origin);
+  }
+
+  // ---- surface simplification (include/ssrlcv_hip.h "surface simplification"): the surface of the height map thinned to a
+  // right-triangle mesh whose midpoint errors stay within `tolerance`, in the map's height units.  Needs points from
+  // setPointsFromHeightMap, unfiltered.  Points, normals and colours are replaced by the kept ones (normals and colours where they
+  // match the points; set them before: the full-resolution normals are gathered, none are recomputed), faces() and saveMesh give the
+  // simplified triangle list, and the surface is no GridMesh any longer: computeSurfaceNormals, renderView and photoConsistency
+  // refuse it.  Returns the number of triangles; 0 when refused or when nothing is left.
+  unsigned long simplifySurface(float tolerance) {
+    const unsigned long cells = (unsigned long)surfaceFrame.w * surfaceFrame.h;
+    if (refusesSimplified("simplifySurface")) return 0;
+    if (points == nullptr || surfaceHeight == nullptr || surfaceHeight->size() != cells || !std::isfinite(tolerance)) {
+      logger.err << "MeshFactory::simplifySurface: needs points from setPointsFromHeightMap and a finite tolerance";
+      return 0;
+    }
+    const uint32_t w = surfaceFrame.w, h = surfaceFrame.h;
+    const float* height = surfaceHeight->device.get();
+    // the numbering of the points: the vertexIndex of the map's mesh at step 1
+    ssrlcv_mesh_params meshParams = {1u, std::numeric_limits<float>::infinity()};
+    const size_t meshWsb = ssrlcv_hip_disparity_mesh_workspace_bytes(w, h, &meshParams);
+    const size_t wsb = std::max(meshWsb, ssrlcv_hip_dsm_simplify_mesh_workspace_bytes(w, h));
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    const unsigned long meshCells = (unsigned long)(w - 1) * (h - 1);
+    ptr::device<unsigned char> gridCells(meshCells ? meshCells : 1);
+    ptr::device<uint32_t> nodeIndex(cells), vertexIndex(cells), counts(2);
+    HipSafeCall(ssrlcv_hip_disparity_mesh(height, w, h, &meshParams, nodeIndex.get(), gridCells.get(), counts.get(), ws.get(), wsb, nullptr));
+    uint32_t c[2] = {0, 0};
+    HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), 4, 1));
+    if (c[0] != points->size()) {
+      logger.err.printf("MeshFactory::simplifySurface: the map has %u valid cells, the cloud %lu points (filtered?)", c[0], points->size());
+      return 0;
+    }
+    ptr::device<float> error(cells);
+    HipSafeCall(ssrlcv_hip_dsm_simplify_errors(height, w, h, error.get(), nullptr));
+    const int status = ssrlcv_hip_dsm_simplify_mesh(height, error.get(), w, h, tolerance, nodeIndex.get(), vertexIndex.get(), nullptr, 0, counts.get(),
+                                                    nullptr, 0, counts.get() + 1, ws.get(), wsb, nullptr);
+    if (status != SSRLCV_OK) {
+      logger.err.printf("MeshFactory::simplifySurface: refused (%s)", ssrlcv_hip_status_string(status));
+      return 0;
+    }
+    HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), 8, 1));
+    const uint32_t t = c[0], m = c[1];
+    clearSurface();
+    if (t == 0) {
+      points = ptr::value<Unity<float3>>();
+      normals = ptr::value<Unity<float3>>();
+      colors = ptr::value<Unity<unsigned char>>();
+      return 0;
+    }
+    ptr::value<Unity<uint3>> tris(nullptr, (unsigned long)t, gpu);
+    ptr::device<uint32_t> kept(m);
+    HipSafeCall(ssrlcv_hip_dsm_simplify_mesh(height, error.get(), w, h, tolerance, nodeIndex.get(), vertexIndex.get(), (uint32_t*)tris->device.get(), t,
+                                             counts.get(), kept.get(), m, counts.get() + 1, ws.get(), wsb, nullptr));
+    std::vector<uint32_t> keptHost(m);
+    HipSafeCall(ssrlcv_hip_memcpy(keptHost.data(), kept.get(), (size_t)m * 4, 1));  // synchronises: the workspace may go out of scope
+    const unsigned long n = points->size();
+    const bool withNormals = normals != nullptr && normals->size() == n, withColors = colors != nullptr && colors->size() == n;
+    points = gathered(points, keptHost);
+    normals = withNormals ? gathered(normals, keptHost) : ptr::value<Unity<float3>>();
+    colors = withColors ? gathered(colors, keptHost) : ptr::value<Unity<unsigned char>>();
+    simplifiedFaces = tris;
+    hasSimplified = true;
+    logger.info.printf("MeshFactory::simplifySurface: %u of %lu vertices, %u of %lu triangles at tolerance %g", m, n, t, 2 * meshCells, (double)tolerance);
+    return t;
   }
 
   // ---- the ortho-image (include/ssrlcv_hip.h "ortho-image"): the picture on the surface model.  generateOrthoImage on the fused,
@@ -627,6 +728,7 @@ class MeshFactory {
     ssrlcv_ortho_view view;
     view.image = nullptr;
     const bool colored = colors != nullptr && points != nullptr && colors->size() == points->size();
+    if (refusesSimplified("renderView")) return r;
     if (!hasSurface || points == nullptr || surface.vertexCount != points->size() || points->size() > 0xFFFFFFFFul ||
         ssrlcv_dsm_ortho_view_host((const ssrlcv_camera*)&camera, &frame, &view) != SSRLCV_OK) {
       logger.err << "MeshFactory::renderView: needs a surface of these points (setSurface) and a camera the ortho-image takes";
@@ -667,6 +769,7 @@ class MeshFactory {
                                     uint32_t maxExtent = 8) {
     PhotoConsistency p;
     p.coverage = p.median = p.nmad = p.rms = std::numeric_limits<double>::quiet_NaN();
+    if (refusesSimplified("photoConsistency")) return p;
     p.view = renderView(camera, frame, maxExtent);
     if (p.view.depth == nullptr || image == nullptr || image->size() != (unsigned long)p.view.w * p.view.h) {
       logger.err << "MeshFactory::photoConsistency: needs a view that renders and an image of the camera's size";

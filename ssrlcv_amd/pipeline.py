@@ -470,6 +470,29 @@ def surface_render(model_or_height, frame, camera, colors=None, max_jump=None, m
     return {"depth": depth, "triangle": triangle, "shade": shade, "counts": {"drawn": drawn, "too_large": too_large, "unusable": unusable}}
 
 
+def surface_simplify(model_or_height, frame, tolerance, errors=None, colors=None, normals=None):
+    """The surface of a surface model (surface_model's dictionary, or its height map alone) thinned to a right-triangle mesh whose
+    midpoint errors stay within `tolerance`, in the map's height units (include/ssrlcv_hip.h "surface simplification"): full
+    resolution where the map is rough and at hole boundaries, large triangles where it is flat.  No vertex is created: the
+    points are capi.dsm_points' gathered by `kept`.  errors: capi.dsm_simplify_errors' map of the same height map from an earlier
+    call -- it does not depend on the tolerance --, or None.  colors (surface_colors'), normals (surface_mesh's): one a vertex of
+    the full mesh, gathered too where given.
+    -> dict(points float32 (m, 3), faces int32 (T, 3) indexing them, kept int32 (m,): the vertices' indices in capi.dsm_points'
+    numbering, strictly ascending; vertex_index int32 (h, w): a kept cell's new index, -1 elsewhere; errors; colors, normals)."""
+    height = model_or_height["height"] if isinstance(model_or_height, dict) else model_or_height
+    pts, n = capi.dsm_points(height, frame)
+    node_index = capi.disparity_mesh(height, 1, float("inf"))[0]
+    errors = capi.dsm_simplify_errors(height) if errors is None else errors
+    faces, _, kept, _, vertex_index = capi.dsm_simplify_mesh(height, errors, tolerance, node_index)
+    gather = kept.to(torch.int64)
+    out = {"points": pts[gather], "faces": faces, "kept": kept, "vertex_index": vertex_index, "errors": errors}
+    if colors is not None:
+        out["colors"] = colors[gather]
+    if normals is not None:
+        out["normals"] = normals.view(-1, 3)[gather]
+    return out
+
+
 def surface_photo_check(model, frame, ortho, image, camera, max_jump=None, max_extent=8, want_map=False):
     """How well a textured surface model predicts a view's own pixels -- an accuracy measure that needs no reference surface: the
     model's mesh takes the greys of its ortho-image (surface_colors of surface_ortho's `ortho`), is drawn into `camera`
