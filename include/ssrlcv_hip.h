@@ -58,7 +58,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      surface registration: register_terms (+ its workspace query), transform_points, register_step_host,
  *      register_compose_host;
  *      mesh render: mesh_render (+ its workspace query), image_residual;
- *      surface simplification: dsm_simplify_errors, dsm_simplify_mesh (+ its workspace query) */
+ *      surface simplification: dsm_simplify_errors, dsm_simplify_mesh (+ its workspace query);
+ *      terrain filter: dsm_morphology, dsm_terrain (+ their workspace queries), dsm_subtract */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1527,6 +1528,89 @@ int ssrlcv_hip_dsm_simplify_mesh(const float* height, const float* error, uint32
                                  const uint32_t* nodeIndex /* may be NULL */, uint32_t* vertexIndex, uint32_t* out, uint32_t capacity,
                                  uint32_t* triCount_dev, uint32_t* kept, uint32_t keptCapacity, uint32_t* vertexCount_dev, void* workspace,
                                  size_t workspaceBytes, ssrlcv_stream_t stream);
+
+/* ---- terrain filter: the fused height map is a digital SURFACE model -- the top of whatever the cameras saw, buildings and trees
+ * included.  This section gives the ground under it (a terrain model) and the height of what stands on the ground (the normalised
+ * surface, height - terrain): grey-scale morphology of a height map, the progressive morphological filter on top of it (Zhang et
+ * al. 2003: the map is opened with growing square windows, and a cell that an opening lowers by more than a threshold is an
+ * object), and the map - map difference.  Erosion and dilation are selections: csrc/terrain.hip is held to a numpy restatement
+ * bit for bit (tests/terrain_ref.py, tests/test_gpu_terrain.py).  Maps as everywhere in this file: float[w h], pitch w.
+ *   validity    a cell is valid iff its bits are not 0x7FC00000; other NaNs, the infinities and -0 are valid values.
+ *   order       values are ordered by the integer key of the median filter ("disparity post-filters" item 4),
+ *               k(f) = b >= 0 ? b : b ^ 0x7FFFFFFF: a total order on bit patterns, so -0 < +0, every NaN has a place, and equal
+ *               keys are equal bits.
+ *   window      W_r(p) = the cells q of the image with |q.x - p.x| <= r and |q.y - p.y| <= r: clipped at the image, never padded.
+ *               The effective radius is min(radius, max(w, h) - 1), applied on the host first: UINT32_MAX is legal and means "the
+ *               whole map", and no kernel forms 2r + 1 of a radius the map does not hold.  radius == 0 is refused.
+ *   1 morphology  ssrlcv_hip_dsm_morphology, op = SSRLCV_MORPH_ERODE (0), _DILATE (1), _OPEN (2) or _CLOSE (3).
+ *     ERODE       out(p) = the value with the smallest key among the valid cells of W_r(p), whether or not p itself is valid;
+ *                 invalid iff the window holds no valid cell.
+ *     DILATE      the same with the largest key.
+ *     OPEN        O = DILATE(ERODE(in)), then O(p) = invalid wherever in(p) is invalid: holes stay holes.  For a valid p the result
+ *                 is always valid and k(O(p)) <= k(in(p)): every window that contains p has a minimum no larger than p, and the
+ *                 dilation at p takes the largest of the minima of such windows, the one centred on p among them.
+ *     CLOSE       the dual: ERODE(DILATE(in)) with the same mask, valid where `in` is and k(C(p)) >= k(in(p)).
+ *     outputs     out of place; every cell of `out` is written and nothing behind it; in == out is refused.  No arithmetic, no
+ *                 tolerance: the output bits are input bits or the invalid pattern.
+ *   2 terrain   ssrlcv_hip_dsm_terrain.  Z_0 = height; for k = 1 .. levels: O_k = OPEN(Z_{k-1}, radius[k-1]) as in item 1, and
+ *               Z_k = O_k.  In float32 with nothing contracted d = Z_{k-1}(p) - O_k(p); a valid cell is FLAGGED at level k iff
+ *               d > threshold[k-1].  The comparison is false for a NaN d, so inf - inf flags nothing, and no difference is ever
+ *               stored: NaN bit patterns cannot leak.
+ *     level       (uint8, may be NULL) 0 for a ground cell that was never flagged, k for the first level that flagged it, 255 for
+ *                 an invalid input cell.
+ *     terrain     the bits of height(p) where `level` would be 0, the invalid pattern everywhere else.
+ *     opened      (may be NULL) Z_levels.
+ *     schedule    the thresholds are the caller's: this interface knows nothing of slopes or cell sizes.  Zhang's schedule,
+ *                 t_1 = initial, t_k = min(initial + slope cell 2 (r_k - r_{k-1}), maximum), is MeshFactory::terrainSchedule and
+ *                 pipeline.terrain_schedule.
+ *     limit       an object flat enough, or wide enough, for the largest window to fit inside it is ground: an axis-aligned
+ *                 plateau of side >= 2 r_max + 1 is never flagged.  This is the method and not a defect.
+ *     border      windows are clipped, so a slope is opened lower within r cells of its uphill borders and may be flagged
+ *                 there.  On an exact plane every cell at least 2 (r_1 + ... + r_K) cells from every border has d = 0 at every
+ *                 level and is never flagged, even at threshold 0: the plane 0.3 i - 0.2 j + 1 on 80 x 70 with radii 1, 2, 4, 8
+ *                 and thresholds 0 flags 1136 cells, all of them within 7 cells of a border.
+ *   3 subtract  ssrlcv_hip_dsm_subtract.  out(p) = a(p) - b(p) in float32 where both are valid; a result that is a NaN is stored
+ *               as the invalid pattern (the sign and payload of inf - inf differ between hosts and the GPU and must not reach the
+ *               map); out(p) is invalid where either input is.  `out` may alias `a` or `b`.  height - filled terrain is the
+ *               normalised surface; the call is also the map - map sibling of ssrlcv_hip_dsm_difference, and its output goes to
+ *               ssrlcv_hip_difference_stats as it is.  No workspace.
+ * Refusals, decided on the host before any launch, the parameters before the buffers, in this order: SSRLCV_ERR_INVALID_ARG for
+ * params NULL, levels 0 or above 8, a radius that is 0 or not above the one before it, a threshold that is negative or not finite
+ * (terrain), op > 3 or radius 0 (morphology); then for w h >= 2^31; a map of 0 cells is then SSRLCV_OK and touches nothing; then
+ * SSRLCV_ERR_INVALID_ARG for a NULL map or workspace (level and opened may be NULL) and for in == out; then SSRLCV_ERR_WORKSPACE.
+ * Workspace (host only; computed in size_t; 0 for a refused or empty size), in whole maps of a256(4 w h) bytes:
+ *     morphology  2 a256(4 w h)     the result of the row pass and the running minima of the pass at work, the first result of
+ *                                   an OPEN or CLOSE waiting in `out`; at an effective radius up to 8 that result alone
+ *     terrain     4 a256(4 w h)     Z_{k-1}, the erosion, the result of the row pass, the running minima
+ * It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no atomics; no block waits for another: bit-equal run to run.  At
+ * an effective radius up to 8 an erosion or dilation is one launch that takes the 2r + 1 taps of a row and then of a column from a
+ * tile in LDS, 34 taps a cell at most; it won its A/B at every such radius.  Above 8 it is a row pass and a column pass, two
+ * launches, an opening four, and the work per cell and pass is O(1) whatever the radius: running minima over segments of 2r + 1
+ * cells from both ends (van Herk / Gil-Werman), never a walk over the window; no loop has a trip count per cell that grows with
+ * the radius.  Until its cells are written, `out` of such an OPEN or CLOSE holds the first of its two results.
+ * Out of scope: slope-adaptive or per-cell thresholds inside the kernel; discs or other windows that are not squares;
+ * cloth-simulation and TIN-densification ground filters; interpolating the terrain under objects with new values (close the
+ * footprints with ssrlcv_hip_stereo_fill_holes, which selects); pit removal before the filter (an opening leaves an isolated pit
+ * and its neighbours alone; CLOSE and ssrlcv_hip_dsm_subtract find pits); classifying the points of a cloud instead of the cells
+ * of a map; the terrain inside the surface registration. */
+#define SSRLCV_MORPH_ERODE 0
+#define SSRLCV_MORPH_DILATE 1
+#define SSRLCV_MORPH_OPEN 2
+#define SSRLCV_MORPH_CLOSE 3
+typedef struct {
+  uint32_t levels;       /* 1 .. 8 */
+  uint32_t radius[8];    /* strictly ascending over the first `levels` entries, each >= 1; the rest ignored */
+  float    threshold[8]; /* finite and >= 0 over the first `levels` entries */
+} ssrlcv_terrain_params; /* 68 bytes */
+size_t ssrlcv_hip_dsm_morphology_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_morphology(const float* in, float* out, uint32_t w, uint32_t h, uint32_t radius, uint32_t op, void* workspace,
+                              size_t workspaceBytes, ssrlcv_stream_t stream);
+size_t ssrlcv_hip_dsm_terrain_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_terrain(const float* height, uint32_t w, uint32_t h, const ssrlcv_terrain_params* params, float* terrain,
+                           uint8_t* level /* may be NULL */, float* opened /* may be NULL */, void* workspace, size_t workspaceBytes,
+                           ssrlcv_stream_t stream);
+int ssrlcv_hip_dsm_subtract(const float* a, const float* b, uint32_t w, uint32_t h, float* out, ssrlcv_stream_t stream);
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

@@ -74,7 +74,8 @@ def load():
                      "ssrlcv_hip_dsm_rasterize_workspace_bytes", "ssrlcv_hip_dsm_points_workspace_bytes",
                      "ssrlcv_hip_dsm_ortho_workspace_bytes", "ssrlcv_hip_difference_stats_workspace_bytes",
                      "ssrlcv_hip_register_terms_workspace_bytes", "ssrlcv_hip_mesh_render_workspace_bytes",
-                     "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes"):
+                     "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes", "ssrlcv_hip_dsm_morphology_workspace_bytes",
+                     "ssrlcv_hip_dsm_terrain_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -133,4 +134,6 @@ EXPORTED = [
     "ssrlcv_register_step_host", "ssrlcv_register_compose_host",
     "ssrlcv_hip_mesh_render_workspace_bytes", "ssrlcv_hip_mesh_render", "ssrlcv_hip_image_residual",
     "ssrlcv_hip_dsm_simplify_errors", "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes", "ssrlcv_hip_dsm_simplify_mesh",
+    "ssrlcv_hip_dsm_morphology_workspace_bytes", "ssrlcv_hip_dsm_morphology", "ssrlcv_hip_dsm_terrain_workspace_bytes",
+    "ssrlcv_hip_dsm_terrain", "ssrlcv_hip_dsm_subtract",
 ]

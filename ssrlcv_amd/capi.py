@@ -1228,6 +1228,62 @@ def dsm_simplify_mesh(height_d, error_d, tolerance, node_index_d=None, capacity=
     return faces[: min(nt, cap)], nt, kept[: min(nv, kcap)], nv, vertex_index
 
 
+# ------------------------------------------------------------------ terrain filter
+class TerrainParams(ctypes.Structure):
+    _fields_ = [("levels", c_u32), ("radius", c_u32 * 8), ("threshold", c_f32 * 8)]
+
+
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+MORPH_WHOLE_MAP = 0xFFFFFFFF  # radius: the window is the whole map
+
+
+def dsm_morphology(height_d, radius, op, out=None, workspace=None):
+    """Grey-scale morphology of a height map with the clipped square window of `radius` cells (ssrlcv_hip_dsm_morphology;
+    include/ssrlcv_hip.h "terrain filter" item 1): MORPH_ERODE takes the smallest valid value of the window, MORPH_DILATE the
+    largest, MORPH_OPEN the dilation of the erosion and MORPH_CLOSE the erosion of the dilation, both with the holes of the input
+    kept.  Selection only: every output is an input value or 0x7FC00000.  Out of place: -> a new float32 (h, w) tensor, or `out`.
+    The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    h, w = _disparity_map(height_d)
+    assert isinstance(radius, int) and not isinstance(radius, bool) and 0 <= radius <= 0xFFFFFFFF  # c_u32 would wrap it
+    assert isinstance(op, int) and not isinstance(op, bool) and 0 <= op <= 0xFFFFFFFF
+    ws = _filter_workspace(LIB.ssrlcv_hip_dsm_morphology_workspace_bytes, w, h, workspace)
+    res = torch.empty((h, w), dtype=torch.float32, device="cuda") if out is None else out
+    assert _disparity_map(res) == (h, w)
+    check(LIB.ssrlcv_hip_dsm_morphology(ptr(height_d), ptr(res), c_u32(w), c_u32(h), c_u32(radius), c_u32(op), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+    return res
+
+
+def dsm_terrain(height_d, radii, thresholds, want_level=True, want_opened=False, workspace=None):
+    """The progressive morphological ground filter (ssrlcv_hip_dsm_terrain; item 2): the map is opened with the windows of
+    `radii` (1 to 8 of them, strictly ascending) in turn, and a valid cell that level k's opening lowers by more than
+    thresholds[k - 1] is an object.  -> (terrain float32 (h, w): the height's bits at the ground cells, 0x7FC00000 elsewhere;
+    level uint8 (h, w) or None: 0 ground, k the first level that flagged the cell, 255 an invalid input cell; opened float32 (h, w)
+    or None: the last opening).  The workspace is reused if it is large enough.  Asynchronous on the current stream."""
+    h, w = _disparity_map(height_d)
+    radii, thresholds = [int(r) for r in radii], [float(t) for t in thresholds]
+    assert len(radii) == len(thresholds) <= 8 and all(0 <= r <= 0xFFFFFFFF for r in radii)
+    p = TerrainParams(len(radii), (c_u32 * 8)(*radii), (c_f32 * 8)(*thresholds))
+    ws = _filter_workspace(LIB.ssrlcv_hip_dsm_terrain_workspace_bytes, w, h, workspace)
+    terrain = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    level = torch.empty((h, w), dtype=torch.uint8, device="cuda") if want_level else None
+    opened = torch.empty((h, w), dtype=torch.float32, device="cuda") if want_opened else None
+    check(LIB.ssrlcv_hip_dsm_terrain(ptr(height_d), c_u32(w), c_u32(h), ctypes.byref(p), ptr(terrain), ptr(level), ptr(opened), ptr(ws),
+                                     c_sz(ws.numel()), stream_ptr()))
+    return terrain, level, opened
+
+
+def dsm_subtract(a_d, b_d, out=None):
+    """a - b of two maps of one grid in float32 (ssrlcv_hip_dsm_subtract; item 3): 0x7FC00000 where either is invalid or the
+    difference is a NaN.  height - filled terrain is the normalised surface; the result is the form difference_stats takes.
+    `out` may be a_d or b_d.  Asynchronous on the current stream."""
+    h, w = _disparity_map(a_d)
+    assert _disparity_map(b_d) == (h, w), "both maps have one grid"
+    res = torch.empty((h, w), dtype=torch.float32, device="cuda") if out is None else out
+    assert _disparity_map(res) == (h, w)
+    check(LIB.ssrlcv_hip_dsm_subtract(ptr(a_d), ptr(b_d), c_u32(w), c_u32(h), ptr(res), stream_ptr()))
+    return res
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

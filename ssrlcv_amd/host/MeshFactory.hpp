@@ -320,6 +320,105 @@ class MeshFactory {
     return out;
   }
 
+  // ---- the terrain filter (include/ssrlcv_hip.h "terrain filter"): the ground under a surface model and the heights of what
+  // stands on it.  extractTerrain(height, w, h, radii, thresholds) gives the bare earth with the objects' footprints cut out;
+  // DisparityFactory::fillHoles closes them (a height map has a disparity map's form); objectHeights(height, terrain, w, h) is
+  // the normalised surface.  The maps are left in the state they came in; the results are in state gpu.
+
+  // the windows and thresholds of the progressive morphological filter (Zhang et al. 2003): radii 1, 2, 4, ... with maxRadius as
+  // the last entry if it is not one of them, unless `radii` comes filled; t_1 = initial, t_k = min(initial + slope cell 2 (r_k -
+  // r_{k-1}), maximum), computed in double and rounded to float once.  false if that takes more than 8 levels or the radii
+  // are not ascending from 1
+  static bool terrainSchedule(double cell, unsigned int maxRadius, double slope, double initial, double maximum, std::vector<uint32_t>& radii,
+                              std::vector<float>& thresholds) {
+    if (radii.empty()) {
+      for (uint64_t r = 1; r < maxRadius; r *= 2) radii.push_back((uint32_t)r);
+      radii.push_back(maxRadius);
+    }
+    thresholds.clear();
+    if (radii.size() > 8 || radii[0] < 1) return false;
+    thresholds.push_back((float)initial);
+    for (size_t k = 1; k < radii.size(); ++k) {
+      if (radii[k] <= radii[k - 1]) return false;
+      thresholds.push_back((float)std::min(initial + slope * cell * 2.0 * (double)(radii[k] - radii[k - 1]), maximum));
+    }
+    return true;
+  }
+
+  // ERODE (op 0), DILATE (1), OPEN (2) or CLOSE (3) of a w x h map with the clipped square window of `radius` cells; null for
+  // an empty grid or a refused call
+  static ptr::value<Unity<float>> morphology(ptr::value<Unity<float>> height, unsigned int w, unsigned int h, unsigned int radius, unsigned int op) {
+    const unsigned long cells = (unsigned long)w * h;
+    if (height == nullptr || cells == 0 || height->size() != cells) {
+      logger.err << "MeshFactory::morphology: the map has w h entries";
+      return ptr::value<Unity<float>>();
+    }
+    MemoryState origin = height->getMemoryState();
+    if (origin != gpu) height->setMemoryState(gpu);
+    const size_t wsb = ssrlcv_hip_dsm_morphology_workspace_bytes(w, h);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::value<Unity<float>> out(nullptr, cells, gpu);
+    const int status = ssrlcv_hip_dsm_morphology(height->device.get(), out->device.get(), w, h, radius, op, ws.get(), wsb, nullptr);
+    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+    if (origin != gpu) height->setMemoryState(origin);
+    if (status != SSRLCV_OK) {
+      logger.err.printf("MeshFactory::morphology: refused (%s)", ssrlcv_hip_status_string(status));
+      return ptr::value<Unity<float>>();
+    }
+    return out;
+  }
+
+  // the bare earth of a w x h height map: the height at the cells no level of the filter flagged, 0x7FC00000 elsewhere.
+  // *level, when asked for: 0 ground, k the first level that flagged the cell, 255 an invalid cell.  Null for a refused call
+  static ptr::value<Unity<float>> extractTerrain(ptr::value<Unity<float>> height, unsigned int w, unsigned int h, const std::vector<uint32_t>& radii,
+                                                 const std::vector<float>& thresholds, ptr::value<Unity<unsigned char>>* level = nullptr) {
+    const unsigned long cells = (unsigned long)w * h;
+    if (height == nullptr || cells == 0 || height->size() != cells || radii.empty() || radii.size() > 8 || radii.size() != thresholds.size()) {
+      logger.err << "MeshFactory::extractTerrain: the map has w h entries, and 1 to 8 radii a threshold each";
+      return ptr::value<Unity<float>>();
+    }
+    ssrlcv_terrain_params params = {};
+    params.levels = (uint32_t)radii.size();
+    for (size_t k = 0; k < radii.size(); ++k) {
+      params.radius[k] = radii[k];
+      params.threshold[k] = thresholds[k];
+    }
+    MemoryState origin = height->getMemoryState();
+    if (origin != gpu) height->setMemoryState(gpu);
+    const size_t wsb = ssrlcv_hip_dsm_terrain_workspace_bytes(w, h);
+    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    ptr::value<Unity<float>> terrain(nullptr, cells, gpu);
+    if (level) *level = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
+    const int status = ssrlcv_hip_dsm_terrain(height->device.get(), w, h, &params, terrain->device.get(), level ? (*level)->device.get() : nullptr, nullptr,
+                                              ws.get(), wsb, nullptr);
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    if (origin != gpu) height->setMemoryState(origin);
+    if (status != SSRLCV_OK) {
+      logger.err.printf("MeshFactory::extractTerrain: refused (%s)", ssrlcv_hip_status_string(status));
+      if (level) *level = ptr::value<Unity<unsigned char>>();
+      return ptr::value<Unity<float>>();
+    }
+    return terrain;
+  }
+
+  // height - terrain where both are valid and the difference is a number, 0x7FC00000 elsewhere: the form differenceStats takes
+  static ptr::value<Unity<float>> objectHeights(ptr::value<Unity<float>> height, ptr::value<Unity<float>> terrain, unsigned int w, unsigned int h) {
+    const unsigned long cells = (unsigned long)w * h;
+    if (height == nullptr || terrain == nullptr || cells == 0 || height->size() != cells || terrain->size() != cells) {
+      logger.err << "MeshFactory::objectHeights: both maps have w h entries";
+      return ptr::value<Unity<float>>();
+    }
+    MemoryState originA = height->getMemoryState(), originB = terrain->getMemoryState();
+    if (originA != gpu) height->setMemoryState(gpu);
+    if (originB != gpu) terrain->setMemoryState(gpu);
+    ptr::value<Unity<float>> out(nullptr, cells, gpu);
+    HipSafeCall(ssrlcv_hip_dsm_subtract(height->device.get(), terrain->device.get(), w, h, out->device.get(), nullptr));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    if (originA != gpu) height->setMemoryState(originA);
+    if (originB != gpu && terrain != height) terrain->setMemoryState(originB);
+    return out;
+  }
+
   // the valid cells of a height map become this factory's points, in raster order: the vertex numbering of
   // DisparityFactory::generateMesh(height, 1, maxJump), so that mesh is the surface of these points
   void setPointsFromHeightMap(ptr::value<Unity<float>> height, const ssrlcv_dsm_frame& frame) {

@@ -493,6 +493,59 @@ def surface_simplify(model_or_height, frame, tolerance, errors=None, colors=None
     return out
 
 
+def terrain_schedule(cell, max_radius, slope, initial, maximum, radii=None):
+    """The windows and thresholds of the progressive morphological filter (Zhang et al. 2003) for capi.dsm_terrain; host only.
+    cell: the side of a cell in the map's height units; slope: the steepest terrain to keep, rise over run; initial, maximum: the
+    first and the largest threshold.  radii default to 1, 2, 4, ... with max_radius as the last entry if it is not one of them;
+    ValueError if that takes more than 8 levels -- pass `radii` then.  t_1 = initial, t_k = min(initial + slope cell 2 (r_k -
+    r_{k-1}), maximum): Zhang's dh_k for windows of 2r + 1 cells, computed in double and rounded to float32 once.
+    -> (radii, thresholds): lists of int and of float."""
+    if radii is None:
+        radii, r = [], 1
+        while r < int(max_radius):
+            radii.append(r)
+            r *= 2
+        radii.append(int(max_radius))
+    radii = [int(r) for r in radii]
+    if not 1 <= len(radii) <= 8:
+        raise ValueError("the filter has 1 to 8 levels, not %d: pass radii" % len(radii))
+    if radii[0] < 1 or any(b <= a for a, b in zip(radii, radii[1:])):
+        raise ValueError("radii are at least 1 and strictly ascending, not %r" % (radii,))
+    thresholds = [float(np.float32(float(initial)))]
+    for a, b in zip(radii, radii[1:]):
+        thresholds.append(float(np.float32(min(float(initial) + float(slope) * float(cell) * 2.0 * (b - a), float(maximum)))))
+    return radii, thresholds
+
+
+def surface_terrain(model_or_height, frame, max_radius, slope, initial, maximum, radii=None,
+                    fill=dict(paths=0xFF, max_gap=None, min_hits=1, rule="median"), want_level=True):
+    """The bare earth under a surface model (surface_model's dictionary, or its height map alone) and the heights of what stands
+    on it (include/ssrlcv_hip.h "terrain filter"): the progressive morphological filter on terrain_schedule(frame.cell,
+    max_radius, slope, initial, maximum, radii), the footprints it cuts out closed by capi.stereo_fill_holes -- fill =
+    dict(paths=, max_gap=, min_hits=, rule=), max_gap None for no limit; fill=None leaves them open --, and height - terrain.
+    An object that holds a whole window of max_radius is ground: choose max_radius above half the widest building, in cells.
+    -> dict(ground: bool (h, w), the valid cells no level flagged; level: uint8 (h, w) or None, 0 ground, k the first level that
+    flagged the cell, 255 no cell; bare: the height at the ground cells, 0x7FC00000 elsewhere; terrain: `bare` with its holes
+    filled; objects: height - terrain; radii, thresholds).  `terrain` is a height map like any other: surface_mesh and
+    surface_simplify take dict(height=terrain), surface_accuracy measures it against a bare-earth reference, and
+    difference_stats(objects) gives the statistics of the object heights."""
+    height = model_or_height["height"] if isinstance(model_or_height, dict) else model_or_height
+    radii, thresholds = terrain_schedule(float(frame.cell), max_radius, slope, initial, maximum, radii)
+    bare, level, _ = capi.dsm_terrain(height, radii, thresholds, want_level=want_level)
+    terrain = bare
+    if fill is not None:
+        if not isinstance(fill, dict) or set(fill) - {"paths", "max_gap", "min_hits", "rule"}:
+            raise TypeError("fill = dict(paths=, max_gap=, min_hits=, rule=) or None")
+        if fill.get("rule", "median") not in _FILL_RULES:
+            raise ValueError("rule is 'min' or 'median', not %r" % (fill["rule"],))
+        gap = fill.get("max_gap")
+        terrain = capi.stereo_fill_holes(bare, fill.get("paths", 0xFF), capi.FILL_NO_LIMIT if gap is None else gap, fill.get("min_hits", 1),
+                                         _FILL_RULES[fill.get("rule", "median")])[0]
+    ground = bare.view(torch.int32) != 0x7FC00000
+    return {"ground": ground, "level": level, "bare": bare, "terrain": terrain, "objects": capi.dsm_subtract(height, terrain),
+            "radii": radii, "thresholds": thresholds}
+
+
 def surface_photo_check(model, frame, ortho, image, camera, max_jump=None, max_extent=8, want_map=False):
     """How well a textured surface model predicts a view's own pixels -- an accuracy measure that needs no reference surface: the
     model's mesh takes the greys of its ortho-image (surface_colors of surface_ortho's `ortho`), is drawn into `camera`
