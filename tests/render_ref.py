@@ -53,16 +53,21 @@ def edge(ax, ay, bx, by, cx, cy):
     return int32(int32(int32(bx - ax) * int32(cy - ay)) - int32(int32(by - ay) * int32(cx - ax)))
 
 
-def triangles(vertex_index, cells):
-    """every emitted triangle in id order -> list of (id, (ip, iq, ir)): the vertexIndex entries of its corners p, q, r"""
+def triangles(vertex_index, cells, loop=False):
+    """every emitted triangle in id order -> list of (id, (ip, iq, ir)): the vertexIndex entries of its corners p, q, r.  loop:
+    visit every cell in turn, the plain form; without it only the cells that emit one, in the same raster order (a grid of
+    millions of cells that holds a few quads; tests/test_large_cases.py holds the two forms to each other)"""
     out = []
     gw = vertex_index.shape[1]
-    for j in range(cells.shape[0]):
-        for i in range(cells.shape[1]):
-            byte = int(cells[j, i])
-            for t, tri in enumerate(M.TRIANGLES[bool(byte & 4)]):
-                if byte >> t & 1:
-                    out.append((2 * (j * (gw - 1) + i) + t, tuple(int(vertex_index[j + dj, i + di]) for di, dj in tri)))
+    if loop:
+        visit = ((j, i) for j in range(cells.shape[0]) for i in range(cells.shape[1]))
+    else:
+        visit = zip(*(a.tolist() for a in np.nonzero(np.asarray(cells) & 3)))
+    for j, i in visit:
+        byte = int(cells[j, i])
+        for t, tri in enumerate(M.TRIANGLES[bool(byte & 4)]):
+            if byte >> t & 1:
+                out.append((2 * (j * (gw - 1) + i) + t, tuple(int(vertex_index[j + dj, i + di]) for di, dj in tri)))
     return out
 
 

@@ -31,8 +31,8 @@ def cviews(capi, views, images_d):
     return arr
 
 
-def ortho_call(capi, c, want_seen=True, want_which=True):
-    """the raw call with guard words around every output, a workspace pre-filled with 0xFF and checked behind its size, and the
+def ortho_call(capi, c, want_seen=True, want_which=True, fill=0xFF):
+    """the raw call with guard words around every output, a workspace pre-filled with `fill` and checked behind its size, and the
     inputs compared with what was uploaded -> dict of uint8 (h, w), None for an output not asked for"""
     fr = c.frame
     cells = fr.w * fr.h
@@ -44,14 +44,14 @@ def ortho_call(capi, c, want_seen=True, want_which=True):
     images_d = [uploaded[id(v.image)] for v in c.views]
     need = int(capi.LIB.ssrlcv_hip_dsm_ortho_workspace_bytes(u32(fr.w), u32(fr.h), u32(len(c.views))))
     assert need == 256
-    ws = torch.full((need + 256,), 0xFF, dtype=torch.uint8, device="cuda")
+    ws = torch.full((need + 256,), fill, dtype=torch.uint8, device="cuda")
     out = {"ortho": Guarded(cells, torch.uint8), "seen": Guarded(cells, torch.uint8) if want_seen else None,
            "which": Guarded(cells, torch.uint8) if want_which else None}
     params = capi.OrthoParams(c.max_steps, c.bias, c.rule)
     capi.check(capi.LIB.ssrlcv_hip_dsm_ortho(vp(height_d.data_ptr()), ctypes.byref(cframe(capi, fr)), cviews(capi, c.views, images_d), u32(len(c.views)),
                                              ctypes.byref(params), *[out[k].ptr if out[k] else vp(0) for k in OUTPUTS], vp(ws.data_ptr()), csz(need),
                                              capi.stream_ptr()))
-    assert (ws[need:] == 0xFF).all(), "the workspace was written behind its size"
+    assert (ws[need:] == fill).all(), "the workspace was written behind its size"
     assert height_d.cpu().numpy().tobytes() == np.ascontiguousarray(c.height).tobytes()   # the inputs are left alone
     for v in c.views:
         assert uploaded[id(v.image)].cpu().numpy().tobytes() == v.image.tobytes()
