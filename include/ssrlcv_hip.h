@@ -59,7 +59,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      register_compose_host;
  *      mesh render: mesh_render (+ its workspace query), image_residual;
  *      surface simplification: dsm_simplify_errors, dsm_simplify_mesh (+ its workspace query);
- *      terrain filter: dsm_morphology, dsm_terrain (+ their workspace queries), dsm_subtract */
+ *      terrain filter: dsm_morphology, dsm_terrain (+ their workspace queries), dsm_subtract;
+ *      shift search: shift_search (+ its workspace query), shift_table_bytes, shift_pick_host */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1259,8 +1260,9 @@ int ssrlcv_hip_dsm_ortho(const float* height, const ssrlcv_dsm_frame* frame, con
  * rank, all quantiles in the same passes, equal prefixes sharing a histogram.  Counts, min and max are integer atomics, one a
  * block.  Integer atomics commute and the sums have a fixed shape: the record is bit-equal run to run and to the restatement.
  * Out of scope, not built: differences along a direction other than the frame's ez; ray casts against unorganised meshes;
- * a shift search; float atomics; weighted statistics.  Registration -- a cloud that lies off in x / y shows every slope of the
- * terrain as height error -- is the next section, "surface registration". */
+ * float atomics; weighted statistics.  Registration -- a cloud that lies off in x / y shows every slope of the
+ * terrain as height error -- is the next section, "surface registration"; a cloud that lies many cells off goes through the
+ * section behind it, "shift search", first. */
 typedef struct {
   float center;          /* finite: subtracted from every valid entry */
   uint32_t absolute;     /* 0 or 1: fabsf of the difference to center */
@@ -1344,8 +1346,9 @@ int ssrlcv_hip_difference_stats(const float* values, uint32_t n, const ssrlcv_di
  * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  The counts are INTEGER atomics, one
  * a block; the sums have a fixed shape; there are no float atomics: the record is bit-equal run to run and to the restatement.
  * The transform uses no atomics.
- * Out of scope, not built: a coarse shift search over many cells (the caller passes an initial pose); robust weights other than
- * the gate; cloud-to-cloud ICP; pushbroom geometry; re-running stereo. */
+ * Out of scope, not built: robust weights other than the gate; cloud-to-cloud ICP; pushbroom geometry; re-running stereo.  The
+ * steps converge from about a cell off: the initial pose of a cloud that lies further off comes from the next section, "shift
+ * search". */
 typedef struct {
   float m[12];    /* [M | T], 3 x 4 row-major: p' = M p + T */
   float pivot[3]; /* the point steps rotate and scale about */
@@ -1368,6 +1371,99 @@ int ssrlcv_hip_transform_points(const ssrlcv_float3* points, uint32_t n, const s
                                 ssrlcv_stream_t stream);
 int ssrlcv_register_step_host(const ssrlcv_register_terms* record, uint32_t dofMask, double lambda, double* delta /* [7] */); /* host only */
 int ssrlcv_register_compose_host(const ssrlcv_register_pose* pose, const double* delta /* [7] */, ssrlcv_register_pose* out); /* host only */
+
+/* ---- shift search: the whole-cell shift between two height maps of one grid, over every shift of a window at once -- what
+ * translatePointCloud by hand does upstream before calculateAverageDifference, and what stands between "a cloud somewhere near
+ * the reference" and the point-to-plane steps of "surface registration", which follow the wrong slopes from tens of cells off.
+ * One GPU call fills a table with the count, the sum and the sum of squares of the height differences of every shift; one host
+ * call picks the shift of least variance, which an unknown height bias does not move.  Everything is an int32 or int64
+ * expression, apart from one float multiplication and one rintf a cell, so the table does not depend on the order of summation:
+ * csrc/shift.hip is held to a numpy restatement byte for byte (tests/shift_ref.py, tests/test_gpu_shift.py).
+ *   maps        moving[w h] and reference[w h]: float32 height maps of one grid, pitch w; a cell that is any NaN is invalid (the
+ *               maps here use 0x7FC00000).  The moving map is what ssrlcv_hip_dsm_rasterize makes of the subject cloud in the
+ *               reference's frame.  Neither is written.
+ *   quantise    a cell of height x becomes t = x * scale, one float32 multiplication; it is valid iff fabsf(t) <= 65536.0f, which is
+ *               false for a NaN; then q = (int32)rintf(t), ties to even.  A cell whose x is finite and that fails the test is
+ *               CLIPPED: it counts as invalid and is counted once per map.
+ *   sampling    with stride g only the cells (i g, j g) exist, i < ceil(w / g), j < ceil(h / g): the search at stride g is, by
+ *               definition, the search at stride 1 on the two maps sampled that way, and every shift, centre and count below is
+ *               in sampled cells.
+ *   shifts      kx, ky = -S .. S, S = radius; the shift is (sx, sy) = (centerX + kx, centerY + ky); its entry has the index
+ *               (ky + S) (2S + 1) + (kx + S).
+ *   entry       over all sampled cells (x, y) where moving is valid, (x + sx, y + sy) lies inside the sampled grid and reference is
+ *               valid there: d = qm(x, y) - qr(x + sx, y + sy), which takes part iff |d - centerQ| <= gateQ; gateQ = UINT32_MAX
+ *               means no test.  ssrlcv_shift_entry: n (uint32), reserved = 0, sum = the sum of d (int64), sumSq = the sum of d d
+ *               (uint64).  A shift with no such cell holds zeros.
+ *   head        ssrlcv_shift_table: validMoving, validReference, clippedMoving, clippedReference, over the sampled cells.
+ *   table       in DEVICE memory: the 16-byte head, then (2S + 1)^2 entries of 24 bytes; ssrlcv_shift_table_bytes gives the size
+ *               (0 for a radius above 32).  Every byte of it is written, reserved words as 0, and nothing behind it.
+ *   limits      S = 0 .. 32; g >= 1; |centerX|, |centerY| <= 2^24; |centerQ| <= 2^18; scale finite and > 0; at most 2^28 sampled
+ *               cells, so that sumSq <= 2^34 2^28 fits.  No index wraps for any legal centre: a shift that leaves the grid
+ *               altogether has an entry of zeros.
+ *   pick        ssrlcv_shift_pick_host (host only, in double, no device) reads a HOST copy of the table.
+ *     candidates  the entries with n >= max(minOverlap, 1).
+ *     score       mean = (double)sum / (double)n;  v = (double)sumSq / (double)n - mean * mean;  every operation rounded on its own,
+ *                 nothing contracted.
+ *     best        the smallest v; ties go to the smaller kx^2 + ky^2, then to the smaller ky, then to the smaller kx.
+ *     step        per axis, from v at the two neighbours of the best shift along it: both must be candidates inside the table,
+ *                 else the step is 0.  den = (vminus - v0) + (vplus - v0); if den > 0 the step is 0.5 (vminus - vplus) / den,
+ *                 clamped to -0.5 .. 0.5; else 0.
+ *     record      ssrlcv_shift_result: shiftX, shiftY = g (center + k), in cells of the full grid (int64); subX, subY = the
+ *                 step times (double)g; bias = mean / (double)scale; variance = v / s2 with s2 = (double)scale (double)scale;
+ *                 second = the smallest v / s2 among the candidates outside the 3 x 3 around the best, +inf if there is none;
+ *                 n of the best entry; candidates = how many there were.
+ *     refusals    SSRLCV_ERR_INVALID_ARG for a NULL, refused params or a tableBytes that is not the size of the params' radius; then
+ *                 SSRLCV_ERR_UNSUPPORTED when there is no candidate.  `out` is untouched on error.
+ *   sign        a best shift s says that moving(x) shows what reference(x + s) shows: the cloud has to move by +s cells along
+ *               ex, ey and by -bias along ez.
+ * Refusals of the device call, decided on the host before any launch, the parameters before the sizes before the buffers:
+ * SSRLCV_ERR_INVALID_ARG for a NULL params, a scale that is not finite and > 0, stride 0, radius > 32, |centerX| or |centerY|
+ * > 2^24, |centerQ| > 2^18; then SSRLCV_ERR_UNSUPPORTED for w or h above 2^24 or more than 2^28 sampled cells; then
+ * SSRLCV_ERR_INVALID_ARG for a table that is NULL or not 8-byte aligned; an empty grid (w h = 0) then writes the all-zero table
+ * and is SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL moving, reference or workspace; then SSRLCV_ERR_WORKSPACE.
+ * Workspace (host only; computed in size_t; 0 for refused params, a refused size or an empty grid), a256 as in "disparity mesh":
+ *     2 a256(4 ceil(w / g) ceil(h / g))
+ *   the int32 keys of both sampled maps, INT32_MIN for an invalid cell.  It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another.  A quantise pass, a thread a sampled
+ * cell of both maps, writes the keys, so the stride is gone before the search; the head counts are INTEGER atomics, one a wave
+ * and counter at most.  In the search pass lanes own shifts, not cells: a block stages a 64 x 16 tile of moving keys and the
+ * reference tile with a halo of S cells in LDS, walks the tile's cells -- the moving key is one LDS word for the whole wave, and
+ * an invalid one skips the cell for the whole wave -- and every lane keeps n, sum and sumSq of its shifts in registers: no
+ * cross-lane reduction anywhere.  The grid is capped, blocks stride over the tiles, and each (block, shift) is flushed once by
+ * 64-bit INTEGER atomics.  Integer atomics commute and there are no float atomics: the table is bit-equal run to run and to the
+ * restatement.
+ * Out of scope, not built: rotation or scale in the search; a sub-cell search by resampling (the step above is a parabola through
+ * three scores); scores other than the variance (correlation coefficients, truncated costs); an FFT form; radii above 32 (use
+ * strides); searching against the reference's mesh instead of its cells; pushbroom geometry. */
+typedef struct {
+  float scale;      /* finite, > 0: quanta a height unit */
+  uint32_t stride;  /* g >= 1 */
+  int32_t centerX;  /* in sampled cells, |centerX| <= 2^24 */
+  int32_t centerY;
+  uint32_t radius;  /* S = 0 .. 32 */
+  int32_t centerQ;  /* in quanta, |centerQ| <= 2^18 */
+  uint32_t gateQ;   /* in quanta; UINT32_MAX: no test */
+} ssrlcv_shift_params; /* 28 bytes */
+typedef struct {
+  uint32_t n, reserved;
+  int64_t sum;
+  uint64_t sumSq;
+} ssrlcv_shift_entry; /* 24 bytes */
+typedef struct {
+  uint32_t validMoving, validReference, clippedMoving, clippedReference;
+} ssrlcv_shift_table; /* 16 bytes: the head; (2 radius + 1)^2 ssrlcv_shift_entry follow it */
+typedef struct {
+  int64_t shiftX, shiftY; /* the best shift in cells of the full grid */
+  double subX, subY;      /* the sub-cell step, in cells of the full grid */
+  double bias, variance, second;
+  uint32_t n, candidates;
+} ssrlcv_shift_result; /* 64 bytes */
+size_t ssrlcv_shift_table_bytes(uint32_t radius); /* host only */
+size_t ssrlcv_hip_shift_search_workspace_bytes(uint32_t w, uint32_t h, const ssrlcv_shift_params* params);
+int ssrlcv_hip_shift_search(const float* moving, const float* reference, uint32_t w, uint32_t h, const ssrlcv_shift_params* params,
+                            ssrlcv_shift_table* table, void* workspace, size_t workspaceBytes, ssrlcv_stream_t stream);
+int ssrlcv_shift_pick_host(const ssrlcv_shift_table* table_host, size_t tableBytes, const ssrlcv_shift_params* params, uint32_t minOverlap,
+                           ssrlcv_shift_result* out); /* host only */
 
 /* ---- mesh render: the grid mesh drawn into a pinhole view -- a z-buffered rasterisation that gives the depth map of the model in
  * that view, the triangle under every pixel, and the vertices' greys carried into the image.  Compared with the view's own

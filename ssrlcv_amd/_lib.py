@@ -75,7 +75,7 @@ def load():
                      "ssrlcv_hip_dsm_ortho_workspace_bytes", "ssrlcv_hip_difference_stats_workspace_bytes",
                      "ssrlcv_hip_register_terms_workspace_bytes", "ssrlcv_hip_mesh_render_workspace_bytes",
                      "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes", "ssrlcv_hip_dsm_morphology_workspace_bytes",
-                     "ssrlcv_hip_dsm_terrain_workspace_bytes"):
+                     "ssrlcv_hip_dsm_terrain_workspace_bytes", "ssrlcv_shift_table_bytes", "ssrlcv_hip_shift_search_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -136,4 +136,5 @@ EXPORTED = [
     "ssrlcv_hip_dsm_simplify_errors", "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes", "ssrlcv_hip_dsm_simplify_mesh",
     "ssrlcv_hip_dsm_morphology_workspace_bytes", "ssrlcv_hip_dsm_morphology", "ssrlcv_hip_dsm_terrain_workspace_bytes",
     "ssrlcv_hip_dsm_terrain", "ssrlcv_hip_dsm_subtract",
+    "ssrlcv_shift_table_bytes", "ssrlcv_hip_shift_search_workspace_bytes", "ssrlcv_hip_shift_search", "ssrlcv_shift_pick_host",
 ]

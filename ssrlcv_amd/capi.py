@@ -1284,6 +1284,68 @@ def dsm_subtract(a_d, b_d, out=None):
     return res
 
 
+# ------------------------------------------------------------------ shift search
+class ShiftParams(ctypes.Structure):
+    """ssrlcv_shift_params: q = rint(height x scale); shifts (centerX + kx, centerY + ky), kx, ky = -radius .. radius, in cells of
+    the grid sampled at `stride`; a difference d takes part iff |d - centerQ| <= gateQ (SHIFT_NO_GATE: always)"""
+    _fields_ = [("scale", c_f32), ("stride", c_u32), ("centerX", ctypes.c_int32), ("centerY", ctypes.c_int32), ("radius", c_u32),
+                ("centerQ", ctypes.c_int32), ("gateQ", c_u32)]
+
+
+class ShiftResult(ctypes.Structure):
+    """ssrlcv_shift_result: the record ssrlcv_shift_pick_host writes"""
+    _fields_ = [("shiftX", ctypes.c_int64), ("shiftY", ctypes.c_int64), ("subX", ctypes.c_double), ("subY", ctypes.c_double),
+                ("bias", ctypes.c_double), ("variance", ctypes.c_double), ("second", ctypes.c_double), ("n", c_u32), ("candidates", c_u32)]
+
+
+assert ctypes.sizeof(ShiftParams) == 28 and ctypes.sizeof(ShiftResult) == 64
+
+SHIFT_NO_GATE = 0xFFFFFFFF
+SHIFT_MAX_RADIUS = 32
+SHIFT_HEAD = np.dtype([("validMoving", "<u4"), ("validReference", "<u4"), ("clippedMoving", "<u4"), ("clippedReference", "<u4")])
+SHIFT_ENTRY = np.dtype([("n", "<u4"), ("reserved", "<u4"), ("sum", "<i8"), ("sumSq", "<u8")])
+assert SHIFT_HEAD.itemsize == 16 and SHIFT_ENTRY.itemsize == 24
+
+
+def shift_search(moving, reference, scale, stride=1, center=(0, 0), radius=8, center_q=0, gate_q=None, ws=None):
+    """The differences of two height maps of one grid at every whole-cell shift of a window (ssrlcv_hip_shift_search;
+    include/ssrlcv_hip.h "shift search").  moving, reference: float32 (h, w) device tensors, any NaN an invalid cell; heights are
+    quantised to rint(height x scale); with `stride` g only the cells (i g, j g) take part, and center and radius are in cells
+    of that sampled grid; gate_q None: no gate.  -> dict(params: the ShiftParams; head: the four counts as a SHIFT_HEAD record;
+    entries: a SHIFT_ENTRY array (2 radius + 1, 2 radius + 1), [ky + radius, kx + radius] the shift center + (kx, ky); bytes: the
+    table as the device wrote it).  The workspace is reused if it is large enough.  One synchronisation (the table)."""
+    h, w = _disparity_map(moving)
+    assert _disparity_map(reference) == (h, w), "both maps have one grid"
+    ints = [int(stride), int(center[0]), int(center[1]), int(radius), int(center_q), SHIFT_NO_GATE if gate_q is None else int(gate_q)]
+    assert 0 <= ints[0] <= 0xFFFFFFFF and 0 <= ints[3] <= 0xFFFFFFFF and 0 <= ints[5] <= 0xFFFFFFFF   # c_u32 would wrap them
+    assert all(-(1 << 31) <= v < (1 << 31) for v in (ints[1], ints[2], ints[4]))
+    params = ShiftParams(float(scale), *ints)
+    size = int(LIB.ssrlcv_shift_table_bytes(c_u32(ints[3])))
+    need = int(LIB.ssrlcv_hip_shift_search_workspace_bytes(c_u32(w), c_u32(h), ctypes.byref(params)))
+    work = ws if ws is not None and ws.numel() >= max(need, 1) else dev_bytes(need)
+    table = torch.empty(max(size, 8) // 8, dtype=torch.int64, device="cuda")       # 8-byte aligned
+    check(LIB.ssrlcv_hip_shift_search(ptr(moving) if w * h else c_vp(0), ptr(reference) if w * h else c_vp(0), c_u32(w), c_u32(h), ctypes.byref(params),
+                                      ptr(table), ptr(work), c_sz(work.numel()), stream_ptr()))
+    raw = table.cpu().numpy().view(np.uint8)[:size].copy()
+    side = 2 * ints[3] + 1
+    return {"params": params, "head": raw[:16].view(SHIFT_HEAD)[0], "entries": raw[16:].view(SHIFT_ENTRY).reshape(side, side), "bytes": raw}
+
+
+def shift_pick(table, params, min_overlap):
+    """ssrlcv_shift_pick_host (host arithmetic: needs no GPU): among the entries with n >= max(min_overlap, 1) the shift of least
+    variance of the differences, the sub-cell step from its neighbours' variances, the height bias and the runner-up outside its
+    3 x 3.  table: shift_search's dictionary, or the table's bytes as a uint8 array.  -> a ShiftResult, or None when no entry
+    has that many cells."""
+    raw = np.ascontiguousarray(table["bytes"] if isinstance(table, dict) else table, dtype=np.uint8)
+    assert 0 <= int(min_overlap) <= 0xFFFFFFFF
+    out = ShiftResult()
+    rc = LIB.ssrlcv_shift_pick_host(raw.ctypes.data_as(c_vp), c_sz(raw.size), ctypes.byref(params), c_u32(int(min_overlap)), ctypes.byref(out))
+    if rc == -4:   # SSRLCV_ERR_UNSUPPORTED
+        return None
+    check(rc)
+    return out
+
+
 # ------------------------------------------------------------------ SIFT pipeline
 class SiftPlan:
     """Owns an ssrlcv_sift_plan and (optionally) the workspace tensor for one W x H image slot."""

@@ -718,7 +718,14 @@ class MeshFactory {
 
   Registration registerToReference(ptr::value<Unity<float3>> cloud, uint32_t dofMask = 0x3Fu, unsigned iterations = 8, float gateFactor = 3.0f,
                                    double damping = 0.0) {
+    return registerToReference(cloud, Registration().pose, dofMask, iterations, gateFactor, damping);
+  }
+
+  // the same from a start pose -- searchShift's, for a cloud that lies many cells off; its pivot is replaced like the identity's
+  Registration registerToReference(ptr::value<Unity<float3>> cloud, const ssrlcv_register_pose& start, uint32_t dofMask = 0x3Fu, unsigned iterations = 8,
+                                   float gateFactor = 3.0f, double damping = 0.0) {
     Registration reg;
+    reg.pose = start;
     if (!hasReference || cloud == nullptr || cloud->size() == 0 || cloud->size() > 0xFFFFFFFFul) {
       logger.err << "MeshFactory::registerToReference: needs a reference surface (setReferenceSurface) and points";
       return reg;
@@ -803,6 +810,123 @@ class MeshFactory {
     }
     if (origin == cpu) cloud->setMemoryState(cpu);
     return reg;
+  }
+
+  // ---- shift search (include/ssrlcv_hip.h "shift search"): the whole-cell shift that lays a height map tens of cells off onto a
+  // reference map of the same grid, coarse to fine -- pipeline.surface_shift_search on two maps, call for call.  `moving` is
+  // generateHeightMap(frame, rule) of the subject cloud.  One ssrlcv_hip_shift_search a level: the first at strides[0], centred on
+  // 0 with `radius`; each later one centred on the shift found so far with radius ceil(g_prev / g) + 1.  gateFactor > 0: only
+  // differences within gateFactor x NMAD of the median at the level's centre shift take part (objectHeights of the two overlapping
+  // slices, two differenceStats).  scale 0: 64 / cell.  minOverlap: the share of the level's valid moving cells a shift needs.
+  // `pose` is `start` (null: the identity) with T moved by cell (x ex + y ey) - bias ez, which is exact for an orthonormal frame:
+  // registerToReference(cloud, pose, ..) takes it as its start.  found is false when a call is refused or a level has no candidate.
+  struct ShiftLevel {
+    ssrlcv_shift_params params;
+    ssrlcv_shift_result result;
+    std::vector<unsigned char> table;  // as the device wrote it: the head, then the entries
+  };
+  struct ShiftSearch {
+    bool found = false;
+    double shiftX = 0, shiftY = 0;  // in cells, the last level's best shift with its sub-cell step
+    ssrlcv_shift_result result = {};
+    ssrlcv_register_pose pose = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, {0, 0, 0}};
+    std::vector<ShiftLevel> levels;
+  };
+
+  static ShiftSearch searchShift(ptr::value<Unity<float>> moving, ptr::value<Unity<float>> reference, const ssrlcv_dsm_frame& frame, uint32_t radius = 8,
+                                 const std::vector<uint32_t>& strides = {4u, 1u}, float gateFactor = 3.0f, float scale = 0.0f, double minOverlap = 0.25,
+                                 const ssrlcv_register_pose* start = nullptr) {
+    ShiftSearch found;
+    const uint32_t w = frame.w, h = frame.h;
+    const unsigned long cells = (unsigned long)w * h;
+    if (moving == nullptr || reference == nullptr || cells == 0 || moving->size() != cells || reference->size() != cells || strides.empty()) {
+      logger.err << "MeshFactory::searchShift: both maps have the frame's w h entries, and there is a stride";
+      return found;
+    }
+    if (start) found.pose = *start;
+    MemoryState originM = moving->getMemoryState(), originR = reference->getMemoryState();
+    if (originM != gpu) moving->setMemoryState(gpu);
+    if (originR != gpu && reference != moving) reference->setMemoryState(gpu);
+    std::vector<float> hostM(cells), hostR(cells);  // the gate's slices are cut on the host
+    HipSafeCall(ssrlcv_hip_memcpy(hostM.data(), moving->device.get(), cells * sizeof(float), 1));
+    HipSafeCall(ssrlcv_hip_memcpy(hostR.data(), reference->device.get(), cells * sizeof(float), 1));
+    const double cell = (double)frame.cell;
+    const float quanta = scale > 0.0f ? scale : (float)(64.0 / cell);
+    int64_t best[2] = {0, 0};
+    bool ok = true;
+    for (size_t k = 0; k < strides.size() && ok; ++k) {
+      const uint32_t g = strides[k];
+      if (g == 0) { ok = false; break; }
+      ShiftLevel level;
+      level.params.scale = quanta;
+      level.params.stride = g;
+      level.params.centerX = k == 0 ? 0 : (int32_t)std::floor((double)best[0] / (double)g + 0.5);
+      level.params.centerY = k == 0 ? 0 : (int32_t)std::floor((double)best[1] / (double)g + 0.5);
+      level.params.radius = k == 0 ? radius : (strides[k - 1] + g - 1u) / g + 1u;
+      level.params.centerQ = 0;
+      level.params.gateQ = 0xFFFFFFFFu;
+      const uint32_t sw = (uint32_t)(((uint64_t)w + g - 1u) / g), sh = (uint32_t)(((uint64_t)h + g - 1u) / g);
+      if (gateFactor > 0.0f) {  // the median and the NMAD of the differences at the centre shift, in quanta
+        const int64_t cx = level.params.centerX, cy = level.params.centerY;
+        const int64_t x0 = std::max<int64_t>(0, -cx), x1 = std::min<int64_t>(sw, (int64_t)sw - cx);
+        const int64_t y0 = std::max<int64_t>(0, -cy), y1 = std::min<int64_t>(sh, (int64_t)sh - cy);
+        if (x1 > x0 && y1 > y0) {
+          const unsigned long sliceW = (unsigned long)(x1 - x0), sliceH = (unsigned long)(y1 - y0);
+          ptr::host<float> a((long)(sliceW * sliceH), true), b((long)(sliceW * sliceH), true);
+          for (unsigned long y = 0; y < sliceH; ++y)
+            for (unsigned long x = 0; x < sliceW; ++x) {
+              a.get()[y * sliceW + x] = hostM[(size_t)((y0 + (int64_t)y) * g) * w + (size_t)((x0 + (int64_t)x) * g)];
+              b.get()[y * sliceW + x] = hostR[(size_t)((y0 + cy + (int64_t)y) * g) * w + (size_t)((x0 + cx + (int64_t)x) * g)];
+            }
+          ptr::value<Unity<float>> sliceM(a, sliceW * sliceH, cpu, true), sliceR(b, sliceW * sliceH, cpu, true);
+          auto diff = objectHeights(sliceM, sliceR, (unsigned int)sliceW, (unsigned int)sliceH);
+          const ssrlcv_diff_stats s = differenceStats(diff, 0.0f, false, {5000u});
+          if (s.finite != 0) {
+            const double mad = (double)differenceStats(diff, s.quantile[0], true, {5000u}).quantile[0];
+            const double cq = std::nearbyint((double)s.quantile[0] * (double)quanta);
+            const double gq = std::floor((double)gateFactor * (1.4826 * mad) * (double)quanta);
+            level.params.centerQ = (int32_t)std::max(-262144.0, std::min(262144.0, cq));
+            level.params.gateQ = (uint32_t)std::max(0.0, std::min(4294967294.0, gq));
+          }
+        }
+      }
+      const size_t tableBytes = ssrlcv_shift_table_bytes(level.params.radius);
+      const size_t wsb = ssrlcv_hip_shift_search_workspace_bytes(w, h, &level.params);
+      if (tableBytes == 0) { ok = false; break; }
+      ptr::device<unsigned char> ws(wsb ? wsb : 1), table(tableBytes);
+      const int status = ssrlcv_hip_shift_search(moving->device.get(), reference->device.get(), w, h, &level.params, (ssrlcv_shift_table*)table.get(), ws.get(),
+                                                 wsb, nullptr);
+      if (status != SSRLCV_OK) {
+        logger.err.printf("MeshFactory::searchShift: refused (%s)", ssrlcv_hip_status_string(status));
+        HipSafeCall(ssrlcv_hip_device_synchronize());
+        ok = false;
+        break;
+      }
+      level.table.resize(tableBytes);
+      HipSafeCall(ssrlcv_hip_memcpy(level.table.data(), table.get(), tableBytes, 1));  // synchronises: the workspace may go out of scope
+      ssrlcv_shift_table head;
+      std::memcpy(&head, level.table.data(), sizeof head);
+      const uint32_t least = (uint32_t)(minOverlap * (double)head.validMoving);
+      if (ssrlcv_shift_pick_host((const ssrlcv_shift_table*)level.table.data(), tableBytes, &level.params, least, &level.result) != SSRLCV_OK) {
+        logger.err.printf("MeshFactory::searchShift: no shift of level %zu has the overlap asked for", k);
+        ok = false;
+        break;
+      }
+      best[0] = level.result.shiftX, best[1] = level.result.shiftY;
+      found.levels.push_back(level);
+    }
+    if (originM != gpu) moving->setMemoryState(originM);
+    if (originR != gpu && reference != moving) reference->setMemoryState(originR);
+    if (!ok || found.levels.empty()) return found;
+    found.result = found.levels.back().result;
+    found.shiftX = (double)best[0] + found.result.subX;
+    found.shiftY = (double)best[1] + found.result.subY;
+    for (int r = 0; r < 3; ++r) {
+      const double along = cell * (found.shiftX * (double)frame.ex[r] + found.shiftY * (double)frame.ey[r]);
+      found.pose.m[4 * r + 3] = (float)(((double)found.pose.m[4 * r + 3] + along) - found.result.bias * (double)frame.ez[r]);
+    }
+    found.found = true;
+    return found;
   }
 
   // ---- mesh render (include/ssrlcv_hip.h "mesh render"): the surface drawn into a camera, and compared with that camera's own

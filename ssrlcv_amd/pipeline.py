@@ -610,7 +610,7 @@ def surface_register(points, reference, frame, max_jump=None, dof="rigid", itera
     `frame`) by point-to-plane Gauss-Newton steps (include/ssrlcv_hip.h "surface registration").  The reference is the triangle
     mesh of the map at step 1, cut where two cells differ by more than max_jump (None: nowhere).  dof: "shift" (translation),
     "rigid" (and rotation), "similarity" (and scale), or a mask of capi.register_step's bits.  initial: a capi.RegisterPose to
-    start from (None: the identity); a coarse search over many cells is the caller's.  The pivot is the float64 mean of the points
+    start from (None: the identity); from many cells off, surface_register_coarse finds it by a coarse search first.  The pivot is the float64 mean of the points
     that have a difference under the initial pose, rounded to float.  Every iteration: with a gate (None: without), one
     surface_difference of the posed cloud and two statistics calls give center = the median and width = gate x NMAD, and only
     points with |d - center| <= width take part; then one capi.register_terms (one 304-byte read-back), capi.register_step with
@@ -671,6 +671,82 @@ def surface_register(points, reference, frame, max_jump=None, dof="rigid", itera
     return {"pose": pose, "converged": converged, "history": history}
 
 
+def _shift_gate(moving, reference, g, center, gate, scale):
+    """(centerQ, gateQ) of one level of surface_shift_search: the median and gate x NMAD of the differences of the two sampled
+    maps at the shift `center`, in quanta; no gate where that shift has no finite difference"""
+    m, r = moving[::g, ::g], reference[::g, ::g]
+    h, w = m.shape
+    (x0, x1), (y0, y1) = ((max(0, -s), min(n, n - s)) for s, n in zip(center, (w, h)))
+    if x1 <= x0 or y1 <= y0:
+        return 0, None
+    diff = capi.dsm_subtract(m[y0:y1, x0:x1].contiguous(), r[y0 + center[1]:y1 + center[1], x0 + center[0]:x1 + center[0]].contiguous())
+    signed = capi.difference_stats(diff, quantiles=(5000,))
+    if signed.finite == 0:
+        return 0, None
+    median = float(signed.quantile[0])
+    mad = float(capi.difference_stats(diff, center=median, absolute=True, quantiles=(5000,)).quantile[0])
+    center_q = int(np.rint(np.float64(median) * np.float64(scale)))
+    gate_q = int(np.floor(np.float64(gate) * (np.float64(1.4826) * np.float64(mad)) * np.float64(scale)))
+    return max(-(1 << 18), min(1 << 18, center_q)), max(0, min(gate_q, capi.SHIFT_NO_GATE - 1))
+
+
+def surface_shift_search(subject, reference, frame, radius=8, strides=(4, 1), gate=3.0, scale=None, min_overlap=0.25, rule="max", initial=None):
+    """The whole-cell shift that lays a subject tens of cells off onto a reference height map (float32 (h, w) device tensor in
+    `frame`), coarse to fine (include/ssrlcv_hip.h "shift search"): what surface_register needs before its first step.  subject: a
+    cloud ((n, 3) float32 device tensor), which goes through transform_cloud(initial) when an initial pose is given and then
+    through capi.dsm_rasterize (rule "max" or "min"), or a height map of the grid of `frame`.  scale: quanta a height unit,
+    64 / cell by default.  One capi.shift_search a level: the first at strides[0], centred on 0 with `radius`; each later one
+    at its stride g centred on the shift found so far, floor(best / g + 0.5), with radius ceil(g_prev / g) + 1.  With a gate
+    (None: without) only differences within gate x NMAD of the median take part, both taken from capi.dsm_subtract of the two
+    sampled maps at the level's centre shift and two statistics calls.  A shift is a candidate if it has at least min_overlap x
+    the level's valid subject cells; the best is the one of least variance of the differences (capi.shift_pick).
+    -> dict(shift: (x, y) in cells, the last level's best shift with its sub-cell step; bias: the subject's height above the
+    reference; variance; second: the least variance outside the 3 x 3 around the best; pose: a capi.RegisterPose, M = the
+    identity (or initial's) and T moved by cell (x ex + y ey) - bias ez, which is exact for the orthonormal frames dsm_frame
+    makes; levels: per level dict(params, result, table)).  Raises SsrlcvError when a level has no candidate."""
+    if rule not in _DSM_RULES:
+        raise ValueError("rule is 'max' or 'min', not %r" % (rule,))
+    strides = [int(g) for g in strides]
+    if not strides or any(g < 1 for g in strides):
+        raise ValueError("strides are at least 1, not %r" % (strides,))
+    is_map = subject.dim() == 2 and tuple(subject.shape) == (int(frame.h), int(frame.w))
+    if is_map:
+        moving = subject
+    else:
+        cloud = subject if initial is None else transform_cloud(subject, initial)
+        moving = capi.dsm_rasterize(cloud, frame, _DSM_RULES[rule], want_source=False, want_count=False)[0]
+    cell = float(frame.cell)
+    scale = float(np.float32(64.0 / cell if scale is None else scale))
+    best, levels, ws = (0, 0), [], None
+    for k, g in enumerate(strides):
+        center = (0, 0) if k == 0 else tuple(int(np.floor(b / g + 0.5)) for b in best)
+        level_radius = int(radius) if k == 0 else -(-strides[k - 1] // g) + 1
+        center_q, gate_q = (0, None) if gate is None else _shift_gate(moving, reference, g, center, gate, scale)
+        table = capi.shift_search(moving, reference, scale, g, center, level_radius, center_q, gate_q, ws)
+        result = capi.shift_pick(table, table["params"], int(float(min_overlap) * int(table["head"]["validMoving"])))
+        if result is None:
+            raise capi.SsrlcvError("surface_shift_search: no shift of level %d (stride %d) has the overlap asked for" % (k, g))
+        best = (int(result.shiftX), int(result.shiftY))
+        levels.append({"params": table["params"], "result": result, "table": table})
+    x, y = best[0] + float(result.subX), best[1] + float(result.subY)
+    start = capi.RegisterPose.make() if initial is None else initial
+    m = np.array(list(start.m), np.float64).reshape(3, 4)
+    ex, ey, ez = (np.array(list(v), np.float64) for v in (frame.ex, frame.ey, frame.ez))
+    pose = capi.RegisterPose.make(m[:, :3], m[:, 3] + cell * (x * ex + y * ey) - float(result.bias) * ez, list(start.pivot))
+    return {"shift": (x, y), "bias": float(result.bias), "variance": float(result.variance), "second": float(result.second), "pose": pose,
+            "levels": levels}
+
+
+def surface_register_coarse(points, reference, frame, search, **register):
+    """surface_register behind a coarse search, for a cloud that lies many cells off: surface_shift_search(points, reference,
+    frame, **search) runs first -- on the cloud under register's `initial`, if there is one -- and its pose is the `initial` of
+    the loop.  -> surface_register's dictionary, which gains `search` (surface_shift_search's)."""
+    found = surface_shift_search(points, reference, frame, **dict(search, initial=register.get("initial")))
+    out = surface_register(points, reference, frame, **dict(register, initial=found["pose"]))
+    out["search"] = found
+    return out
+
+
 def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=False, register=None, **kw):
     """How far a surface lies from a reference height map (`reference` in `frame`): `subject` is a cloud ((n, 3) float32 device
     tensor) or a height map (float32 (h, w): any tensor when subject_frame is given, one of the grid of `frame` without), which
@@ -681,7 +757,8 @@ def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=Fal
     height-map subject also error_map: the differences scattered back into the subject's grid by its validity mask, a map in
     the form of every map here.  With register = a dict of surface_register's arguments (dof, iterations, gate, initial, damping;
     max_jump is kw's) the subject's points are registered to the reference first and the differences are those of the registered
-    points: the report gains pose and registration (surface_register's dictionary)."""
+    points: the report gains pose and registration (surface_register's dictionary).  register may also hold search = a dict of
+    surface_shift_search's arguments, for a subject that lies many cells off: the registration is surface_register_coarse's."""
     sub_frame = frame if subject_frame is None else subject_frame
     is_map = subject_frame is not None or (subject.dim() == 2 and tuple(subject.shape) == (int(frame.h), int(frame.w)))
     if want_map and not is_map:
@@ -691,7 +768,12 @@ def surface_accuracy(subject, reference, frame, subject_frame=None, want_map=Fal
     if register is not None:
         if not kw.get("mesh", True):
             raise ValueError("register needs the mesh of the reference (mesh=True)")
-        registration = surface_register(points, reference, frame, max_jump=kw.get("max_jump"), **dict(register))
+        register = dict(register)
+        search = register.pop("search", None)
+        if search is None:
+            registration = surface_register(points, reference, frame, max_jump=kw.get("max_jump"), **register)
+        else:
+            registration = surface_register_coarse(points, reference, frame, search, max_jump=kw.get("max_jump"), **register)
         points = transform_cloud(points, registration["pose"])
     diff = surface_difference(points, reference, frame, **kw)
     signed = difference_stats(diff, quantiles=(5000,))
