@@ -41,11 +41,12 @@
 //   GridMesh surface = factory.generateMesh(disparity, 1, 1.0f);       // triangles over the step-1 grid, cut at jumps above 1
 //   meshFactory.setPoints(cloud); meshFactory.setSurface(surface); meshFactory.computeSurfaceNormals();
 //
-// Pixels keep upstream's memory-state contract: forced onto the gpu for the call, restored to their origin state after it.
+// Pixels and maps are on the gpu for the call and leave it in the state they came in (Scoped.hpp).
 #pragma once
 #include "GridMesh.hpp"
 #include "Image.hpp"
 #include "MatchFactory.hpp"
+#include "Scoped.hpp"
 
 namespace ssrlcv {
 
@@ -59,19 +60,12 @@ class DisparityFactory {
   unsigned int census = 0;  // 0: SAD costs
   uint2 mapSize = {0u, 0u};  // of the last generateDisparities: a Unity<float> does not carry its width
 
-  static void toGpu(ptr::value<Image> image, MemoryState& origin, bool& keepHost) {
+  static const ptr::value<Unity<unsigned char>>& grey(const ptr::value<Image>& image) {
     if (image->colorDepth != 1) {
       logger.err << "ERROR: dense stereo takes single-channel images (convertToBW first)";
       std::exit(-1);
     }
-    origin = image->pixels->getMemoryState();
-    keepHost = origin == cpu;  // the kernels only read the pixels: keep the host copy, drop the device one afterwards
-    if (keepHost) image->pixels->transferMemoryTo(gpu);
-    else if (origin != gpu) image->pixels->setMemoryState(gpu);
-  }
-  static void restore(ptr::value<Image> image, MemoryState origin, bool keepHost) {
-    if (keepHost) image->pixels->clear(gpu);
-    else if (origin != gpu) image->pixels->setMemoryState(origin);
+    return image->pixels;
   }
 
  public:
@@ -146,12 +140,9 @@ class DisparityFactory {
         logger.err << "ERROR: dense stereo parameters outside the contract (radius 1..15, 1..256 disparities from -32768..32767)";
       std::exit(-1);
     }
-    MemoryState originL, originR;
-    bool keepL, keepR;
-    toGpu(left, originL, keepL);
-    toGpu(right, originR, keepR);
+    GpuRead<unsigned char> leftOnGpu(grey(left)), rightOnGpu(grey(right));
     const unsigned long n = (unsigned long)w * h;
-    ptr::device<unsigned char> workspace((long)wsBytes);
+    DeviceScratch workspace(wsBytes);
     ptr::value<Unity<float>> disparity(nullptr, n ? n : 1ul, gpu);
     ptr::value<Unity<unsigned int>> costs;
     if (cost) costs = ptr::value<Unity<unsigned int>>(nullptr, n ? n : 1ul, gpu);
@@ -168,9 +159,6 @@ class DisparityFactory {
       HipSafeCall(ssrlcv_hip_stereo_sad_u8(left->pixels->device.get(), right->pixels->device.get(), w, h, &params, workspace.get(), wsBytes,
                                            disparity->device.get(), cost ? costs->device.get() : nullptr, nullptr));
     HipCheckError();
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    restore(left, originL, keepL);
-    restore(right, originR, keepR);
     if (cost) *cost = costs;
     return disparity;
   }
@@ -183,19 +171,17 @@ class DisparityFactory {
       logger.err << "ERROR: the sampling step of dense stereo matches is at least 1";
       std::exit(-1);
     }
-    MemoryState origin = disparity->getMemoryState();
-    if (origin != gpu) disparity->setMemoryState(gpu);
+    GpuRead<float> onGpu(disparity);
     // samples per row and column: ceil(n / step) without the sum n + step - 1, which wraps for a step near 2^32
     const uint32_t cap = (w ? (w - 1) / step + 1 : 0) * (h ? (h - 1) / step + 1 : 0);
-    ptr::device<unsigned char> workspace((long)wsBytes);
     ptr::device<Match> staging((long)(cap ? cap : 1));
     ptr::device<uint32_t> countDev(1);
+    DeviceScratch workspace(wsBytes);
     uint32_t count = 0;
     HipSafeCall(ssrlcv_hip_stereo_matches(disparity->device.get(), w, h, step, left->id, right->id,
                                           reinterpret_cast<ssrlcv_match*>(staging.get()), cap, countDev.get(), workspace.get(), wsBytes, nullptr));
     HipCheckError();
     HipSafeCall(ssrlcv_hip_memcpy(&count, countDev.get(), sizeof count, 1));
-    if (origin != gpu) disparity->setMemoryState(origin);
     if (count == 0) {
       logger.err << "ERROR: dense stereo left no valid pixel";
       std::exit(0);
@@ -221,18 +207,13 @@ class DisparityFactory {
       logger.err << "ERROR: the images of a pair to rectify have their cameras' size";
       std::exit(-1);
     }
-    MemoryState originL, originR;
-    bool keepL, keepR;
-    toGpu(left, originL, keepL);
-    toGpu(right, originR, keepR);
+    GpuRead<unsigned char> leftOnGpu(grey(left)), rightOnGpu(grey(right));
     const unsigned long n = (unsigned long)rect.w * rect.h;
     ptr::value<Unity<unsigned char>> pixelsL(nullptr, n, gpu), pixelsR(nullptr, n, gpu);
     HipSafeCall(ssrlcv_hip_warp_homography_u8(left->pixels->device.get(), rect.w, rect.h, rect.Hl, pixelsL->device.get(), rect.w, rect.h, nullptr));
     HipSafeCall(ssrlcv_hip_warp_homography_u8(right->pixels->device.get(), rect.w, rect.h, rect.Hr, pixelsR->device.get(), rect.w, rect.h, nullptr));
     HipCheckError();
     HipSafeCall(ssrlcv_hip_device_synchronize());  // the sources may leave the gpu
-    restore(left, originL, keepL);
-    restore(right, originR, keepR);
     leftOut = ptr::value<Image>(uint2{rect.w, rect.h}, 1u, pixelsL);
     rightOut = ptr::value<Image>(uint2{rect.w, rect.h}, 1u, pixelsR);
     leftOut->id = left->id;
@@ -243,14 +224,11 @@ class DisparityFactory {
   // in place on generateDisparities' maps of a pair rectify() made: the pixels whose windows (with a census cost: whose
   // footprints, radius + census radius) left a source image become invalid (it only removes pixels); cost may be nullptr
   void maskRectified(ptr::value<Unity<float>> disparity, ptr::value<Unity<unsigned int>> cost, const Rectification& rect) {
-    MemoryState origin = disparity->getMemoryState(), originC = cost != nullptr ? cost->getMemoryState() : gpu;
-    if (origin != gpu) disparity->setMemoryState(gpu);
-    if (cost != nullptr && originC != gpu) cost->setMemoryState(gpu);
+    GpuWrite<float> onGpu(disparity);
+    GpuWrite<unsigned int> costOnGpu(cost);
     HipSafeCall(ssrlcv_hip_stereo_mask_rectified(disparity->device.get(), cost != nullptr ? cost->device.get() : nullptr, rect.w, rect.h,
                                                  footprintRadius(), rect.Hl, rect.Hr, rect.w, rect.h, nullptr));
     HipCheckError();
-    if (origin != gpu) disparity->setMemoryState(origin);
-    if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);
   }
 
   // in place on a map of generateDisparities (include/ssrlcv_hip.h "disparity post-filters" item 3; the map has the size of
@@ -264,16 +242,12 @@ class DisparityFactory {
       logger.err << "ERROR: the speckle filter takes a map of the size of the last pair matched (setMapSize for any other)";
       std::exit(-1);
     }
-    MemoryState origin = disparity->getMemoryState(), originC = cost != nullptr ? cost->getMemoryState() : gpu;
-    if (origin != gpu) disparity->setMemoryState(gpu);
-    if (cost != nullptr && originC != gpu) cost->setMemoryState(gpu);
-    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+    GpuWrite<float> onGpu(disparity);
+    GpuWrite<unsigned int> costOnGpu(cost);
+    DeviceScratch workspace(wsBytes);
     HipSafeCall(ssrlcv_hip_stereo_filter_speckles(disparity->device.get(), cost != nullptr ? cost->device.get() : nullptr, w, h, maxDiff,
                                                   maxSpeckleSize, workspace.get(), wsBytes, nullptr));
     HipCheckError();
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    if (origin != gpu) disparity->setMemoryState(origin);
-    if (cost != nullptr && originC != gpu) cost->setMemoryState(originC);
   }
 
   // a new map, in state gpu: every valid pixel becomes the lower median of the valid pixels of its (2 radius + 1)^2 window,
@@ -284,13 +258,11 @@ class DisparityFactory {
       logger.err << "ERROR: the median filter takes a map of the size of the last pair matched (setMapSize for any other)";
       std::exit(-1);
     }
-    MemoryState origin = disparity->getMemoryState();
-    if (origin != gpu) disparity->setMemoryState(gpu);
+    GpuRead<float> onGpu(disparity);
     ptr::value<Unity<float>> filtered(nullptr, disparity->size(), gpu);
     HipSafeCall(ssrlcv_hip_stereo_filter_median(disparity->device.get(), filtered->device.get(), w, h, radius, nullptr));
     HipCheckError();
     HipSafeCall(ssrlcv_hip_device_synchronize());  // the source may leave the gpu
-    if (origin != gpu) disparity->setMemoryState(origin);
     return filtered;
   }
 
@@ -313,16 +285,13 @@ class DisparityFactory {
       std::exit(-1);
     }
     const size_t wsBytes = ssrlcv_hip_stereo_fill_holes_workspace_bytes(w, h, &params);  // 0 for refused parameters: the call says so
-    MemoryState origin = disparity->getMemoryState();
-    if (origin != gpu) disparity->setMemoryState(gpu);
+    GpuRead<float> onGpu(disparity);
     ptr::value<Unity<float>> out(nullptr, disparity->size(), gpu);
     if (filled != nullptr) *filled = ptr::value<Unity<unsigned char>>(nullptr, disparity->size(), gpu);
-    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
+    DeviceScratch workspace(wsBytes);
     HipSafeCall(ssrlcv_hip_stereo_fill_holes(disparity->device.get(), out->device.get(), filled != nullptr ? (*filled)->device.get() : nullptr, w, h,
                                              &params, workspace.get(), wsBytes, nullptr));
     HipCheckError();
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    if (origin != gpu) disparity->setMemoryState(origin);
     return out;
   }
 
@@ -337,34 +306,31 @@ class DisparityFactory {
       std::exit(-1);
     }
     const size_t wsBytes = ssrlcv_hip_disparity_mesh_workspace_bytes(w, h, &params);  // 0 for refused parameters: the call says so
-    MemoryState origin = disparity->getMemoryState();
-    if (origin != gpu) disparity->setMemoryState(gpu);
+    GpuRead<float> onGpu(disparity);
     GridMesh mesh;
     mesh.gw = meshStep && w ? (w - 1) / meshStep + 1 : 0;
     mesh.gh = meshStep && h ? (h - 1) / meshStep + 1 : 0;
     const unsigned long nodes = (unsigned long)mesh.gw * mesh.gh;
     mesh.vertexIndex = ptr::value<Unity<unsigned int>>(nullptr, nodes ? nodes : 1ul, gpu);
     mesh.cells = ptr::value<Unity<unsigned char>>(nullptr, mesh.numCells() ? mesh.numCells() : 1ul, gpu);
-    ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
     ptr::device<uint32_t> countDev(1);
+    DeviceScratch workspace(wsBytes);
     HipSafeCall(ssrlcv_hip_disparity_mesh(disparity->device.get(), w, h, &params, mesh.vertexIndex->device.get(), mesh.cells->device.get(),
                                           countDev.get(), workspace.get(), wsBytes, nullptr));
     HipCheckError();
-    HipSafeCall(ssrlcv_hip_memcpy(&mesh.vertexCount, countDev.get(), sizeof mesh.vertexCount, 1));  // synchronises: the workspace may go
-    if (origin != gpu) disparity->setMemoryState(origin);
+    HipSafeCall(ssrlcv_hip_memcpy(&mesh.vertexCount, countDev.get(), sizeof mesh.vertexCount, 1));
     return mesh;
   }
 
   // in place: generateMatches' records of a rectified pair, through Hl and Hr into source pixels; a record that does not
   // map back is removed (validateMatches' stable compaction)
   void unrectifyMatches(ptr::value<Unity<Match>> matches, const Rectification& rect) {
-    MemoryState origin = matches->getMemoryState();
-    if (origin != gpu) matches->setMemoryState(gpu);
+    GpuWrite<Match> onGpu(matches);  // on leaving it brings back what the Unity then holds: the kept records
     const uint32_t n = (uint32_t)matches->size();
     HipSafeCall(ssrlcv_hip_matches_apply_homography(reinterpret_cast<ssrlcv_match*>(matches->device.get()), n, rect.Hl, rect.Hr, nullptr));
     HipCheckError();
     const size_t wsBytes = ssrlcv_hip_match_workspace_bytes(n, 1);
-    ptr::device<unsigned char> workspace((long)wsBytes);
+    DeviceScratch workspace(wsBytes);
     uint32_t left = 0;
     HipSafeCall(ssrlcv_hip_compact_matches(SSRLCV_OUT_MATCH, matches->device.get(), n, &left, workspace.get(), wsBytes, nullptr));
     if (left == 0) {
@@ -376,7 +342,6 @@ class DisparityFactory {
       HipSafeCall(ssrlcv_hip_memcpy(kept.get(), matches->device.get(), (size_t)left * sizeof(Match), 2));
       matches->setData(kept, left, gpu);
     }
-    if (origin != gpu) matches->setMemoryState(origin);
   }
 };
 

@@ -136,6 +136,7 @@ MatchSet generateMatchesExhaustiveSharded(Comm& c, MatchFactory<T>& matchFactory
   for (int v = 0; v < V; ++v) {
     auto& f = features[(size_t)v];
     if (imageOwner(v, c.world) == c.rank) {
+      // no guard: every rank ends with every image's features on the gpu, the owner's included
       if (f->getMemoryState() != gpu && f->getMemoryState() != both) f->setMemoryState(gpu);
       else if (f->getMemoryState() == both && f->getFore() == cpu) f->transferMemoryTo(gpu);
     } else {
@@ -201,6 +202,7 @@ inline ptr::value<Unity<float3>> nViewTriangulateSharded(Comm& c, MatchSet* matc
     return ptr::value<Unity<float3>>();
   const unsigned long M = matchSet->matches->size(), K = matchSet->keyPoints->size();
   if (images.empty() || images.at(0)->isPushbroom) throw std::invalid_argument("nViewTriangulateSharded: projective cameras only");
+  // no guards: the match set and the cloud end on the cpu, like nViewTriangulate's
   matchSet->matches->transferMemoryTo(gpu);
   matchSet->keyPoints->transferMemoryTo(gpu);
   unsigned long lo = 0, hi = 0;
@@ -250,21 +252,17 @@ inline MatchSet selectPairBundles(MatchSet* matchSet, int imageA, int imageB) {
   if (matchSet == nullptr || matchSet->matches == nullptr || matchSet->keyPoints == nullptr || matchSet->matches->size() == 0)
     return MatchSet();  // (null members = no bundle of that pair; no zero-length allocation)
   const unsigned long M = matchSet->matches->size(), K = matchSet->keyPoints->size();
-  const MemoryState mmOrigin = matchSet->matches->getMemoryState(), kpOrigin = matchSet->keyPoints->getMemoryState();
-  if (matchSet->matches->getFore() == cpu) matchSet->matches->transferMemoryTo(gpu);
-  if (matchSet->keyPoints->getFore() == cpu) matchSet->keyPoints->transferMemoryTo(gpu);
+  GpuRead<MultiMatch> matchesOnGpu(matchSet->matches);
+  GpuRead<KeyPoint> keyPointsOnGpu(matchSet->keyPoints);
   ptr::device<ssrlcv_multimatch> mm_d((long)M);
   ptr::device<ssrlcv_keypoint> kp_d((long)(2 * M));
   ptr::device<uint32_t> count_d(1);
-  const size_t wsBytes = ssrlcv_hip_select_pair_workspace_bytes((uint32_t)M);
-  ptr::device<unsigned char> ws_d((long)wsBytes);
+  DeviceScratch ws_d(ssrlcv_hip_select_pair_workspace_bytes((uint32_t)M));
   HipSafeCall(ssrlcv_hip_select_pair_bundles(reinterpret_cast<const ssrlcv_multimatch*>(matchSet->matches->device.get()),
                                              reinterpret_cast<const ssrlcv_keypoint*>(matchSet->keyPoints->device.get()), (uint32_t)M, (uint32_t)K,
-                                             imageA, imageB, mm_d.get(), kp_d.get(), count_d.get(), ws_d.get(), wsBytes, nullptr));
+                                             imageA, imageB, mm_d.get(), kp_d.get(), count_d.get(), ws_d.get(), ws_d.bytes(), nullptr));
   uint32_t n = 0;
   HipSafeCall(ssrlcv_hip_memcpy(&n, count_d.get(), sizeof n, 1));
-  if (mmOrigin == cpu) matchSet->matches->clear(gpu);
-  if (kpOrigin == cpu) matchSet->keyPoints->clear(gpu);
   MatchSet pair;
   if (n == 0) return pair;  // (a Unity<T> cannot be empty: null members = no bundle of that pair)
   pair.matches = ptr::value<Unity<MultiMatch>>(nullptr, (unsigned long)n, gpu);
@@ -288,6 +286,7 @@ inline std::vector<float> evaluateCameraSetsSharded(Comm& c, MatchSet* pairSet, 
   // and a rank without bundles queues nothing else in front of the all-reduce -- order the two explicitly
   HipSafeCall(ssrlcv_hip_device_synchronize());
   if (pairSet->matches != nullptr && pairSet->matches->size()) {
+    // no guards: a pair set from the host stays in state both for the next of the iteration's evaluations
     if (pairSet->matches->getFore() == cpu) pairSet->matches->transferMemoryTo(gpu);
     if (pairSet->keyPoints->getFore() == cpu) pairSet->keyPoints->transferMemoryTo(gpu);
     unsigned long lo = 0, hi = 0;

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <fstream>
 #include <string>
+#include "Scoped.hpp"
 #include "Unity.hpp"
 #include "cuda_vec_types.hpp"
 
@@ -112,14 +113,12 @@ inline void convertToBW(ptr::value<Unity<unsigned char>> pixels, unsigned int co
     logger.err.printf("ERROR colorDepth of %u is not supported", colorDepth);  // generateBW's default branch traps
     std::exit(-1);
   }
-  MemoryState origin = pixels->getMemoryState();
-  if (origin != gpu) pixels->setMemoryState(gpu);
+  GpuWrite<unsigned char> onGpu(pixels);  // on leaving it brings back what the Unity then holds: the grey pixels
   unsigned long numPixels = pixels->size() / colorDepth;
   ptr::device<unsigned char> bwPixels_device((long)numPixels);
   HipSafeCall(ssrlcv_hip_convert_to_bw(pixels->device.get(), colorDepth, bwPixels_device.get(), numPixels, nullptr));
   HipCheckError();
   pixels->setData(bwPixels_device, numPixels, gpu);
-  if (origin != gpu) pixels->setMemoryState(origin);
 }
 
 static_assert(sizeof(Image::Camera) == sizeof(ssrlcv_camera), "Image::Camera must be 80 B");

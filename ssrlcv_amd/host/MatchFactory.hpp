@@ -9,10 +9,12 @@
 // (validateMatches = stable compaction).
 #pragma once
 #include <algorithm>
+#include <deque>
 #include <iterator>
 #include <vector>
 #include "Feature.hpp"
 #include "Image.hpp"
+#include "Scoped.hpp"
 
 namespace ssrlcv {
 
@@ -72,21 +74,14 @@ class MatchFactory {
                              ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures, float epsilon,
                              float delta, ptr::value<Unity<float>> seedDistances, const float* fundamental = nullptr) {
     static_assert(std::is_same<T, SIFT_Descriptor>::value, "MatchFactory is provided for SIFT_Descriptor");
-    MemoryState origin[2] = {queryFeatures->getMemoryState(), targetFeatures->getMemoryState()};
-    if (origin[0] != gpu) queryFeatures->setMemoryState(gpu);
-    if (origin[1] != gpu) targetFeatures->setMemoryState(gpu);
+    GpuRead<Feature<T>> queryOnGpu(queryFeatures), targetOnGpu(targetFeatures);
     uint32_t nq = (uint32_t)queryFeatures->size(), nt = (uint32_t)targetFeatures->size();
-    const float* seed_d = nullptr;
-    MemoryState seedOrigin = null;
-    if (seedDistances != nullptr) {
-      if (seedDistances->size() != queryFeatures->size()) {
-        logger.err << "ERROR: seedDistances should have come from matching a seed image to queryFeatures";
-        std::exit(-1);
-      }
-      seedOrigin = seedDistances->getMemoryState();
-      if (seedOrigin != gpu) seedDistances->setMemoryState(gpu);
-      seed_d = seedDistances->device.get();
+    if (seedDistances != nullptr && seedDistances->size() != queryFeatures->size()) {
+      logger.err << "ERROR: seedDistances should have come from matching a seed image to queryFeatures";
+      std::exit(-1);
     }
+    GpuRead<float> seedOnGpu(seedDistances);
+    const float* seed_d = seedDistances != nullptr ? seedDistances->device.get() : nullptr;
     ssrlcv_match_params p = make_params(mode, query, target, epsilon, delta, relativeThreshold, absoluteThreshold);
     if (fundamental) std::memcpy(p.fundamental, fundamental, sizeof p.fundamental);
     size_t wsBytes = ssrlcv_hip_match_workspace_bytes(nq, nt);
@@ -96,7 +91,6 @@ class MatchFactory {
                                         reinterpret_cast<const ssrlcv_sift_feature*>(targetFeatures->device.get()), nt,
                                         seed_d, &p, outKind, matches->device.get(), ws, wsBytes, nullptr));
     HipCheckError();
-    if (seedDistances != nullptr && seedOrigin != gpu) seedDistances->setMemoryState(seedOrigin);
     // validateMatches (src/MatchFactory.cu:32-108)
     uint32_t left = 0;
     HipSafeCall(ssrlcv_hip_compact_matches(outKind, matches->device.get(), nq, &left, ws, wsBytes, nullptr));
@@ -108,8 +102,6 @@ class MatchFactory {
       HipSafeCall(ssrlcv_hip_memcpy(validated.get(), matches->device.get(), (size_t)left * sizeof(OUT), 2));
       matches->setData(validated, left, gpu);
     }
-    if (origin[0] != gpu) queryFeatures->setMemoryState(origin[0]);
-    if (origin[1] != gpu) targetFeatures->setMemoryState(origin[1]);
     return matches;
   }
 
@@ -121,9 +113,7 @@ class MatchFactory {
                                   ptr::value<Image> target, ptr::value<Unity<Feature<T>>> targetFeatures, float ratio,
                                   bool mutual) {
     static_assert(std::is_same<T, SIFT_Descriptor>::value, "MatchFactory is provided for SIFT_Descriptor");
-    MemoryState origin[2] = {queryFeatures->getMemoryState(), targetFeatures->getMemoryState()};
-    if (origin[0] != gpu) queryFeatures->setMemoryState(gpu);
-    if (origin[1] != gpu) targetFeatures->setMemoryState(gpu);
+    GpuRead<Feature<T>> queryOnGpu(queryFeatures), targetOnGpu(targetFeatures);
     uint32_t nq = (uint32_t)queryFeatures->size(), nt = (uint32_t)targetFeatures->size();
     ssrlcv_ratio_params p;
     p.queryImageID = (uint32_t)query->id;
@@ -148,8 +138,6 @@ class MatchFactory {
       HipSafeCall(ssrlcv_hip_memcpy(validated.get(), matches->device.get(), (size_t)left * sizeof(OUT), 2));
       matches->setData(validated, left, gpu);
     }
-    if (origin[0] != gpu) queryFeatures->setMemoryState(origin[0]);
-    if (origin[1] != gpu) targetFeatures->setMemoryState(origin[1]);
     return matches;
   }
 
@@ -166,9 +154,8 @@ class MatchFactory {
 
   // src/MatchFactory.cu:315-346
   ptr::value<Unity<float>> getSeedDistances(ptr::value<Unity<Feature<T>>> features) {
-    MemoryState origin = features->getMemoryState();
-    if (seedFeatures->getMemoryState() != gpu) seedFeatures->setMemoryState(gpu);
-    if (origin != gpu) features->setMemoryState(gpu);
+    if (seedFeatures->getMemoryState() != gpu) seedFeatures->setMemoryState(gpu);  // no guard: the seed features stay on the gpu for the next call
+    GpuRead<Feature<T>> onGpu(features);
     uint32_t nq = (uint32_t)features->size(), ns = (uint32_t)seedFeatures->size();
     ptr::value<Unity<float>> out(nullptr, (unsigned long)nq, gpu);
     size_t wsBytes = ssrlcv_hip_match_workspace_bytes(nq, ns);
@@ -176,7 +163,6 @@ class MatchFactory {
                                                  reinterpret_cast<const ssrlcv_sift_feature*>(seedFeatures->device.get()),
                                                  ns, out->device.get(), workspace(wsBytes), wsBytes, nullptr));
     HipCheckError();
-    if (origin != gpu) features->setMemoryState(origin);
     return out;
   }
 
@@ -260,6 +246,7 @@ class MatchFactory {
 
   // convertMatchToRaw (src/MatchFactory.cu:257-280, :2921-2926): slice the DMatch base
   ptr::value<Unity<Match>> getRawMatches(ptr::value<Unity<DMatch>> matches) {
+    // no guard: a `both` input is read on the host as it is and never refreshed, and the result goes where the input's fore was
     MemoryState origin = matches->getMemoryState();
     bool onGpu = origin == gpu || matches->getFore() == gpu;
     if (onGpu && origin == gpu) matches->transferMemoryTo(cpu);
@@ -317,26 +304,24 @@ class MatchFactory {
     for (auto& m : matchIndices) pairCounts.push_back((uint32_t)m->size());
     const size_t mergeBytes = ssrlcv_hip_merge_workspace_bytes((uint32_t)V, numFeatures.data(), (uint32_t)totalMatches);
     if (mergeBytes != 0 && totalMatches <= 0x7fffffffull) {
-      std::vector<MemoryState> origin(V);
+      std::deque<GpuRead<Feature<T>>> featuresOnGpu;  // a deque constructs its guards in place
       std::vector<const ssrlcv_sift_feature*> featPtr(V);
       for (size_t i = 0; i < V; ++i) {
-        origin[i] = features[i]->getMemoryState();
-        if (origin[i] != gpu && origin[i] != both) features[i]->setMemoryState(gpu);
-        else if (origin[i] == both && features[i]->getFore() == cpu) features[i]->transferMemoryTo(gpu);
+        featuresOnGpu.emplace_back(features[i]);
         featPtr[i] = reinterpret_cast<const ssrlcv_sift_feature*>(features[i]->device.get());
       }
       ptr::device<uint2_pair> allPairs((long)totalMatches);
       size_t at = 0;
       for (auto& m : matchIndices) {
         if (m->size() == 0) continue;
-        if (m->getMemoryState() != gpu && m->getMemoryState() != both) m->setMemoryState(gpu);
+        if (m->getMemoryState() != gpu && m->getMemoryState() != both) m->setMemoryState(gpu);  // no guard: the pair lists stay where the merge read them
         HipSafeCall(ssrlcv_hip_memcpy(allPairs.get() + at, m->device.get(), m->size() * sizeof(uint2_pair), 2));
         at += m->size();
       }
-      ptr::device<unsigned char> mergeWs((long)mergeBytes);
       ptr::device<MultiMatch> mm_d((long)totalMatches);
       ptr::device<uint2> mem_d((long)(2 * totalMatches));
       ptr::device<uint32_t> counts_d(4);
+      DeviceScratch mergeWs(mergeBytes);
       HipSafeCall(ssrlcv_hip_merge_matches((uint32_t)V, numFeatures.data(), (uint32_t)pairCounts.size(), pairCounts.data(),
                                            reinterpret_cast<const ssrlcv_uint2_pair*>(allPairs.get()), mergeWs.get(), mergeBytes,
                                            reinterpret_cast<ssrlcv_multimatch*>(mm_d.get()),
@@ -354,13 +339,11 @@ class MatchFactory {
                                                       numFeatures.data(), (uint32_t)V,
                                                       reinterpret_cast<ssrlcv_keypoint*>(matchSet.keyPoints->device.get()), nullptr));
       HipCheckError();
-      for (size_t i = 0; i < V; ++i)
-        if (origin[i] != gpu && origin[i] != both) features[i]->setMemoryState(origin[i]);
       return matchSet;
     }
     std::vector<uint2_pair> allPairs;
     for (auto& m : matchIndices) {
-      if (m->getMemoryState() != cpu) m->setMemoryState(cpu);
+      if (m->getMemoryState() != cpu) m->setMemoryState(cpu);  // no guard: the pair lists stay where the merge read them
       allPairs.insert(allPairs.end(), m->host.get(), m->host.get() + m->size());
     }
     ssrlcv_multimatch* mm_raw = nullptr;
@@ -369,12 +352,8 @@ class MatchFactory {
     HipSafeCall(ssrlcv_merge_matches_host((uint32_t)V, numFeatures.data(), (uint32_t)pairCounts.size(), pairCounts.data(),
                                           reinterpret_cast<const ssrlcv_uint2_pair*>(allPairs.data()), &mm_raw, &mem_raw,
                                           &nmm, &nmem));
-    std::vector<MemoryState> origin(V);
-    for (size_t i = 0; i < V; ++i) {
-      origin[i] = features[i]->getMemoryState();
-      if (origin[i] != cpu && origin[i] != both) features[i]->setMemoryState(cpu);
-      else if (origin[i] == both && features[i]->getFore() == gpu) features[i]->transferMemoryTo(cpu);
-    }
+    std::deque<CpuRead<Feature<T>>> featuresOnCpu;  // a deque constructs its guards in place
+    for (size_t i = 0; i < V; ++i) featuresOnCpu.emplace_back(features[i]);
     logger.info.printf("total matches found in set = %d", (int)nmm);
     matchSet.matches = ptr::value<Unity<MultiMatch>>(nullptr, (unsigned long)nmm, cpu);
     std::memcpy(matchSet.matches->host.get(), mm_raw, sizeof(MultiMatch) * nmm);
@@ -385,8 +364,6 @@ class MatchFactory {
     ssrlcv_host_free(mem_raw);
     matchSet.keyPoints = ptr::value<Unity<KeyPoint>>(nullptr, (unsigned long)kp_vec.size(), gpu);
     HipSafeCall(ssrlcv_hip_memcpy(matchSet.keyPoints->device.get(), kp_vec.data(), kp_vec.size() * sizeof(KeyPoint), 0));
-    for (size_t i = 0; i < V; ++i)
-      if (origin[i] != cpu && origin[i] != both) features[i]->setMemoryState(origin[i]);
     return matchSet;
   }
 };

@@ -17,11 +17,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <string>
 #include <vector>
 #include "GridMesh.hpp"
 #include "Image.hpp"
+#include "Scoped.hpp"
 #include "Unity.hpp"
 #include "cuda_vec_types.hpp"
 #include "io_util.hpp"
@@ -33,10 +35,9 @@ class MeshFactory {
   // the k-NN of `points` (on the gpu) -> neighbour indices, and their d2 when dist2 != nullptr
   void knn(int k, ptr::device<uint32_t>& nbr, ptr::device<float>* dist2) {
     const uint32_t n = (uint32_t)points->size();
-    const size_t wsb = ssrlcv_hip_knn_workspace_bytes(n, (uint32_t)k);
-    ptr::device<unsigned char> ws(wsb);
+    DeviceScratch ws(ssrlcv_hip_knn_workspace_bytes(n, (uint32_t)k));
     HipSafeCall(ssrlcv_hip_knn((const ssrlcv_float3*)points->device.get(), n, (uint32_t)k, 0.0f, nbr.get(),
-                               dist2 ? dist2->get() : nullptr, nullptr, ws.get(), wsb, nullptr));
+                               dist2 ? dist2->get() : nullptr, nullptr, ws.get(), ws.bytes(), nullptr));
   }
   // the filter on `points` (on the gpu): kept points, their normals (when `normals` matches), mean distances, count
   uint32_t filter(int k, float sigma, ptr::device<ssrlcv_float3>& kept, ptr::device<float>* keptNormals,
@@ -48,22 +49,19 @@ class MeshFactory {
     ptr::device<uint32_t> index(n);
     ptr::device<double> stats(3);
     ptr::device<uint32_t> count(1);
-    const size_t wsb = ssrlcv_hip_neighbor_filter_workspace_bytes(n, (uint32_t)k);
-    ptr::device<unsigned char> ws(wsb);
+    DeviceScratch ws(ssrlcv_hip_neighbor_filter_workspace_bytes(n, (uint32_t)k));
     HipSafeCall(ssrlcv_hip_neighbor_distance_filter((const ssrlcv_float3*)points->device.get(), n, d2.get(), (uint32_t)k,
                                                     sigma, meanDist ? meanDist->get() : nullptr, stats.get(), kept.get(),
                                                     index.get(), keptNormals ? (const float*)normals->device.get() : nullptr,
-                                                    keptNormals ? keptNormals->get() : nullptr, count.get(), ws.get(), wsb,
-                                                    nullptr));
+                                                    keptNormals ? keptNormals->get() : nullptr, count.get(), ws.get(),
+                                                    ws.bytes(), nullptr));
     uint32_t c = 0;
     HipSafeCall(ssrlcv_hip_memcpy(&c, count.get(), sizeof c, 1));
     HipSafeCall(ssrlcv_hip_memcpy(filterStats, stats.get(), sizeof filterStats, 1));
     if (followSurface) {  // the kept rows, ascending, are the vertices the surface keeps: kept point j is vertex j
-      const size_t sel = ssrlcv_hip_mesh_select_workspace_bytes(surface.vertexCount);
-      ptr::device<unsigned char> selWs(sel ? sel : 1);
+      DeviceScratch selWs(ssrlcv_hip_mesh_select_workspace_bytes(surface.vertexCount));
       HipSafeCall(ssrlcv_hip_mesh_select(surface.vertexIndex->device.get(), surface.cells->device.get(), surface.gw, surface.gh,
-                                         surface.vertexCount, index.get(), c, selWs.get(), sel, nullptr));
-      HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace and the index go out of scope
+                                         surface.vertexCount, index.get(), c, selWs.get(), selWs.bytes(), nullptr));
       surface.vertexCount = c;
     }
     return c;
@@ -79,15 +77,11 @@ class MeshFactory {
   // rows `rows` (ascending) of `from`, in the state `from` is in
   template <typename T>
   static ptr::value<Unity<T>> gathered(ptr::value<Unity<T>> from, const std::vector<uint32_t>& rows) {
-    MemoryState origin = from->getMemoryState();
-    if (origin == gpu || from->getFore() == gpu) from->transferMemoryTo(cpu);
+    CpuRead<T> onCpu(from);
     ptr::host<T> values((long)rows.size(), true);
     for (size_t k = 0; k < rows.size(); ++k) values.get()[k] = from->host.get()[rows[k]];
     ptr::value<Unity<T>> out(values, (unsigned long)rows.size(), cpu, true);
-    if (origin == gpu) {
-      from->setMemoryState(gpu);
-      out->setMemoryState(gpu);
-    }
+    if (onCpu.entry() == gpu) out->setMemoryState(gpu);
     return out;
   }
   bool usable(int k, const char* what) const {
@@ -155,53 +149,43 @@ class MeshFactory {
       logger.err << "MeshFactory::computeSurfaceNormals: needs a surface of these points (setSurface)";
       return;
     }
-    MemoryState origin = points->getMemoryState();
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
+    GpuRead<float3> onGpu(points);
     const uint32_t n = (uint32_t)points->size();
     normals = ptr::value<Unity<float3>>(ptr::device<float3>(n), (unsigned long)n, gpu);
     HipSafeCall(ssrlcv_hip_memset(normals->device.get(), 0, (size_t)n * sizeof(float3)));
     HipSafeCall(ssrlcv_hip_mesh_normals((const ssrlcv_float3*)points->device.get(), n, surface.vertexIndex->device.get(),
                                         surface.cells->device.get(), surface.gw, surface.gh, (float*)normals->device.get(), nullptr));
     HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (origin == cpu) {
-      points->setMemoryState(cpu);
-      normals->setMemoryState(cpu);
-    }
+    if (onGpu.entry() == cpu) normals->setMemoryState(cpu);
   }
 
   // the surface's triangles as vertex index triples, in state gpu; null without a surface or without a triangle
   ptr::value<Unity<uint3>> faces() {
     if (hasSimplified) return simplifiedFaces;
     if (!hasSurface) return ptr::value<Unity<uint3>>();
-    const size_t wsb = ssrlcv_hip_mesh_triangles_workspace_bytes(surface.gw, surface.gh);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    DeviceScratch ws(ssrlcv_hip_mesh_triangles_workspace_bytes(surface.gw, surface.gh));
     ptr::device<uint32_t> count(1);
     HipSafeCall(ssrlcv_hip_mesh_triangles(surface.vertexIndex->device.get(), surface.cells->device.get(), surface.gw, surface.gh, nullptr,
-                                          0, count.get(), ws.get(), wsb, nullptr));
+                                          0, count.get(), ws.get(), ws.bytes(), nullptr));
     uint32_t t = 0;
     HipSafeCall(ssrlcv_hip_memcpy(&t, count.get(), sizeof t, 1));
     if (t == 0) return ptr::value<Unity<uint3>>();
     ptr::value<Unity<uint3>> out(nullptr, (unsigned long)t, gpu);
     HipSafeCall(ssrlcv_hip_mesh_triangles(surface.vertexIndex->device.get(), surface.cells->device.get(), surface.gw, surface.gh,
-                                          (uint32_t*)out->device.get(), t, count.get(), ws.get(), wsb, nullptr));
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+                                          (uint32_t*)out->device.get(), t, count.get(), ws.get(), ws.bytes(), nullptr));
     return out;
   }
 
   // m_i: the mean distance of every point to its k nearest neighbours (+inf for non-finite points)
   ptr::value<Unity<float>> calculateAverageDistancesToNeighbors(int k) {
     if (!usable(k, "calculateAverageDistancesToNeighbors")) return ptr::value<Unity<float>>();
-    MemoryState origin = points->getMemoryState();
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
+    GpuRead<float3> onGpu(points);
     const unsigned long n = points->size();
     ptr::device<ssrlcv_float3> kept(n);
     ptr::device<float> mean(n);
     filter(k, 0.0f, kept, nullptr, &mean);
     ptr::value<Unity<float>> out(mean, n, gpu);
-    if (origin == cpu) {
-      points->setMemoryState(cpu);
-      out->setMemoryState(cpu);
-    }
+    if (onGpu.entry() == cpu) out->setMemoryState(cpu);
     return out;
   }
 
@@ -214,12 +198,10 @@ class MeshFactory {
       logger.err << "MeshFactory::filterByNeighborDistance: drops the simplified surface (filter before simplifySurface)";
       clearSurface();
     }
-    MemoryState origin = points->getMemoryState();
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
     const unsigned long n = points->size();
     const bool withNormals = normals != nullptr && normals->size() == n;
-    MemoryState originN = withNormals ? normals->getMemoryState() : null;
-    if (withNormals && (originN == cpu || normals->getFore() == cpu)) normals->transferMemoryTo(gpu);
+    // the guards hold the Unitys that came in: `points` and `normals` are replaced below
+    GpuRead<float3> onGpu(points), normalsOnGpu(withNormals ? normals : ptr::value<Unity<float3>>());
     ptr::device<ssrlcv_float3> kept(n);
     ptr::device<float> keptNormals(withNormals ? 3 * n : 1);
     const uint32_t c = filter(k, sigma, kept, withNormals ? &keptNormals : nullptr, nullptr, hasSurface);
@@ -234,11 +216,11 @@ class MeshFactory {
     }
     points = ptr::value<Unity<float3>>(ptr::device<float3>(c), (unsigned long)c, gpu);
     HipSafeCall(ssrlcv_hip_memcpy(points->device.get(), kept.get(), (size_t)c * sizeof(float3), 2));
-    if (origin == cpu) points->setMemoryState(cpu);
+    if (onGpu.entry() == cpu) points->setMemoryState(cpu);
     if (withNormals) {
       normals = ptr::value<Unity<float3>>(ptr::device<float3>(c), (unsigned long)c, gpu);
       HipSafeCall(ssrlcv_hip_memcpy(normals->device.get(), keptNormals.get(), (size_t)c * sizeof(float3), 2));
-      if (originN == cpu) normals->setMemoryState(cpu);
+      if (normalsOnGpu.entry() == cpu) normals->setMemoryState(cpu);
     } else if (normals != nullptr) {
       normals = ptr::value<Unity<float3>>();  // computed for another cloud
     }
@@ -247,8 +229,7 @@ class MeshFactory {
   // unit normals from the k nearest neighbours, oriented towards viewpoint (e.g. the mean camera position)
   void computeNormals(int k, float3 viewpoint) {
     if (!usable(k, "computeNormals")) return;
-    MemoryState origin = points->getMemoryState();
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
+    GpuRead<float3> onGpu(points);
     const uint32_t n = (uint32_t)points->size();
     ptr::device<uint32_t> nbr((size_t)n * k);
     knn(k, nbr, nullptr);
@@ -256,10 +237,7 @@ class MeshFactory {
     const ssrlcv_float3 vp = {viewpoint.x, viewpoint.y, viewpoint.z};
     HipSafeCall(ssrlcv_hip_point_normals((const ssrlcv_float3*)points->device.get(), n, nbr.get(), (uint32_t)k, vp,
                                          (float*)normals->device.get(), nullptr));
-    if (origin == cpu) {
-      points->setMemoryState(cpu);
-      normals->setMemoryState(cpu);
-    }
+    if (onGpu.entry() == cpu) normals->setMemoryState(cpu);
   }
 
   // ---- the surface model (include/ssrlcv_hip.h "surface model"): the clouds of several pairs become one surface through a
@@ -276,15 +254,11 @@ class MeshFactory {
       logger.err << "MeshFactory::generateHeightMap: needs points and a grid with a cell";
       return ptr::value<Unity<float>>();
     }
-    MemoryState origin = points->getMemoryState();
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
-    const size_t wsb = ssrlcv_hip_dsm_rasterize_workspace_bytes(frame.w, frame.h);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float3> onGpu(points);
+    DeviceScratch ws(ssrlcv_hip_dsm_rasterize_workspace_bytes(frame.w, frame.h));
     ptr::value<Unity<float>> height(nullptr, cells, gpu);
     HipSafeCall(ssrlcv_hip_dsm_rasterize((const ssrlcv_float3*)points->device.get(), (uint32_t)points->size(), &frame, rule, height->device.get(),
-                                         nullptr, nullptr, ws.get(), wsb, nullptr));
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    if (origin == cpu) points->setMemoryState(cpu);
+                                         nullptr, nullptr, ws.get(), ws.bytes(), nullptr));
     return height;
   }
 
@@ -299,15 +273,14 @@ class MeshFactory {
       logger.err << "MeshFactory::fuseHeightMaps: needs 1 to 8 maps of a grid with a cell";
       return ptr::value<Unity<float>>();
     }
-    std::vector<MemoryState> origin;
+    std::deque<GpuRead<float>> onGpu;  // a deque constructs its guards in place
     std::vector<const float*> dev;
     for (auto& m : maps) {
       if (m == nullptr || m->size() != cells) {
         logger.err << "MeshFactory::fuseHeightMaps: every map has w h entries";
         return ptr::value<Unity<float>>();
       }
-      origin.push_back(m->getMemoryState());
-      if (origin.back() != gpu) m->setMemoryState(gpu);
+      onGpu.emplace_back(m);
       dev.push_back(m->device.get());
     }
     ptr::value<Unity<float>> out(nullptr, cells, gpu);
@@ -315,8 +288,6 @@ class MeshFactory {
     HipSafeCall(ssrlcv_hip_dsm_fuse(dev.data(), (uint32_t)maps.size(), w, h, minViews, maxSpread, rule, out->device.get(),
                                     views ? (*views)->device.get() : nullptr, nullptr));
     HipSafeCall(ssrlcv_hip_device_synchronize());
-    for (size_t k = 0; k < maps.size(); ++k)
-      if (origin[k] != gpu) maps[k]->setMemoryState(origin[k]);
     return out;
   }
 
@@ -353,14 +324,10 @@ class MeshFactory {
       logger.err << "MeshFactory::morphology: the map has w h entries";
       return ptr::value<Unity<float>>();
     }
-    MemoryState origin = height->getMemoryState();
-    if (origin != gpu) height->setMemoryState(gpu);
-    const size_t wsb = ssrlcv_hip_dsm_morphology_workspace_bytes(w, h);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float> onGpu(height);
+    DeviceScratch ws(ssrlcv_hip_dsm_morphology_workspace_bytes(w, h));
     ptr::value<Unity<float>> out(nullptr, cells, gpu);
-    const int status = ssrlcv_hip_dsm_morphology(height->device.get(), out->device.get(), w, h, radius, op, ws.get(), wsb, nullptr);
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    if (origin != gpu) height->setMemoryState(origin);
+    const int status = ssrlcv_hip_dsm_morphology(height->device.get(), out->device.get(), w, h, radius, op, ws.get(), ws.bytes(), nullptr);
     if (status != SSRLCV_OK) {
       logger.err.printf("MeshFactory::morphology: refused (%s)", ssrlcv_hip_status_string(status));
       return ptr::value<Unity<float>>();
@@ -383,16 +350,12 @@ class MeshFactory {
       params.radius[k] = radii[k];
       params.threshold[k] = thresholds[k];
     }
-    MemoryState origin = height->getMemoryState();
-    if (origin != gpu) height->setMemoryState(gpu);
-    const size_t wsb = ssrlcv_hip_dsm_terrain_workspace_bytes(w, h);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float> onGpu(height);
+    DeviceScratch ws(ssrlcv_hip_dsm_terrain_workspace_bytes(w, h));
     ptr::value<Unity<float>> terrain(nullptr, cells, gpu);
     if (level) *level = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
     const int status = ssrlcv_hip_dsm_terrain(height->device.get(), w, h, &params, terrain->device.get(), level ? (*level)->device.get() : nullptr, nullptr,
-                                              ws.get(), wsb, nullptr);
-    HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (origin != gpu) height->setMemoryState(origin);
+                                              ws.get(), ws.bytes(), nullptr);
     if (status != SSRLCV_OK) {
       logger.err.printf("MeshFactory::extractTerrain: refused (%s)", ssrlcv_hip_status_string(status));
       if (level) *level = ptr::value<Unity<unsigned char>>();
@@ -408,14 +371,10 @@ class MeshFactory {
       logger.err << "MeshFactory::objectHeights: both maps have w h entries";
       return ptr::value<Unity<float>>();
     }
-    MemoryState originA = height->getMemoryState(), originB = terrain->getMemoryState();
-    if (originA != gpu) height->setMemoryState(gpu);
-    if (originB != gpu) terrain->setMemoryState(gpu);
+    GpuRead<float> heightOnGpu(height), terrainOnGpu(terrain);
     ptr::value<Unity<float>> out(nullptr, cells, gpu);
     HipSafeCall(ssrlcv_hip_dsm_subtract(height->device.get(), terrain->device.get(), w, h, out->device.get(), nullptr));
     HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (originA != gpu) height->setMemoryState(originA);
-    if (originB != gpu && terrain != height) terrain->setMemoryState(originB);
     return out;
   }
 
@@ -427,25 +386,21 @@ class MeshFactory {
       logger.err << "MeshFactory::setPointsFromHeightMap: the map has frame.w frame.h entries";
       return;
     }
-    MemoryState origin = height->getMemoryState();
-    if (origin != gpu) height->setMemoryState(gpu);
-    const size_t wsb = ssrlcv_hip_dsm_points_workspace_bytes(frame.w, frame.h);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float> onGpu(height);
     ptr::device<uint32_t> count(1);
-    HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, nullptr, 0, count.get(), ws.get(), wsb, nullptr));
+    DeviceScratch ws(ssrlcv_hip_dsm_points_workspace_bytes(frame.w, frame.h));
+    HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, nullptr, 0, count.get(), ws.get(), ws.bytes(), nullptr));
     uint32_t n = 0;
     HipSafeCall(ssrlcv_hip_memcpy(&n, count.get(), sizeof n, 1));
     if (n == 0) {
       setPoints(ptr::value<Unity<float3>>());
-    } else {
-      ptr::value<Unity<float3>> pts(nullptr, (unsigned long)n, gpu);
-      HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, (ssrlcv_float3*)pts->device.get(), n, count.get(), ws.get(), wsb, nullptr));
-      HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-      setPoints(pts);
-      surfaceHeight = copyToGpu(height);  // simplifySurface works on the map the points came from
-      surfaceFrame = frame;
+      return;
     }
-    if (origin != gpu) height->setMemoryState(origin);
+    ptr::value<Unity<float3>> pts(nullptr, (unsigned long)n, gpu);
+    HipSafeCall(ssrlcv_hip_dsm_points(height->device.get(), &frame, (ssrlcv_float3*)pts->device.get(), n, count.get(), ws.get(), ws.bytes(), nullptr));
+    setPoints(pts);
+    surfaceHeight = copyToGpu(height);  // simplifySurface works on the map the points came from
+    surfaceFrame = frame;
   }
 
   // ---- surface simplification (include/ssrlcv_hip.h "surface simplification"): the surface of the height map thinned to a
@@ -467,10 +422,10 @@ class MeshFactory {
     ssrlcv_mesh_params meshParams = {1u, std::numeric_limits<float>::infinity()};
     const size_t meshWsb = ssrlcv_hip_disparity_mesh_workspace_bytes(w, h, &meshParams);
     const size_t wsb = std::max(meshWsb, ssrlcv_hip_dsm_simplify_mesh_workspace_bytes(w, h));
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
     const unsigned long meshCells = (unsigned long)(w - 1) * (h - 1);
     ptr::device<unsigned char> gridCells(meshCells ? meshCells : 1);
     ptr::device<uint32_t> nodeIndex(cells), vertexIndex(cells), counts(2);
+    DeviceScratch ws(wsb);
     HipSafeCall(ssrlcv_hip_disparity_mesh(height, w, h, &meshParams, nodeIndex.get(), gridCells.get(), counts.get(), ws.get(), wsb, nullptr));
     uint32_t c[2] = {0, 0};
     HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), 4, 1));
@@ -500,7 +455,7 @@ class MeshFactory {
     HipSafeCall(ssrlcv_hip_dsm_simplify_mesh(height, error.get(), w, h, tolerance, nodeIndex.get(), vertexIndex.get(), (uint32_t*)tris->device.get(), t,
                                              counts.get(), kept.get(), m, counts.get() + 1, ws.get(), wsb, nullptr));
     std::vector<uint32_t> keptHost(m);
-    HipSafeCall(ssrlcv_hip_memcpy(keptHost.data(), kept.get(), (size_t)m * 4, 1));  // synchronises: the workspace may go out of scope
+    HipSafeCall(ssrlcv_hip_memcpy(keptHost.data(), kept.get(), (size_t)m * 4, 1));
     const unsigned long n = points->size();
     const bool withNormals = normals != nullptr && normals->size() == n, withColors = colors != nullptr && colors->size() == n;
     points = gathered(points, keptHost);
@@ -530,33 +485,24 @@ class MeshFactory {
       return ptr::value<Unity<unsigned char>>();
     }
     std::vector<ssrlcv_ortho_view> views(images.size());
-    std::vector<MemoryState> origin;
+    std::deque<GpuRead<unsigned char>> imagesOnGpu;  // a deque constructs its guards in place
     for (size_t k = 0; k < images.size(); ++k) {
       views[k].image = nullptr;
       if (ssrlcv_dsm_ortho_view_host(&cameras[k], &frame, &views[k]) != SSRLCV_OK || images[k] == nullptr ||
           images[k]->size() != (unsigned long)views[k].w * views[k].h) {
         logger.err.printf("MeshFactory::generateOrthoImage: view %lu: a refused camera, or an image that has not its size", (unsigned long)k);
-        for (size_t i = 0; i < origin.size(); ++i)
-          if (origin[i] != gpu) images[i]->setMemoryState(origin[i]);
         return ptr::value<Unity<unsigned char>>();
       }
-      origin.push_back(images[k]->getMemoryState());
-      if (origin.back() != gpu) images[k]->setMemoryState(gpu);
+      imagesOnGpu.emplace_back(images[k]);
       views[k].image = images[k]->device.get();
     }
-    MemoryState originH = height->getMemoryState();
-    if (originH != gpu) height->setMemoryState(gpu);
-    const size_t wsb = ssrlcv_hip_dsm_ortho_workspace_bytes(frame.w, frame.h, (uint32_t)views.size());
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float> heightOnGpu(height);
+    DeviceScratch ws(ssrlcv_hip_dsm_ortho_workspace_bytes(frame.w, frame.h, (uint32_t)views.size()));
     ptr::value<Unity<unsigned char>> ortho(nullptr, cells, gpu);
     if (seen) *seen = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
     if (which) *which = ptr::value<Unity<unsigned char>>(nullptr, cells, gpu);
     HipSafeCall(ssrlcv_hip_dsm_ortho(height->device.get(), &frame, views.data(), (uint32_t)views.size(), &params, ortho->device.get(),
-                                     seen ? (*seen)->device.get() : nullptr, which ? (*which)->device.get() : nullptr, ws.get(), wsb, nullptr));
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
-    if (originH != gpu) height->setMemoryState(originH);
-    for (size_t k = 0; k < images.size(); ++k)
-      if (origin[k] != gpu) images[k]->setMemoryState(origin[k]);
+                                     seen ? (*seen)->device.get() : nullptr, which ? (*which)->device.get() : nullptr, ws.get(), ws.bytes(), nullptr));
     return ortho;
   }
 
@@ -567,19 +513,18 @@ class MeshFactory {
       logger.err << "MeshFactory::setVertexColors: needs points, and an ortho-image and a height map of one grid";
       return;
     }
-    MemoryState originO = ortho->getMemoryState(), originH = height->getMemoryState();
-    if (originO == gpu || ortho->getFore() == gpu) ortho->transferMemoryTo(cpu);
-    if (originH == gpu || height->getFore() == gpu) height->transferMemoryTo(cpu);
-    const unsigned char* grey = ortho->host.get();
-    const float* z = height->host.get();
     std::vector<unsigned char> kept;
-    for (unsigned long c = 0; c < height->size(); ++c) {
-      uint32_t bits;
-      std::memcpy(&bits, z + c, 4);
-      if (bits != 0x7FC00000u) kept.push_back(grey[c]);
+    {
+      CpuRead<unsigned char> orthoOnCpu(ortho);
+      CpuRead<float> heightOnCpu(height);
+      const unsigned char* grey = ortho->host.get();
+      const float* z = height->host.get();
+      for (unsigned long c = 0; c < height->size(); ++c) {
+        uint32_t bits;
+        std::memcpy(&bits, z + c, 4);
+        if (bits != 0x7FC00000u) kept.push_back(grey[c]);
+      }
     }
-    if (originO == gpu) ortho->setMemoryState(gpu);
-    if (originH == gpu) height->setMemoryState(gpu);
     if (kept.size() != points->size()) {
       logger.err.printf("MeshFactory::setVertexColors: the map has %lu valid cells, the cloud %lu points", (unsigned long)kept.size(), points->size());
       return;
@@ -611,12 +556,10 @@ class MeshFactory {
     const unsigned long meshCells = (unsigned long)(frame.w - 1) * (frame.h - 1);
     referenceCells = ptr::value<Unity<unsigned char>>(nullptr, meshCells ? meshCells : 1, gpu);  // never NULL: NULL would mean CELL mode
     ssrlcv_mesh_params params = {1u, maxJump};
-    const size_t wsb = ssrlcv_hip_disparity_mesh_workspace_bytes(frame.w, frame.h, &params);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
     ptr::device<uint32_t> vertexIndex(cells), count(1);
+    DeviceScratch ws(ssrlcv_hip_disparity_mesh_workspace_bytes(frame.w, frame.h, &params));
     HipSafeCall(ssrlcv_hip_disparity_mesh(referenceHeight->device.get(), frame.w, frame.h, &params, vertexIndex.get(), referenceCells->device.get(),
-                                          count.get(), ws.get(), wsb, nullptr));
-    HipSafeCall(ssrlcv_hip_device_synchronize());  // the workspace goes out of scope
+                                          count.get(), ws.get(), ws.bytes(), nullptr));
     hasReference = true;
   }
 
@@ -636,13 +579,11 @@ class MeshFactory {
       logger.err.printf("MeshFactory::calculatePerPointDifference: planeNormal is not the reference frame's ez (dot %g)", (double)dot);
       return ptr::value<Unity<float>>();
     }
-    MemoryState origin = cloud->getMemoryState();
-    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
+    GpuRead<float3> onGpu(cloud);
     ptr::value<Unity<float>> diff(nullptr, cloud->size(), gpu);
     HipSafeCall(ssrlcv_hip_dsm_difference((const ssrlcv_float3*)cloud->device.get(), (uint32_t)cloud->size(), referenceHeight->device.get(),
                                           &referenceFrame, referenceCells->device.get(), diff->device.get(), nullptr));
     HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (origin == cpu) cloud->setMemoryState(cpu);
     return diff;
   }
 
@@ -658,15 +599,12 @@ class MeshFactory {
   static ssrlcv_diff_stats differenceStats(ptr::value<Unity<float>> values, float center, bool absolute, const std::vector<uint32_t>& quantiles) {
     ssrlcv_diff_stats_params params = {center, absolute ? 1u : 0u, (uint32_t)quantiles.size(), {0, 0, 0, 0, 0, 0, 0, 0}};
     for (size_t k = 0; k < quantiles.size() && k < 8; ++k) params.quantile[k] = quantiles[k];
-    MemoryState origin = values->getMemoryState();
-    if (origin != gpu) values->setMemoryState(gpu);
-    const size_t wsb = ssrlcv_hip_difference_stats_workspace_bytes((uint32_t)values->size(), &params);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
+    GpuRead<float> onGpu(values);
     ptr::device<ssrlcv_diff_stats> record(1);
-    HipSafeCall(ssrlcv_hip_difference_stats(values->device.get(), (uint32_t)values->size(), &params, record.get(), ws.get(), wsb, nullptr));
+    DeviceScratch ws(ssrlcv_hip_difference_stats_workspace_bytes((uint32_t)values->size(), &params));
+    HipSafeCall(ssrlcv_hip_difference_stats(values->device.get(), (uint32_t)values->size(), &params, record.get(), ws.get(), ws.bytes(), nullptr));
     ssrlcv_diff_stats host;
-    HipSafeCall(ssrlcv_hip_memcpy(&host, record.get(), sizeof host, 1));  // synchronises: the workspace may go out of scope
-    if (origin != gpu) values->setMemoryState(origin);
+    HipSafeCall(ssrlcv_hip_memcpy(&host, record.get(), sizeof host, 1));
     return host;
   }
 
@@ -731,9 +669,8 @@ class MeshFactory {
       return reg;
     }
     const uint32_t n = (uint32_t)cloud->size();
-    MemoryState origin = cloud->getMemoryState();
-    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
-    const ssrlcv_float3* points = (const ssrlcv_float3*)cloud->device.get();
+    GpuRead<float3> onGpu(cloud);
+    const ssrlcv_float3* points =(const ssrlcv_float3*)cloud->device.get();
     ptr::value<Unity<float3>> posed(nullptr, n, gpu);
     ptr::value<Unity<float>> diff(nullptr, n, gpu);
     auto difference = [&]() {
@@ -764,9 +701,8 @@ class MeshFactory {
       ++has;
     }
     for (int a = 0; a < 3; ++a) reg.pose.pivot[a] = has ? (float)(sum[a] / (double)has) : 0.0f;
-    const size_t wsb = ssrlcv_hip_register_terms_workspace_bytes(n);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
     ptr::device<ssrlcv_register_terms> record(1);
+    DeviceScratch ws(ssrlcv_hip_register_terms_workspace_bytes(n));
     const double inf = std::numeric_limits<double>::infinity();
     for (unsigned it = 0; it < iterations; ++it) {
       ssrlcv_register_params params = {0.0f, (float)inf};
@@ -778,7 +714,7 @@ class MeshFactory {
         params.gate = (float)((double)gateFactor * (1.4826 * (double)differenceStats(diff, params.center, true, {5000u}).quantile[0]));
       }
       HipSafeCall(ssrlcv_hip_register_terms(points, n, &reg.pose, referenceHeight->device.get(), &referenceFrame, referenceCells->device.get(), &params,
-                                            record.get(), ws.get(), wsb, nullptr));
+                                            record.get(), ws.get(), ws.bytes(), nullptr));
       ssrlcv_register_terms terms;
       HipSafeCall(ssrlcv_hip_memcpy(&terms, record.get(), sizeof terms, 1));
       RegistrationStep step;
@@ -808,7 +744,6 @@ class MeshFactory {
         break;
       }
     }
-    if (origin == cpu) cloud->setMemoryState(cpu);
     return reg;
   }
 
@@ -844,9 +779,7 @@ class MeshFactory {
       return found;
     }
     if (start) found.pose = *start;
-    MemoryState originM = moving->getMemoryState(), originR = reference->getMemoryState();
-    if (originM != gpu) moving->setMemoryState(gpu);
-    if (originR != gpu && reference != moving) reference->setMemoryState(gpu);
+    GpuRead<float> movingOnGpu(moving), referenceOnGpu(reference);
     std::vector<float> hostM(cells), hostR(cells);  // the gate's slices are cut on the host
     HipSafeCall(ssrlcv_hip_memcpy(hostM.data(), moving->device.get(), cells * sizeof(float), 1));
     HipSafeCall(ssrlcv_hip_memcpy(hostR.data(), reference->device.get(), cells * sizeof(float), 1));
@@ -891,19 +824,18 @@ class MeshFactory {
         }
       }
       const size_t tableBytes = ssrlcv_shift_table_bytes(level.params.radius);
-      const size_t wsb = ssrlcv_hip_shift_search_workspace_bytes(w, h, &level.params);
       if (tableBytes == 0) { ok = false; break; }
-      ptr::device<unsigned char> ws(wsb ? wsb : 1), table(tableBytes);
+      ptr::device<unsigned char> table(tableBytes);
+      DeviceScratch ws(ssrlcv_hip_shift_search_workspace_bytes(w, h, &level.params));
       const int status = ssrlcv_hip_shift_search(moving->device.get(), reference->device.get(), w, h, &level.params, (ssrlcv_shift_table*)table.get(), ws.get(),
-                                                 wsb, nullptr);
+                                                 ws.bytes(), nullptr);
       if (status != SSRLCV_OK) {
         logger.err.printf("MeshFactory::searchShift: refused (%s)", ssrlcv_hip_status_string(status));
-        HipSafeCall(ssrlcv_hip_device_synchronize());
         ok = false;
         break;
       }
       level.table.resize(tableBytes);
-      HipSafeCall(ssrlcv_hip_memcpy(level.table.data(), table.get(), tableBytes, 1));  // synchronises: the workspace may go out of scope
+      HipSafeCall(ssrlcv_hip_memcpy(level.table.data(), table.get(), tableBytes, 1));
       ssrlcv_shift_table head;
       std::memcpy(&head, level.table.data(), sizeof head);
       const uint32_t least = (uint32_t)(minOverlap * (double)head.validMoving);
@@ -915,8 +847,6 @@ class MeshFactory {
       best[0] = level.result.shiftX, best[1] = level.result.shiftY;
       found.levels.push_back(level);
     }
-    if (originM != gpu) moving->setMemoryState(originM);
-    if (originR != gpu && reference != moving) reference->setMemoryState(originR);
     if (!ok || found.levels.empty()) return found;
     found.result = found.levels.back().result;
     found.shiftX = (double)best[0] + found.result.subX;
@@ -957,32 +887,28 @@ class MeshFactory {
       logger.err << "MeshFactory::renderView: needs a surface of these points (setSurface) and a camera the ortho-image takes";
       return r;
     }
-    MemoryState origin = points->getMemoryState(), originC = colored ? colors->getMemoryState() : gpu;
-    if (origin == cpu || points->getFore() == cpu) points->transferMemoryTo(gpu);
-    if (colored && (originC == cpu || colors->getFore() == cpu)) colors->transferMemoryTo(gpu);
+    GpuRead<float3> onGpu(points);
+    GpuRead<unsigned char> colorsOnGpu(colored ? colors : ptr::value<Unity<unsigned char>>());
     const uint32_t n = (uint32_t)points->size();
     const unsigned long pixels = (unsigned long)view.w * view.h;
     const ssrlcv_render_params params = {maxExtent};
-    const size_t wsb = ssrlcv_hip_mesh_render_workspace_bytes(n, view.w, view.h);
-    ptr::device<unsigned char> ws(wsb ? wsb : 1);
     ptr::device<uint32_t> counts(3);
+    DeviceScratch ws(ssrlcv_hip_mesh_render_workspace_bytes(n, view.w, view.h));
     r.w = view.w, r.h = view.h;
     r.depth = ptr::value<Unity<float>>(nullptr, pixels, gpu);
     r.triangle = ptr::value<Unity<unsigned int>>(nullptr, pixels, gpu);
     r.shade = ptr::value<Unity<unsigned char>>(nullptr, pixels, gpu);
     const int status = ssrlcv_hip_mesh_render((const ssrlcv_float3*)points->device.get(), n, colored ? colors->device.get() : nullptr,
                                               surface.vertexIndex->device.get(), surface.cells->device.get(), surface.gw, surface.gh, &view, &params,
-                                              r.depth->device.get(), r.triangle->device.get(), r.shade->device.get(), counts.get(), ws.get(), wsb, nullptr);
+                                              r.depth->device.get(), r.triangle->device.get(), r.shade->device.get(), counts.get(), ws.get(), ws.bytes(), nullptr);
     if (status == SSRLCV_OK) {
       uint32_t c[3] = {0, 0, 0};
-      HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), sizeof c, 1));  // synchronises: the workspace may go out of scope
+      HipSafeCall(ssrlcv_hip_memcpy(c, counts.get(), sizeof c, 1));
       r.drawn = c[0], r.tooLarge = c[1], r.unusable = c[2];
     } else {
       logger.err.printf("MeshFactory::renderView: refused (%s)", ssrlcv_hip_status_string(status));
       r = RenderedView();
     }
-    if (origin == cpu) points->setMemoryState(cpu);
-    if (colored && originC == cpu) colors->setMemoryState(cpu);
     return r;
   }
 
@@ -998,13 +924,13 @@ class MeshFactory {
       logger.err << "MeshFactory::photoConsistency: needs a view that renders and an image of the camera's size";
       return p;
     }
-    MemoryState origin = image->getMemoryState();
-    if (origin == cpu || image->getFore() == cpu) image->transferMemoryTo(gpu);
     p.residual = ptr::value<Unity<float>>(nullptr, image->size(), gpu);
-    HipSafeCall(ssrlcv_hip_image_residual(image->device.get(), p.view.shade->device.get(), p.view.depth->device.get(), p.view.w, p.view.h,
-                                          p.residual->device.get(), nullptr));
-    HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (origin == cpu) image->setMemoryState(cpu);
+    {
+      GpuRead<unsigned char> onGpu(image);
+      HipSafeCall(ssrlcv_hip_image_residual(image->device.get(), p.view.shade->device.get(), p.view.depth->device.get(), p.view.w, p.view.h,
+                                            p.residual->device.get(), nullptr));
+      HipSafeCall(ssrlcv_hip_device_synchronize());
+    }
     const ssrlcv_diff_stats s = differenceStats(p.residual, 0.0f, false, {5000u});
     p.coverage = (double)s.finite / (double)s.n;
     if (s.finite == 0) return p;

@@ -121,9 +121,7 @@ inline void applyRelativePose(const Image::Camera& a, const Pose& pose, Image::C
 // reference builds it and where its bundle generator expects it (src/PointCloudFactory.cu:840-846).
 inline MatchSet pairwiseMatchSet(const ptr::value<Unity<DMatch>>& pairs, float* largestDistance) {
   const unsigned long n = pairs->size();
-  const MemoryState before = pairs->getMemoryState();
-  if (before == cpu) pairs->setMemoryState(gpu);
-  else if (before == both && pairs->getFore() == cpu) pairs->transferMemoryTo(gpu);
+  GpuRead<DMatch> onGpu(pairs);
   MatchSet ms;
   ms.keyPoints = ptr::value<Unity<KeyPoint>>(nullptr, 2 * n, gpu);
   ms.matches = ptr::value<Unity<MultiMatch>>(nullptr, n, gpu);
@@ -136,7 +134,6 @@ inline MatchSet pairwiseMatchSet(const ptr::value<Unity<DMatch>>& pairs, float* 
   HipSafeCall(ssrlcv_hip_memcpy(largestDistance, peak.get(), sizeof(float), 1));
   ms.keyPoints->setMemoryState(cpu);
   ms.matches->setMemoryState(cpu);
-  if (before == cpu) pairs->setMemoryState(cpu);
   return ms;
 }
 

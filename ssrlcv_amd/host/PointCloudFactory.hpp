@@ -16,6 +16,7 @@
 #include <vector>
 #include "Image.hpp"
 #include "MatchFactory.hpp"
+#include "Scoped.hpp"
 #include "matrix_util.hpp"
 
 namespace ssrlcv {
@@ -42,6 +43,7 @@ class PointCloudFactory {
 
   ptr::value<Unity<float3>> triangulate(bool nview, BundleSet bundleSet, ptr::value<Unity<float>> errors, float* errSum,
                                         float* cutoff, bool wantPoints) {
+    // no guards: upstream's end state is not the entry state -- lines, bundles, errors and the cloud all end on the cpu
     bundleSet.lines->transferMemoryTo(gpu);
     bundleSet.bundles->transferMemoryTo(gpu);
     uint32_t n = (uint32_t)bundleSet.bundles->size();
@@ -92,6 +94,7 @@ class PointCloudFactory {
   BundleSet generateBundles(MatchSet* matchSet, std::vector<ptr::value<Image>> images) {
     ptr::value<Unity<Bundle>> bundles(nullptr, matchSet->matches->size(), gpu);
     ptr::value<Unity<Bundle::Line>> lines(nullptr, matchSet->keyPoints->size(), gpu);
+    // no guards: upstream leaves the match set on the cpu whatever state it came in
     matchSet->matches->transferMemoryTo(gpu);
     matchSet->keyPoints->transferMemoryTo(gpu);
     uint32_t nb = (uint32_t)bundles->size();
@@ -146,8 +149,7 @@ class PointCloudFactory {
   // X = (kp0.x - center.x) Z / foc, Y likewise (ssrlcv_hip_stereo_points); the four-argument form measures from the pixel
   // origin.  Like the triangulators the cloud comes back on the cpu; the matches are restored to their origin state.
   ptr::value<Unity<float3>> stereo_disparity(ptr::value<Unity<Match>> matches, float foc, float baseline, float doffset, float2 center) {
-    MemoryState origin = matches->getMemoryState();
-    if (origin != gpu) matches->setMemoryState(gpu);
+    GpuRead<Match> onGpu(matches);
     const uint32_t n = (uint32_t)matches->size();
     ptr::value<Unity<float3>> pointcloud(nullptr, (unsigned long)n, gpu);
     HipSafeCall(ssrlcv_hip_stereo_points(reinterpret_cast<const ssrlcv_match*>(matches->device.get()), n, foc, baseline, doffset, center.x,
@@ -155,7 +157,6 @@ class PointCloudFactory {
     HipCheckError();
     pointcloud->transferMemoryTo(cpu);
     pointcloud->clear(gpu);
-    if (origin != gpu) matches->setMemoryState(origin);
     return pointcloud;
   }
   ptr::value<Unity<float3>> stereo_disparity(ptr::value<Unity<Match>> matches, float foc, float baseline, float doffset) {
@@ -209,6 +210,7 @@ class PointCloudFactory {
   void filterOnDevice(MatchSet* matchSet, std::vector<ptr::value<Image>>& images, int kind, float cutoff, float sigma, int sampleJump) {
     const bool twoView = images.size() == 2;
     const uint32_t nb = (uint32_t)matchSet->matches->size(), nk = (uint32_t)matchSet->keyPoints->size();
+    // no guards: the match set ends on the cpu, as upstream's generateBundles leaves it
     matchSet->matches->transferMemoryTo(gpu);
     matchSet->keyPoints->transferMemoryTo(gpu);
     auto* mm = reinterpret_cast<const ssrlcv_multimatch*>(matchSet->matches->device.get());
@@ -221,7 +223,7 @@ class PointCloudFactory {
       ptr::device<ssrlcv_camera> cams_d((long)cams.size());
       HipSafeCall(ssrlcv_hip_memcpy(cams_d.get(), cams.data(), cams.size() * sizeof(ssrlcv_camera), 0));
       HipSafeCall(ssrlcv_hip_generate_bundles(mm, kp, nb, cams_d.get(), (uint32_t)cams.size(), bundles.get(), lines.get(), nullptr));
-      HipSafeCall(ssrlcv_hip_device_synchronize());  // cams_d goes out of scope
+      HipSafeCall(ssrlcv_hip_device_synchronize());  // cams_d is freed at the end of this block
     } else {
       std::vector<ssrlcv_pushbroom> pbs(images.size());
       for (size_t i = 0; i < images.size(); ++i) std::memcpy(&pbs[i], &images[i]->pushbroom, sizeof(ssrlcv_pushbroom));
@@ -246,13 +248,12 @@ class PointCloudFactory {
       HipSafeCall(ssrlcv_hip_error_sample_cutoff(errors.get(), nb, (uint32_t)sampleJump, sigma, cut_d.get(), nullptr));
       tri(cut_d.get());
     }
-    const size_t wsBytes = ssrlcv_hip_filter_workspace_bytes(nb);
-    ptr::device<unsigned char> ws((long)wsBytes);
     ptr::value<Unity<MultiMatch>> mmOut(nullptr, (unsigned long)nb, gpu);
     ptr::value<Unity<KeyPoint>> kpOut(nullptr, (unsigned long)nk, gpu);
     ptr::device<uint32_t> counts_d(3);
+    DeviceScratch ws(ssrlcv_hip_filter_workspace_bytes(nb));
     HipSafeCall(ssrlcv_hip_filter_matchset(bundles.get(), kp, nb, reinterpret_cast<ssrlcv_multimatch*>(mmOut->device.get()),
-                                           reinterpret_cast<ssrlcv_keypoint*>(kpOut->device.get()), counts_d.get(), ws.get(), wsBytes, nullptr));
+                                           reinterpret_cast<ssrlcv_keypoint*>(kpOut->device.get()), counts_d.get(), ws.get(), ws.bytes(), nullptr));
     uint32_t counts[3] = {0, 0, 0};
     HipSafeCall(ssrlcv_hip_memcpy(counts, counts_d.get(), sizeof counts, 1));
     HipCheckError();
@@ -291,6 +292,7 @@ class PointCloudFactory {
 
   // f(cameras) for K parameter sets in one launch; params_host = K x (6 * images) floats
   std::vector<float> evaluateCameraSets(MatchSet* matchSet, std::vector<ptr::value<Image>> images, const std::vector<float>& params_host, uint32_t K) {
+    // no guards: the match set ends on the cpu, like generateBundles' (it comes in on the cpu from there)
     matchSet->matches->transferMemoryTo(gpu);
     matchSet->keyPoints->transferMemoryTo(gpu);
     std::vector<ssrlcv_camera> cams;
@@ -483,14 +485,10 @@ class PointCloudFactory {
   // MeshFactory::registerToReference finds such a pose.
   void transformPointCloud(ptr::value<Unity<float3>> cloud, const ssrlcv_register_pose& pose) {
     if (cloud == nullptr || cloud->size() == 0 || cloud->size() > 0xFFFFFFFFul) return;
-    MemoryState origin = cloud->getMemoryState();
-    if (origin == cpu || cloud->getFore() == cpu) cloud->transferMemoryTo(gpu);
+    GpuWrite<float3> onGpu(cloud);
     ssrlcv_float3* p = (ssrlcv_float3*)cloud->device.get();
     HipSafeCall(ssrlcv_hip_transform_points(p, (uint32_t)cloud->size(), &pose, p, nullptr));
     HipSafeCall(ssrlcv_hip_device_synchronize());
-    if (cloud->getFore() != gpu) cloud->setFore(gpu);  // the device holds the moved points
-    if (origin == cpu) cloud->setMemoryState(cpu);     // brings them back
-    else if (origin == both) cloud->transferMemoryTo(cpu);
   }
 
   // Upstream's scalePointCloud / translatePointCloud / rotatePointCloud: a pose built on the host, then transformPointCloud.

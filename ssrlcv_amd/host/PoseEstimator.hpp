@@ -12,6 +12,7 @@
 #include <cstdio>
 #include "Image.hpp"
 #include "MatchFactory.hpp"
+#include "Scoped.hpp"
 #include "matrix_util.hpp"
 
 namespace ssrlcv {
@@ -76,15 +77,14 @@ class PoseEstimator {
   // the RANSAC call behind both public methods; mask / F (device) receive the inlier mask and F when not null
   FMatrixInliers fmatrixRANSAC(unsigned samples, float threshold, uint64_t seed, ptr::device<unsigned char>* mask,
                                ptr::device<float>* Fdev = nullptr) {
-    MemoryState origin = matches->getMemoryState();
-    if (origin == cpu || matches->getFore() == cpu) matches->transferMemoryTo(gpu);
+    GpuRead<Match> onGpu(matches);
     const uint32_t n = (uint32_t)matches->size();
-    ptr::device<unsigned char> ws(ssrlcv_hip_fmatrix_ransac_workspace_bytes(n, samples));
     ptr::device<float> Fown(9);
     ptr::device<uint32_t> count(1);
+    DeviceScratch ws(ssrlcv_hip_fmatrix_ransac_workspace_bytes(n, samples));
     float* Fd = Fdev ? Fdev->get() : Fown.get();
     HipSafeCall(ssrlcv_hip_fmatrix_ransac((const ssrlcv_match*)matches->device.get(), n, samples, threshold, seed, ws.get(),
-                                          ssrlcv_hip_fmatrix_ransac_workspace_bytes(n, samples), Fd, count.get(),
+                                          ws.bytes(), Fd, count.get(),
                                           mask ? mask->get() : nullptr, nullptr, nullptr, nullptr));
     FMatrixInliers out;
     uint32_t c = 0;
@@ -92,7 +92,6 @@ class PoseEstimator {
     HipSafeCall(ssrlcv_hip_memcpy(&c, count.get(), sizeof c, 1));
     out.inliers = c;
     out.valid = c >= 7;
-    if (origin == cpu) matches->setMemoryState(cpu);
     return out;
   }
 
@@ -110,18 +109,17 @@ class PoseEstimator {
   // estimateFMatrixRANSAC with its defaults, then the relative pose of E = K_t^T F K_q (the cheirality vote on its
   // inliers), in LM_optimize's convention.  Without a valid F: an error in the log and the cameras' own relative pose.
   Pose estimatePoseRANSAC() {
-    MemoryState origin = matches->getMemoryState();
-    if (origin == cpu || matches->getFore() == cpu) matches->transferMemoryTo(gpu);
+    GpuRead<Match> onGpu(matches);
     const unsigned long n = matches->size();
     ptr::device<unsigned char> mask(n ? n : 1);
     ptr::device<float> F(9);
     FMatrixInliers fm = fmatrixRANSAC(4096, 1.0f, 0, &mask, &F);
     Pose pose;
     if (fm.valid) {
-      ptr::device<unsigned char> aux(SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES);
+      DeviceScratch aux(SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES);
       HipSafeCall(ssrlcv_hip_pose_from_fmatrix((const ssrlcv_match*)matches->device.get(), (uint32_t)n, mask.get(), F.get(),
                                                (const ssrlcv_camera*)&query->camera, (const ssrlcv_camera*)&target->camera,
-                                               aux.get(), SSRLCV_FMATRIX_AUX_WORKSPACE_BYTES, (ssrlcv_pose*)&pose, nullptr));
+                                               aux.get(), aux.bytes(), (ssrlcv_pose*)&pose, nullptr));
     } else {
       logger.err.printf("PoseEstimator::estimatePoseRANSAC: no valid F-matrix (%lu inliers); using the cameras' relative pose",
                         fm.inliers);
@@ -131,7 +129,6 @@ class PoseEstimator {
       pose.y = b.y / 1000;
       pose.z = b.z / 1000;
     }
-    if (origin == cpu) matches->setMemoryState(cpu);
     return pose;
   }
 
@@ -162,8 +159,7 @@ class PoseEstimator {
 
   // public here (private upstream) so that tests can drive single iterations
   bool LM_iteration(Pose* pose, float* lambda) {
-    MemoryState origin = matches->getMemoryState();
-    if (origin == cpu || matches->getFore() == cpu) matches->transferMemoryTo(gpu);
+    GpuRead<Match> onGpu(matches);
     ptr::device<float> terms(43);
     HipSafeCall(ssrlcv_hip_pose_lm_terms((const ssrlcv_match*)matches->device.get(), (uint32_t)matches->size(),
                                          (const ssrlcv_pose*)pose, (const ssrlcv_camera*)&query->camera,
@@ -204,7 +200,6 @@ class PoseEstimator {
       *lambda /= 4;  // the loop's last doubling plus one real halving
       *pose = newPose;
     }
-    if (origin == cpu) matches->setMemoryState(cpu);
     return ok;
   }
 };

@@ -16,6 +16,7 @@
 #include <vector>
 #include "Feature.hpp"
 #include "Image.hpp"
+#include "Scoped.hpp"
 
 namespace ssrlcv {
 
@@ -96,21 +97,17 @@ class SIFT_FeatureFactory : public FeatureFactory {
                                                                unsigned int maxOrientations,
                                                                float orientationThreshold = 0.8) {
     logger.info.printf("Generating SIFT features for image %d", image->id);
-    MemoryState origin = image->pixels->getMemoryState();
-    // Upstream moves the pixels to the device with a hard setMemoryState(gpu) and back with setMemoryState(origin)
-    // (src/SIFT_FeatureFactory.cu:22-24,166): the second is a device-to-host copy of bytes the host had a moment ago.  The
-    // kernels only READ single-channel pixels, so for cpu-state grey pixels the host copy is kept (transferMemoryTo: state
-    // both) and the way back is clear(gpu): the same state and the same bytes at return, without the copy (0.55 ms of a
-    // 4096^2 image's 6.1).  Colour pixels are converted on the device and take upstream's round trip.
-    const bool keepHost = origin == cpu && image->colorDepth == 1;
-    if (keepHost) image->pixels->transferMemoryTo(gpu);
-    else if (origin != gpu) image->pixels->setMemoryState(gpu);
-    // convert image to BW (src/SIFT_FeatureFactory.cu:26-29)
+    // convert image to BW (src/SIFT_FeatureFactory.cu:26-29): the grey pixels are in the state the colour ones came in
     if (image->colorDepth != 1) {
       convertToBW(image->pixels, image->colorDepth);
       image->colorDepth = 1;
     }
+    // Upstream moves the pixels to the device with a hard setMemoryState(gpu) and back to their origin state
+    // (src/SIFT_FeatureFactory.cu:22-24,166): the second is a device-to-host copy of bytes the host had a moment ago.  The
+    // kernels only READ the grey pixels, so the guard keeps a host copy: the same state and the same bytes at return,
+    // without the copy (0.55 ms of a 4096^2 image's 6.1).
     if (dense) {
+      GpuRead<unsigned char> onGpu(image->pixels);
       ssrlcv_dense_params dp;
       dp.stride = denseStride;
       dp.sigma = denseSigma;
@@ -127,16 +124,14 @@ class SIFT_FeatureFactory : public FeatureFactory {
       HipSafeCall(rc);
       const uint32_t cap = ssrlcv_sift_dense_max_features(image->size.x, image->size.y, &dp);
       const size_t wsBytes = ssrlcv_hip_sift_dense_workspace_bytes(image->size.x, image->size.y, &dp);
-      ptr::device<unsigned char> workspace((long)(wsBytes ? wsBytes : 1));
       ptr::device<Feature<SIFT_Descriptor>> staging((long)(cap ? cap : 1));
       ptr::device<uint32_t> countDev(1);
+      DeviceScratch workspace(wsBytes);
       uint32_t count = 0;
       HipSafeCall(ssrlcv_hip_sift_dense_u8(image->pixels->device.get(), image->size.x, image->size.y, &dp, workspace.get(), wsBytes,
                                            reinterpret_cast<ssrlcv_sift_feature*>(staging.get()), cap, countDev.get(), nullptr));
       HipCheckError();
       HipSafeCall(ssrlcv_hip_memcpy(&count, countDev.get(), sizeof count, 1));
-      if (keepHost) image->pixels->clear(gpu);
-      else if (origin != gpu) image->pixels->setMemoryState(origin);
       if (count == 0) {
         logger.err << "ERROR: something went wrong and there are 0 keypoints";
         std::exit(0);
@@ -165,29 +160,30 @@ class SIFT_FeatureFactory : public FeatureFactory {
     params.maxKeyPointsPerOctave = slot.perOctave;
     if (!slot.plan) build(slot, image->size, params);
     uint32_t count = 0;
-    for (;;) {
-      HipSafeCall(ssrlcv_hip_sift_extract(slot.plan, image->pixels->device.get(), slot.workspace.get(),
-                                          reinterpret_cast<ssrlcv_sift_feature*>(slot.staging.get()), slot.count.get(),
-                                          nullptr));
-      HipCheckError();
-      // The reference's lists are unbounded; the plan's are sized up front.  A list that outgrew its capacity was
-      // truncated: grow and run again, so that the caller always gets the reference's result.
-      uint32_t overflowMask = 0;
-      int rc = ssrlcv_sift_plan_overflow(slot.plan, slot.workspace.get(), &overflowMask, nullptr);
-      if (rc != SSRLCV_ERR_CAPACITY) {
-        HipSafeCall(rc);
-        break;
+    {
+      GpuRead<unsigned char> onGpu(image->pixels);  // dropped again before the exact-size copy is made
+      for (;;) {
+        HipSafeCall(ssrlcv_hip_sift_extract(slot.plan, image->pixels->device.get(), slot.workspace.get(),
+                                            reinterpret_cast<ssrlcv_sift_feature*>(slot.staging.get()), slot.count.get(),
+                                            nullptr));
+        HipCheckError();
+        // The reference's lists are unbounded; the plan's are sized up front.  A list that outgrew its capacity was
+        // truncated: grow and run again, so that the caller always gets the reference's result.
+        uint32_t overflowMask = 0;
+        int rc = ssrlcv_sift_plan_overflow(slot.plan, slot.workspace.get(), &overflowMask, nullptr);
+        if (rc != SSRLCV_ERR_CAPACITY) {
+          HipSafeCall(rc);
+          break;
+        }
+        const unsigned long px = 4ul * image->size.x * image->size.y;
+        slot.perOctave = slot.perOctave ? slot.perOctave * 2 : (uint32_t)(px / 8);  // default bound is px / 16
+        logger.warn.printf("key-point capacity exceeded (octave mask %u): re-running with %u key points per octave",
+                           overflowMask, slot.perOctave);
+        params.maxKeyPointsPerOctave = slot.perOctave;
+        build(slot, image->size, params);
       }
-      const unsigned long px = 4ul * image->size.x * image->size.y;
-      slot.perOctave = slot.perOctave ? slot.perOctave * 2 : (uint32_t)(px / 8);  // default bound is px / 16
-      logger.warn.printf("key-point capacity exceeded (octave mask %u): re-running with %u key points per octave",
-                         overflowMask, slot.perOctave);
-      params.maxKeyPointsPerOctave = slot.perOctave;
-      build(slot, image->size, params);
+      HipSafeCall(ssrlcv_hip_memcpy(&count, slot.count.get(), sizeof count, 1));
     }
-    HipSafeCall(ssrlcv_hip_memcpy(&count, slot.count.get(), sizeof count, 1));
-    if (keepHost) image->pixels->clear(gpu);
-    else if (origin != gpu) image->pixels->setMemoryState(origin);
     if (count == 0) {
       logger.err << "ERROR: something went wrong and there are 0 keypoints";
       std::exit(0);

@@ -5,13 +5,13 @@
 #pragma once
 #include <fstream>
 #include <string>
+#include "Scoped.hpp"
 #include "Unity.hpp"
 #include "cuda_vec_types.hpp"
 
 namespace ssrlcv {
 inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, std::string dir = "out/") {
-  MemoryState origin = points->getMemoryState();
-  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
+  CpuRead<float3> onCpu(points);
   std::ofstream of;
   of.open(dir + filename + ".ply");
   of << "ply\nformat ascii 1.0\n";
@@ -22,7 +22,6 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, std
   float3* p = points->host.get();
   for (unsigned long i = 0; i < points->size(); i++) of << p[i].x << " " << p[i].y << " " << p[i].z << "\n";
   of.close();
-  if (origin == gpu) points->setMemoryState(gpu);
 }
 
 // The same writer with a normal per vertex (property float nx / ny / nz; MeshFactory::savePoints once normals exist).
@@ -34,9 +33,7 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
     logger.err.printf("writePLY: %lu normals for %lu points", normals->size(), points->size());
     return;
   }
-  MemoryState origin = points->getMemoryState(), originN = normals->getMemoryState();
-  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
-  if (originN == gpu || normals->getFore() == gpu) normals->transferMemoryTo(cpu);
+  CpuRead<float3> onCpu(points), normalsOnCpu(normals);
   std::ofstream of;
   of.open(dir + filename + ".ply");
   of.precision(9);
@@ -51,8 +48,6 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
   for (unsigned long i = 0; i < points->size(); i++)
     of << p[i].x << " " << p[i].y << " " << p[i].z << " " << n[i].x << " " << n[i].y << " " << n[i].z << "\n";
   of.close();
-  if (origin == gpu) points->setMemoryState(gpu);
-  if (originN == gpu) normals->setMemoryState(gpu);
 }
 
 // The same writer with triangles behind the vertices (element face / property list uchar int vertex_indices;
@@ -66,11 +61,8 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
     return;
   }
   const unsigned long numFaces = faces != nullptr ? faces->size() : 0ul;
-  MemoryState origin = points->getMemoryState(), originN = withNormals ? normals->getMemoryState() : cpu;
-  MemoryState originF = numFaces ? faces->getMemoryState() : cpu;
-  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
-  if (withNormals && (originN == gpu || normals->getFore() == gpu)) normals->transferMemoryTo(cpu);
-  if (numFaces && (originF == gpu || faces->getFore() == gpu)) faces->transferMemoryTo(cpu);
+  CpuRead<float3> onCpu(points), normalsOnCpu(normals);
+  CpuRead<uint3> facesOnCpu(numFaces ? faces : ptr::value<Unity<uint3>>());
   std::ofstream of;
   of.open(dir + filename + ".ply");
   of.precision(9);
@@ -92,9 +84,6 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
   const uint3* f = numFaces ? faces->host.get() : nullptr;
   for (unsigned long i = 0; i < numFaces; i++) of << "3 " << f[i].x << " " << f[i].y << " " << f[i].z << "\n";
   of.close();
-  if (origin == gpu) points->setMemoryState(gpu);
-  if (withNormals && originN == gpu) normals->setMemoryState(gpu);
-  if (numFaces && originF == gpu) faces->setMemoryState(gpu);
 }
 
 // The same writer with a grey per vertex behind the normals (property uchar red / green / blue, the grey three times;
@@ -108,12 +97,9 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
     return;
   }
   const unsigned long numFaces = faces != nullptr ? faces->size() : 0ul;
-  MemoryState origin = points->getMemoryState(), originN = withNormals ? normals->getMemoryState() : cpu;
-  MemoryState originF = numFaces ? faces->getMemoryState() : cpu, originC = colors->getMemoryState();
-  if (origin == gpu || points->getFore() == gpu) points->transferMemoryTo(cpu);
-  if (withNormals && (originN == gpu || normals->getFore() == gpu)) normals->transferMemoryTo(cpu);
-  if (numFaces && (originF == gpu || faces->getFore() == gpu)) faces->transferMemoryTo(cpu);
-  if (originC == gpu || colors->getFore() == gpu) colors->transferMemoryTo(cpu);
+  CpuRead<float3> onCpu(points), normalsOnCpu(normals);
+  CpuRead<uint3> facesOnCpu(numFaces ? faces : ptr::value<Unity<uint3>>());
+  CpuRead<unsigned char> colorsOnCpu(colors);
   std::ofstream of;
   of.open(dir + filename + ".ply");
   of.precision(9);
@@ -137,9 +123,5 @@ inline void writePLY(std::string filename, ptr::value<Unity<float3>> points, ptr
   const uint3* f = numFaces ? faces->host.get() : nullptr;
   for (unsigned long i = 0; i < numFaces; i++) of << "3 " << f[i].x << " " << f[i].y << " " << f[i].z << "\n";
   of.close();
-  if (origin == gpu) points->setMemoryState(gpu);
-  if (withNormals && originN == gpu) normals->setMemoryState(gpu);
-  if (numFaces && originF == gpu) faces->setMemoryState(gpu);
-  if (originC == gpu) colors->setMemoryState(gpu);
 }
 }  // namespace ssrlcv
