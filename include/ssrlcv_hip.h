@@ -60,7 +60,8 @@ typedef void* ssrlcv_stream_t; /* hipStream_t */
  *      mesh render: mesh_render (+ its workspace query), image_residual;
  *      surface simplification: dsm_simplify_errors, dsm_simplify_mesh (+ its workspace query);
  *      terrain filter: dsm_morphology, dsm_terrain (+ their workspace queries), dsm_subtract;
- *      shift search: shift_search (+ its workspace query), shift_table_bytes, shift_pick_host */
+ *      shift search: shift_search (+ its workspace query), shift_table_bytes, shift_pick_host;
+ *      surface objects: dsm_objects (+ its workspace query), object_measures_host */
 #define SSRLCV_HIP_ABI_VERSION 4
 int ssrlcv_hip_abi_version(void);
 const char* ssrlcv_hip_version(void);
@@ -1707,6 +1708,122 @@ int ssrlcv_hip_dsm_terrain(const float* height, uint32_t w, uint32_t h, const ss
                            uint8_t* level /* may be NULL */, float* opened /* may be NULL */, void* workspace, size_t workspaceBytes,
                            ssrlcv_stream_t stream);
 int ssrlcv_hip_dsm_subtract(const float* a, const float* b, uint32_t w, uint32_t h, float* out, ssrlcv_stream_t stream);
+
+/* ---- surface objects: the `objects` map of "terrain filter" (height - terrain) says how high something stands above the ground
+ * at every cell; this section says WHAT stands there: one record per object -- a connected footprint of cells at least minHeight
+ * above the ground -- with its place, area, outline length, moments and height sums, and a map of the objects' numbers.  An
+ * inventory of buildings and trees, without reading the map back.  Everything a record holds is an integer sum, an integer
+ * minimum or maximum, or a selected bit pattern, so it does not depend on the order of summation: csrc/objects.hip is held to a
+ * numpy restatement byte for byte (tests/objects_ref.py, tests/test_gpu_objects.py), and that to a plain loop over cells.
+ * Maps as everywhere in this file: float[w h], pitch w, a cell invalid iff its bits are 0x7FC00000.
+ *   1 members   a cell is a member iff it is valid and v >= minHeight in float32.  The comparison is false for a NaN, so no
+ *               member is a NaN (a non-canonical NaN is a valid cell and never a member); +inf is a member.  minHeight = -inf
+ *               takes every valid cell that is no NaN, minHeight = +inf the +inf cells alone.
+ *   2 objects   the components of "disparity post-filters" items 1-2 with maxDiff, of the map that holds v at members and the
+ *               invalid pattern everywhere else: 4-connectivity, and the object's `label` is that section's label, the smallest
+ *               raster index y w + x of its cells.  maxDiff = +inf joins a footprint whatever its roof does; a finite value parts
+ *               a roof from a tree that leans on it.  Two +inf cells do not link (inf - inf is a NaN), as that section says.
+ *   3 kept      an object is kept iff cells >= minCells (minCells = 0 behaves as 1).  Kept objects are numbered 0, 1, ... in
+ *               ascending label.  *count_dev = the full number kept.  Only the first min(count, capacity) records are written, in
+ *               that order; nothing behind records[capacity) is touched; records may be NULL with capacity 0: the truncation
+ *               contract of ssrlcv_hip_stereo_matches.
+ *   4 ids       (uint32[w h], may be NULL; if given, every entry is written) a cell of a kept object holds the object's number;
+ *               a non-member holds UINT32_MAX, and so does a member of a dropped object.  The numbers do not depend on
+ *               capacity: an object numbered at or above it still has its number in ids.
+ *   5 record    ssrlcv_object_record, over the object's cells (x, y):
+ *     label, cells            as above; 1 <= cells <= w h <= 2^30.
+ *     minX, minY, maxX, maxY  the bounding box, inclusive; below 65536.
+ *     sumX, sumY, sumXX, sumXY, sumYY   the sums of x, y, x x, x y, y y of the integer cell coordinates: sumX, sumY <= 2^30 (2^16
+ *                             - 1) < 2^46; sumXX, sumXY, sumYY <= 2^30 (2^16 - 1)^2 < 2^62.
+ *     perimeter               the number of cell sides whose other side lies outside the map or is not a cell of the same object;
+ *                             at most 2 cells + 2 <= 2^31 + 2 (a 4-connected set), and the 2 w + 2 h sides of the grid are below 2^18.
+ *     peak, peakIndex         the bits of the value with the largest order key k(f) of the median filter ("disparity
+ *                             post-filters" item 4), and the smallest raster index that holds those bits.  -0 < +0.
+ *     low                     the bits of the value with the smallest key.
+ *     quantise                heights are quantised exactly as "shift search" quantises: t = v * scale, one float32
+ *                             multiplication; the cell takes part iff fabsf(t) <= 65536.0f; then q = (int32)rintf(t), ties to even.
+ *     clipped                 the members that fail that test (+inf among them); they count in `clipped` and in nothing below.
+ *     sumQ, sumQQ             the sums of q and of q q over the cells that take part: |sumQ| <= 2^30 2^16 = 2^46, sumQQ <= 2^30
+ *                             2^32 = 2^62.
+ *     reserved                0.
+ *   6 limits    w, h <= 65536 and w h <= 2^30.  With these every sum fits its field, as the bounds above say.
+ *   7 measures  ssrlcv_object_measures_host (host only, in double, no device) turns one record into lengths, areas and shapes.
+ *               Only + - * / and sqrt, every operation rounded on its own, nothing contracted, no libm call; u(k) is (double)k of
+ *               an integer field (a sum above 2^53 rounds to nearest even there), c = (double)frame->cell, s = (double)scale:
+ *                 n = u(cells);  cc = c * c;  area = n * cc;  perimeterLength = u(perimeter) * c;
+ *                 compactness = (12.566370614359172 * area) / (perimeterLength * perimeterLength)      4 pi area / perimeter^2
+ *                 centroidX = u(sumX) / n;  centroidY = u(sumY) / n                                     in cells, corner (0, 0) = 0
+ *                 a = (centroidX + 0.5) * c;  b = (centroidY + 0.5) * c;  world[k] = (origin[k] + a * ex[k]) + b * ey[k]
+ *               -- cell centres as ssrlcv_hip_dsm_points places a cell, on the frame's plane (the object heights are relative to the
+ *               terrain and say nothing about the height of the ground) --
+ *                 m = u(cells - clipped);  meanQ = u(sumQ) / m;  meanHeight = meanQ / s;  volume = (u(sumQ) / s) * cc;
+ *                 var = u(sumQQ) / m - meanQ * meanQ;  rmsHeight = sqrt(var < 0 ? 0 : var) / s          about the mean
+ *                 mxx = u(sumXX) / n - centroidX * centroidX;  mxy = u(sumXY) / n - centroidX * centroidY;
+ *                 myy = u(sumYY) / n - centroidY * centroidY                                            in cells^2
+ *                 t = 0.5 * (mxx + myy);  d = 0.5 * (mxx - myy);  r = sqrt(d * d + mxy * mxy);
+ *                 lambdaMajor = t + r;  l = t - r;  lambdaMinor = l < 0 ? 0 : l;
+ *                 (vx, vy) = d >= 0 ? (d + r, mxy) : (mxy, r - d);  if vx < 0 both change sign;  g = sqrt(vx * vx + vy * vy);
+ *                 (axisX, axisY) = g > 0 ? (vx / g, vy / g) : (1, 0)                                    the major axis, axisX >= 0
+ *                 elongation = lambdaMinor > 0 ? sqrt(lambdaMajor / lambdaMinor) : lambdaMajor > 0 ? +inf : 1
+ *               A record with cells - clipped = 0 has meanHeight and rmsHeight a NaN (0 / 0) and volume 0; it is not refused.
+ *               Refused with SSRLCV_ERR_INVALID_ARG: a NULL record, frame or out, a refused frame ("surface model"), a scale that
+ *               is not finite and > 0, cells = 0 or clipped > cells.  `out` is untouched on error.
+ * Refusals of the device call, decided on the host before any launch, the parameters before the sizes before the buffers, invalid
+ * before unsupported within each: SSRLCV_ERR_INVALID_ARG for params NULL, minHeight a NaN, maxDiff a NaN or negative, scale not
+ * finite or not > 0; then SSRLCV_ERR_UNSUPPORTED for w or h above 65536 or w h above 2^30; then SSRLCV_ERR_INVALID_ARG for a NULL
+ * count_dev; a map of 0 cells then writes *count_dev = 0 and is SSRLCV_OK; then SSRLCV_ERR_INVALID_ARG for a NULL map or workspace,
+ * or for records that are NULL with capacity > 0 or not 8-byte aligned (their 64-bit sums are added in place); then
+ * SSRLCV_ERR_WORKSPACE for a short workspace.
+ * Workspace (host only; computed in size_t; 0 for a refused or empty size), a256 and c as in "disparity mesh":
+ *     3 a256(4 w h) + c(w h)
+ *   the member map, which gives its place to the objects' numbers once the labelling has read it; the labels; the component
+ *   counts; the tables of the compaction.  It may hold anything on entry.
+ * Execution: asynchronous on `stream`; no host synchronisation; no block waits for another; integer atomics only; bit-equal run
+ * to run.  A mask pass writes the member map; the labelling is that of "disparity post-filters", called, not copied; the kept
+ * roots go through one ordered compaction (csrc/compact.h), which numbers them and initialises their records; the reduction
+ * walks the map in 64 x 16 tiles.  There a cell's contributions merge first inside its wave over runs of adjacent lanes of one
+ * tile-local component (one ballot gives the runs, shuffles add over them, as k_cc_tile and k_dsm_scatter do), next in LDS per tile-local root,
+ * and each (tile, object, field) is flushed once to the record: 64-bit atomic adds for the seven sums, a 64-bit atomic max on
+ * (key << 32) | (0xFFFFFFFF - index) for the peak, 32-bit atomic min, max and add for the box, `low`, `perimeter` and `clipped`;
+ * a tile-local component that is the whole object is stored without atomics.  The perimeter compares final labels, read with a
+ * halo of one cell.  The same pass writes ids.  A record of an object numbered at or above capacity is never touched.  A last
+ * pass, a thread a record, turns the keys back into bits and writes *count_dev.  Capped grids stride over their items.
+ * Out of scope: 8-connectivity; outlines as polygons; per-object medians or other quantiles; classifying an object as building or
+ * vegetation; objects of a cloud instead of a map; merging objects across tiles of a larger mosaic. */
+typedef struct {
+  float minHeight;   /* no NaN; -inf and +inf are legal */
+  float maxDiff;     /* >= 0, +inf is legal */
+  float scale;       /* finite, > 0: quanta a height unit */
+  uint32_t minCells; /* 0 behaves as 1 */
+} ssrlcv_object_params; /* 16 bytes */
+typedef struct {
+  uint32_t label, cells;           /* smallest raster index of the object; number of its cells */
+  uint32_t minX, minY, maxX, maxY; /* bounding box, inclusive */
+  uint32_t perimeter, clipped;
+  uint32_t peakIndex;
+  float peak;
+  float low;
+  uint32_t reserved; /* 0 */
+  uint64_t sumX, sumY, sumXX, sumXY, sumYY;
+  int64_t sumQ;
+  uint64_t sumQQ;
+} ssrlcv_object_record; /* 104 bytes */
+typedef struct {
+  double area, perimeterLength, compactness;
+  double centroidX, centroidY; /* in cells */
+  double world[3];             /* the centroid on the frame's plane */
+  double meanHeight, volume, rmsHeight;
+  double mxx, mxy, myy;        /* central second moments, cells^2 */
+  double lambdaMajor, lambdaMinor;
+  double axisX, axisY;         /* unit vector of the major axis in cells, axisX >= 0 */
+  double elongation;
+} ssrlcv_object_measures; /* 152 bytes */
+size_t ssrlcv_hip_dsm_objects_workspace_bytes(uint32_t w, uint32_t h);
+int ssrlcv_hip_dsm_objects(const float* objects, uint32_t w, uint32_t h, const ssrlcv_object_params* params, uint32_t* ids /* may be NULL */,
+                           ssrlcv_object_record* records, uint32_t capacity, uint32_t* count_dev, void* workspace, size_t workspaceBytes,
+                           ssrlcv_stream_t stream);
+int ssrlcv_object_measures_host(const ssrlcv_object_record* record, const ssrlcv_dsm_frame* frame, float scale,
+                                ssrlcv_object_measures* out); /* host only */
 
 /* The reference's key-point lists are unbounded (thrust-sized); the plan's are sized at creation
  * (ssrlcv_sift_params.maxKeyPointsPerOctave, default: a density bound).  If a list outgrew its capacity during the last

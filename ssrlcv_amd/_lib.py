@@ -75,7 +75,8 @@ def load():
                      "ssrlcv_hip_dsm_ortho_workspace_bytes", "ssrlcv_hip_difference_stats_workspace_bytes",
                      "ssrlcv_hip_register_terms_workspace_bytes", "ssrlcv_hip_mesh_render_workspace_bytes",
                      "ssrlcv_hip_dsm_simplify_mesh_workspace_bytes", "ssrlcv_hip_dsm_morphology_workspace_bytes",
-                     "ssrlcv_hip_dsm_terrain_workspace_bytes", "ssrlcv_shift_table_bytes", "ssrlcv_hip_shift_search_workspace_bytes"):
+                     "ssrlcv_hip_dsm_terrain_workspace_bytes", "ssrlcv_shift_table_bytes", "ssrlcv_hip_shift_search_workspace_bytes",
+                     "ssrlcv_hip_dsm_objects_workspace_bytes"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.ssrlcv_sift_plan_max_features.restype = ctypes.c_uint32
         _lib.ssrlcv_sift_dense_max_features.restype = ctypes.c_uint32
@@ -137,4 +138,5 @@ EXPORTED = [
     "ssrlcv_hip_dsm_morphology_workspace_bytes", "ssrlcv_hip_dsm_morphology", "ssrlcv_hip_dsm_terrain_workspace_bytes",
     "ssrlcv_hip_dsm_terrain", "ssrlcv_hip_dsm_subtract",
     "ssrlcv_shift_table_bytes", "ssrlcv_hip_shift_search_workspace_bytes", "ssrlcv_hip_shift_search", "ssrlcv_shift_pick_host",
+    "ssrlcv_hip_dsm_objects_workspace_bytes", "ssrlcv_hip_dsm_objects", "ssrlcv_object_measures_host",
 ]

@@ -1284,6 +1284,76 @@ def dsm_subtract(a_d, b_d, out=None):
     return res
 
 
+# ------------------------------------------------------------------ surface objects
+class ObjectParams(ctypes.Structure):
+    """ssrlcv_object_params: a cell is a member iff it is valid and v >= minHeight; members link as disparity_components links with
+    maxDiff; q = rint(v x scale); an object of fewer than minCells cells is dropped (0 behaves as 1)"""
+    _fields_ = [("minHeight", c_f32), ("maxDiff", c_f32), ("scale", c_f32), ("minCells", c_u32)]
+
+
+class ObjectRecord(ctypes.Structure):
+    """ssrlcv_object_record: one kept object"""
+    _fields_ = [("label", c_u32), ("cells", c_u32), ("minX", c_u32), ("minY", c_u32), ("maxX", c_u32), ("maxY", c_u32), ("perimeter", c_u32),
+                ("clipped", c_u32), ("peakIndex", c_u32), ("peak", c_f32), ("low", c_f32), ("reserved", c_u32), ("sumX", ctypes.c_uint64),
+                ("sumY", ctypes.c_uint64), ("sumXX", ctypes.c_uint64), ("sumXY", ctypes.c_uint64), ("sumYY", ctypes.c_uint64),
+                ("sumQ", ctypes.c_int64), ("sumQQ", ctypes.c_uint64)]
+
+
+class ObjectMeasures(ctypes.Structure):
+    """ssrlcv_object_measures: what ssrlcv_object_measures_host makes of a record"""
+    _fields_ = [(name, ctypes.c_double) for name in ("area", "perimeterLength", "compactness", "centroidX", "centroidY")] + \
+               [("world", ctypes.c_double * 3)] + \
+               [(name, ctypes.c_double) for name in ("meanHeight", "volume", "rmsHeight", "mxx", "mxy", "myy", "lambdaMajor", "lambdaMinor",
+                                                     "axisX", "axisY", "elongation")]
+
+
+OBJECT_RECORD = np.dtype([("label", "<u4"), ("cells", "<u4"), ("minX", "<u4"), ("minY", "<u4"), ("maxX", "<u4"), ("maxY", "<u4"),
+                          ("perimeter", "<u4"), ("clipped", "<u4"), ("peakIndex", "<u4"), ("peak", "<f4"), ("low", "<f4"), ("reserved", "<u4"),
+                          ("sumX", "<u8"), ("sumY", "<u8"), ("sumXX", "<u8"), ("sumXY", "<u8"), ("sumYY", "<u8"), ("sumQ", "<i8"), ("sumQQ", "<u8")])
+assert ctypes.sizeof(ObjectParams) == 16 and ctypes.sizeof(ObjectRecord) == 104 == OBJECT_RECORD.itemsize and ctypes.sizeof(ObjectMeasures) == 152
+
+
+def dsm_objects(objects_d, min_height, max_diff=float("inf"), min_cells=1, scale=256.0, capacity=None, want_ids=True, workspace=None):
+    """The objects of an object-height map (ssrlcv_hip_dsm_objects; include/ssrlcv_hip.h "surface objects"): the 4-connected
+    components of the cells that are valid and >= min_height, linked where they differ by at most max_diff; those of at least
+    min_cells cells are numbered in raster order of their first cells.  capacity None: a first call with capacity 0 counts them and
+    a second one writes every record; a number: one call, at most that many records.
+    -> (count: the full number kept; ids int32 (h, w) holding the uint32 bits: the object's number, -1 for a cell of none, or None;
+    records: an OBJECT_RECORD array of min(count, capacity)).  The workspace is reused if it is large enough.  One
+    synchronisation a call (the count)."""
+    h, w = _disparity_map(objects_d)
+    assert isinstance(min_cells, int) and not isinstance(min_cells, bool) and 0 <= min_cells <= 0xFFFFFFFF  # c_u32 would wrap it
+    assert capacity is None or (isinstance(capacity, int) and not isinstance(capacity, bool) and 0 <= capacity <= 0xFFFFFFFF)
+    p = ObjectParams(float(min_height), float(max_diff), float(scale), min_cells)
+    ws = _filter_workspace(LIB.ssrlcv_hip_dsm_objects_workspace_bytes, w, h, workspace)
+    ids = torch.empty((h, w), dtype=torch.int32, device="cuda") if want_ids else None
+    count_d = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def call(cap, want):
+        records = torch.empty(max(cap * 13, 1), dtype=torch.int64, device="cuda")  # 104 bytes a record, 8-byte aligned
+        check(LIB.ssrlcv_hip_dsm_objects(ptr(objects_d) if w * h else c_vp(0), c_u32(w), c_u32(h), ctypes.byref(p), ptr(ids) if want else c_vp(0),
+                                         ptr(records) if cap else c_vp(0), c_u32(cap), ptr(count_d), ptr(ws), c_sz(ws.numel()), stream_ptr()))
+        return int(count_d.cpu().numpy().view(np.uint32)[0]), records
+
+    if capacity is None:
+        capacity = call(0, False)[0]
+    count, records = call(capacity, want_ids)
+    got = min(count, capacity)
+    return count, ids, records.cpu().numpy().view(np.uint8)[:got * 104].view(OBJECT_RECORD).copy()
+
+
+def object_measures(record, frame, scale=256.0):
+    """ssrlcv_object_measures_host (host arithmetic: needs no GPU): area, perimeter length, compactness, centroid in cells and on the
+    frame's plane in the world, mean height, volume and RMS height, the central second moments, their eigenvalues, the major
+    axis and the elongation of one record (a row of an OBJECT_RECORD array or an ObjectRecord).  -> an ObjectMeasures."""
+    if not isinstance(record, ObjectRecord):
+        raw = np.asarray(record, OBJECT_RECORD).reshape(1).tobytes()
+        record = ObjectRecord.from_buffer_copy(raw)
+    out = ObjectMeasures()
+    check(LIB.ssrlcv_object_measures_host(ctypes.byref(record), ctypes.byref(frame), c_f32(float(scale)), ctypes.byref(out)))
+    return out
+
+
 # ------------------------------------------------------------------ shift search
 class ShiftParams(ctypes.Structure):
     """ssrlcv_shift_params: q = rint(height x scale); shifts (centerX + kx, centerY + ky), kx, ky = -radius .. radius, in cells of

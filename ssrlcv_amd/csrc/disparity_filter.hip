@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include "ssrlcv_hip.h"
 #include "align256.h"
+#include "cc_label.h"
 #include "device_math.h"
 #include "order_key.h"
 
@@ -484,6 +485,14 @@ void label_components(const float* disparity, uint32_t w, uint32_t h, float maxD
 bool bad_max_diff(float maxDiff) { return !(maxDiff >= 0.0f); }  // a NaN or a negative number
 
 }  // namespace
+
+// the same labelling for objects.hip (cc_label.h)
+namespace svcc {
+static_assert(kTileW == ::kTileW && kTileH == ::kTileH, "cc_label.h names k_cc_tile's tile");
+void label_components(const float* disparity, uint32_t w, uint32_t h, float maxDiff, uint32_t* labels, uint32_t* counts, hipStream_t stream) {
+  ::label_components(disparity, w, h, maxDiff, labels, counts, stream);
+}
+}  // namespace svcc
 
 extern "C" {
 

@@ -378,6 +378,47 @@ class MeshFactory {
     return out;
   }
 
+  // ---- surface objects (include/ssrlcv_hip.h "surface objects"): what stands on the terrain, one record an object.
+  // extractObjects(objects, w, h, params) takes objectHeights' map: the 4-connected footprints of the cells at least
+  // params.minHeight high, those of params.minCells cells and more numbered in raster order of their first cells.  A first call
+  // counts them, a second one writes every record (host memory, in that order).  *ids, when asked for (state gpu): the number of
+  // a cell's object, UINT32_MAX for a cell of none.  false for an empty grid or a refused call; the map is left in the state it
+  // came in.
+  static bool extractObjects(ptr::value<Unity<float>> objects, unsigned int w, unsigned int h, const ssrlcv_object_params& params,
+                             std::vector<ssrlcv_object_record>& records, ptr::value<Unity<uint32_t>>* ids = nullptr) {
+    const unsigned long cells = (unsigned long)w * h;
+    records.clear();
+    if (ids) *ids = ptr::value<Unity<uint32_t>>();
+    if (objects == nullptr || cells == 0 || objects->size() != cells) {
+      logger.err << "MeshFactory::extractObjects: the map has w h entries";
+      return false;
+    }
+    GpuRead<float> onGpu(objects);
+    ptr::device<uint32_t> count(1);
+    DeviceScratch ws(ssrlcv_hip_dsm_objects_workspace_bytes(w, h));
+    int status = ssrlcv_hip_dsm_objects(objects->device.get(), w, h, &params, nullptr, nullptr, 0, count.get(), ws.get(), ws.bytes(), nullptr);
+    if (status != SSRLCV_OK) {
+      logger.err.printf("MeshFactory::extractObjects: refused (%s)", ssrlcv_hip_status_string(status));
+      return false;
+    }
+    uint32_t n = 0;
+    HipSafeCall(ssrlcv_hip_memcpy(&n, count.get(), sizeof n, 1));
+    if (ids) *ids = ptr::value<Unity<uint32_t>>(nullptr, cells, gpu);
+    ptr::device<uint64_t> device((unsigned long)(n ? n : 1) * (sizeof(ssrlcv_object_record) / 8));  // 8-byte aligned: the sums are added in place
+    HipSafeCall(ssrlcv_hip_dsm_objects(objects->device.get(), w, h, &params, ids ? (*ids)->device.get() : nullptr, (ssrlcv_object_record*)device.get(), n,
+                                       count.get(), ws.get(), ws.bytes(), nullptr));
+    records.resize(n);
+    if (n) HipSafeCall(ssrlcv_hip_memcpy(records.data(), device.get(), (size_t)n * sizeof(ssrlcv_object_record), 1));
+    HipSafeCall(ssrlcv_hip_device_synchronize());
+    return true;
+  }
+
+  // area, outline length, compactness, centroid (cells, and on the frame's plane in the world), mean height, volume, RMS height,
+  // second moments, major axis and elongation of one record; host arithmetic, no device.  `scale` is the params' scale
+  static bool objectMeasures(const ssrlcv_object_record& record, const ssrlcv_dsm_frame& frame, float scale, ssrlcv_object_measures& out) {
+    return ssrlcv_object_measures_host(&record, &frame, scale, &out) == SSRLCV_OK;
+  }
+
   // the valid cells of a height map become this factory's points, in raster order: the vertex numbering of
   // DisparityFactory::generateMesh(height, 1, maxJump), so that mesh is the surface of these points
   void setPointsFromHeightMap(ptr::value<Unity<float>> height, const ssrlcv_dsm_frame& frame) {

@@ -546,6 +546,28 @@ def surface_terrain(model_or_height, frame, max_radius, slope, initial, maximum,
             "radii": radii, "thresholds": thresholds}
 
 
+_MEASURES = ("area", "perimeterLength", "compactness", "centroidX", "centroidY", "meanHeight", "volume", "rmsHeight", "mxx", "mxy", "myy",
+             "lambdaMajor", "lambdaMinor", "axisX", "axisY", "elongation")
+
+
+def surface_objects(terrain_or_objects, frame, min_height, max_diff=float("inf"), min_cells=1, scale=256.0):
+    """What stands on the terrain (include/ssrlcv_hip.h "surface objects"): the inventory of surface_terrain's dictionary, or of its
+    `objects` map alone.  An object is a 4-connected footprint of cells at least min_height above the ground, joined where
+    neighbours differ by at most max_diff (inf: a footprint whatever its roof does); those of fewer than min_cells cells are
+    dropped; heights are summed as rint(height x scale).  A first call counts the objects, a second one writes their records.
+    -> dict(count; ids int32 (h, w): the object's number, in raster order of the objects' first cells, -1 for a cell of none;
+    records: a capi.OBJECT_RECORD array; measures: one dictionary a record -- area, perimeterLength, compactness, centroidX,
+    centroidY, world (3 floats), meanHeight, volume, rmsHeight, mxx, mxy, myy, lambdaMajor, lambdaMinor, axisX, axisY, elongation
+    -- in the frame's units, from capi.object_measures)."""
+    objects = terrain_or_objects["objects"] if isinstance(terrain_or_objects, dict) else terrain_or_objects
+    count, ids, records = capi.dsm_objects(objects, min_height, max_diff, int(min_cells), scale)
+    measures = []
+    for record in records:
+        m = capi.object_measures(record, frame, scale)
+        measures.append(dict({name: float(getattr(m, name)) for name in _MEASURES}, world=[float(v) for v in m.world]))
+    return {"count": count, "ids": ids, "records": records, "measures": measures}
+
+
 def surface_photo_check(model, frame, ortho, image, camera, max_jump=None, max_extent=8, want_map=False):
     """How well a textured surface model predicts a view's own pixels -- an accuracy measure that needs no reference surface: the
     model's mesh takes the greys of its ortho-image (surface_colors of surface_ortho's `ortho`), is drawn into `camera`
